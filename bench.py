@@ -1,12 +1,16 @@
 #!/usr/bin/env python3
 """Benchmark of the enhance() hot path on MI355X (BASELINE.json metric: 48 kHz audio frames/s, hop = 480).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One "step" = one enhance() over one batch of B synthetic noisy 48 kHz clips already resident in HBM
 (config.workload: DeepFilterNet3, B=256 x 10 s per GPU = BASELINE.json configs[1]; weak scaling over GPUs: every rank
 owns its own B clips, no data-path collective; the finished waveforms are gathered to rank 0 over RCCL, overlapped with
-the next step).  Prints ONE JSON line on rank 0 (contract in the task statement), including
+the next step).  Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times the K steps and prints the headline
+(metric, value, unit, higher_is_better, dtype, ms_per_step = wall time of the K timed steps / K, the workload); inputs and
+weights are seeded, so the same arguments compute the same thing every run.  --dump-outputs DIR writes what the last timed
+step returned (DIR/enhanced.npy: a fixed, seeded sample of 16 whole clips, float32).  --full measures the rest after the
+timed steps as well (minutes; the headline keys keep their meaning).  Keys of the line:
   dtype         "f32" data and accumulation; the dense contractions of the GRU projections / recurrences and of the fused DF-encoder
                 convolutions run as fp16-split MFMAs (x = hi + lo in f16, 3 products, fp32 accumulate: ~2^-21 relative).
                 exact_fp32_ms_per_step: the same step with every contraction on the exact fp32 kernels (DFX_EXACT_FP32=1), same run.
@@ -27,7 +31,10 @@ import os
 import sys
 import time
 
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")  # one hardware queue per engine stream (read when HIP initialises)
+# one hardware queue per engine stream (read when HIP initialises).  A smaller inherited value (ROCm's default is 4) would put the timed handle
+# on the event-synchronised GRU phase, twice as slow: raised to 24 here, for this process and the ones it starts.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
@@ -108,8 +115,12 @@ def cpu_baseline(p, sd, clips: int, seconds: float, keep=None) -> dict:
 def main() -> None:
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=_positive, default=20, help="timed steps")
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--full", action="store_true", help="after the headline also measure everything else: rooflines, per-kernel breakdown, exact fp32, "
+                                                        "host to host, BASELINE configs[3] / [4], the CPU baseline and parity against the oracle")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step returned as DIR/<name>.npy (float32; "
+                                                                          "a fixed, seeded sample of at most 64 MB)")
     ap.add_argument("--batch", type=int, default=256, help="clips per GPU")
     ap.add_argument("--seconds", type=float, default=10.0, help="clip length")
     ap.add_argument("--model", default="df3", choices=["df3", "defaults"])
@@ -167,11 +178,12 @@ def main() -> None:
     from deepfilternet_amd.distributed import enhance_sharded
 
     pending = [None, None]  # the gather of step i overlaps step i+1 (RCCL runs on its own stream)
+    gathered = [None, None]  # what the gather of the last step k & 1 handed rank 0
 
     def step(i: int):
         k = i & 1
         if pending[k] is not None:
-            pending[k].wait()
+            gathered[k] = pending[k].wait() if args.dump_outputs else None
             pending[k] = None
         if gather:
             pending[k] = enhance_sharded(model, df_state, x, presharded=True, counts=[B] * world, gather=True, dst=0)
@@ -181,7 +193,7 @@ def main() -> None:
     def drain():
         for k in (0, 1):
             if pending[k] is not None:
-                pending[k].wait()
+                gathered[k] = pending[k].wait() if args.dump_outputs else None
                 pending[k] = None
 
     if args.host_io_only:
@@ -191,8 +203,9 @@ def main() -> None:
         step(i)
     drain()
     torch.cuda.synchronize()
+    profile_loop = args.full or args.main_only   # a plain run times the steps alone
     _lib.prof_reset()
-    # two hipEventRecords per step on the launch stream around the finishing kernel; everything else untouched.  (Since round 3 enhance()
+    # (--full, --main-only) two hipEventRecords per step on the launch stream around the finishing kernel; everything else untouched.  (Since round 3 enhance()
     # applies the deep filter + gains INSIDE the ISTFT kernel, dfx_k_synthesis_rows; with DFX_FUSE_DFA=0 the separate deep-filter kernel is
     # timed in the loop as before.)
     # (round 6: and two around the STFT kernel, the first kernel of a pass: the serialised-step figure of `rooflines.dfx_k_analysis` runs it behind a
@@ -201,7 +214,8 @@ def main() -> None:
     loop_kernels = ["dfx_k_df_apply", "dfx_k_synthesis", "dfx_k_analysis"]
     if os.environ.get("DFX_BENCH_PROF_ANALYSIS") == "0":   # dev: the A/B of the comment above
         loop_kernels.remove("dfx_k_analysis")
-    _lib.prof_enable(loop_kernels)
+    if profile_loop:
+        _lib.prof_enable(loop_kernels)
     if dist is not None:
         dist.barrier()
     torch.cuda.synchronize()
@@ -233,6 +247,16 @@ def main() -> None:
     assert torch.isfinite(y).all()
     gru_persistent = bool(model.query(model.Q_GRU_PERSISTENT))
     model.check()  # raises if a kernel of the loop reported a fault (fp16-split range, a flag wait that timed out): results would be invalid
+    if args.dump_outputs and rank == 0:   # what a caller of the timed path received from the last step (rank 0: the gathered batch)
+        dump_outputs(args.dump_outputs, gathered[(args.steps - 1) & 1] if gather else y)
+
+    if not (args.full or args.main_only):
+        if rank == 0:
+            print(json.dumps(headline(args, p, world, B, T, Tf, dt, per_rank_ms, gather, gru_persistent)), flush=True)
+        if dist is not None:
+            dist.barrier()
+            dist.destroy_process_group()
+        return
 
     # ---- multi-GPU: the same timed loop without the final gather (so that a scaling run can tell compute from the collective)
     no_gather_ms = None
@@ -569,30 +593,19 @@ def main() -> None:
     torch.cuda.empty_cache()
 
     frames = world * B * (T // HOP) * args.steps
-    out = {
-        "metric": "48 kHz audio frames/sec (hop=480), DeepFilterNet3 enhance()",
-        "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-        "dtype": "f32 (storage and accumulation; GRU projections / recurrences, the fused DF-encoder convolutions and the pointwise halves of the ERB separable convolutions as fp16-split MFMAs: "
-                 "x = hi + lo in f16, hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16, ~2^-21 relative; see exact_fp32_ms_per_step)",
+    out = headline(args, p, world, B, T, Tf, dt, per_rank_ms, gather, gru_persistent)
+    out.update({
         "exact_fp32_ms_per_step": exact_ms, "exact_fp32_rms_diff_of_output": exact_diff, "exact_fp32_gru_phase_form": exact_form,
-        "data": "synthetic (seeded harmonic+noise 48 kHz audio, seeded random DeepFilterNet3 weights)",
-        "config": {"workload": f"DeepFilterNet3 ({'recalled shipped shape, conv_ch=64' if args.model == 'df3' else 'code defaults'}) "
-                               f"enhance(pad=True), batch={B} clips x {args.seconds:g} s @48 kHz per GPU, {Tf} STFT frames per clip",
-                   "batch_per_gpu": B, "clip_seconds": args.seconds, "global_batch": B * world,
-                   "parallelism": f"clips sharded over {world} GPU(s); " + ("async RCCL gather of waveforms to rank 0" if gather else "no collective"),
-                   "inputs_resident_in_hbm": True},
-        "ms_per_step_without_gather": no_gather_ms, "ms_per_step_host_consumer": host_consumer_ms, "per_rank_ms_per_step": [round(v, 4) for v in per_rank_ms],
+        "ms_per_step_without_gather": no_gather_ms, "ms_per_step_host_consumer": host_consumer_ms,
         "rccl_ranks": (dist.get_world_size() if dist is not None else 1),
         "enqueue": {"policy": "one big pass in flight per model handle (a call first waits, on the host, for the previous pass to drain) and the GRU phase "
                               "of a pass is enqueued once its encoder front has run: packets waiting at the head of the pass's ~13 hardware queues slow "
                               "the kernels that are running; every step of the timed loop still runs to completion inside the timed region",
                     "ms_per_step_with_free_enqueue_ahead": ahead_ms, "switch": "DFX_ENQUEUE_AHEAD=1"},
         "host_io": host_io,
-        "gru_phase_form": (("persistent flag-synchronised launch (dfx_k_gru_seq_p2: recurrences on pairs of CUs)" if os.environ.get("DFX_GRU_PAIR", "1")[:1] != "0" and B > 16 else "persistent flag-synchronised launch (dfx_k_gru_seq)") if gru_persistent else "event-synchronised launches per (layer, time chunk)"),
         "roofline": roofline, "rooflines": rooflines, "configs": configs, "cpu_baseline": cpu, "parity": parity, "kernels": kern,
         "realtime_factor": frames / dt / 100.0,
-    }
+    })
     # the numbers a reader of the line's tail looks for, once more at the very end
     def _g(d, *ks):
         for k in ks:
@@ -616,6 +629,53 @@ def main() -> None:
     if dist is not None:
         dist.barrier()
         dist.destroy_process_group()
+
+
+def headline(args, p, world: int, B: int, T: int, Tf: int, dt: float, per_rank_ms, gather: bool, gru_persistent: bool) -> dict:
+    """The keys of the result line that the timed loop alone determines: all that a plain run prints (--full adds the rest)."""
+    frames = world * B * (T // HOP) * args.steps
+    return {
+        "metric": "48 kHz audio frames/sec (hop=480), DeepFilterNet3 enhance()",
+        "value": frames / dt, "unit": "frames/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f32 (storage and accumulation; GRU projections / recurrences, the fused DF-encoder convolutions and the pointwise halves of the ERB separable convolutions as fp16-split MFMAs: "
+                 "x = hi + lo in f16, hi*hi + hi*lo + lo*hi on v_mfma_f32_16x16x32_f16, ~2^-21 relative; see exact_fp32_ms_per_step)",
+        "data": "synthetic (seeded harmonic+noise 48 kHz audio, seeded random DeepFilterNet3 weights)",
+        "config": {"workload": f"DeepFilterNet3 ({'recalled shipped shape, conv_ch=64' if args.model == 'df3' else 'code defaults'}) "
+                               f"enhance(pad=True), batch={B} clips x {args.seconds:g} s @48 kHz per GPU, {Tf} STFT frames per clip",
+                   "batch_per_gpu": B, "clip_seconds": args.seconds, "global_batch": B * world,
+                   "parallelism": f"clips sharded over {world} GPU(s); " + ("async RCCL gather of waveforms to rank 0" if gather else "no collective"),
+                   "inputs_resident_in_hbm": True},
+        "per_rank_ms_per_step": [round(v, 4) for v in per_rank_ms],
+        "gru_phase_form": (("persistent flag-synchronised launch (dfx_k_gru_seq_p2: recurrences on pairs of CUs)" if os.environ.get("DFX_GRU_PAIR", "1")[:1] != "0" and B > 16 else "persistent flag-synchronised launch (dfx_k_gru_seq)") if gru_persistent else "event-synchronised launches per (layer, time chunk)"),
+    }
+
+
+DUMP_MAX_BYTES = 64 * 10**6
+DUMP_CLIPS = 16
+
+
+def dump_outputs(out_dir: str, y: torch.Tensor) -> None:
+    """--dump-outputs DIR: the enhanced waveforms the last timed step returned, as DIR/enhanced.npy (float32).  The whole [B, T] batch is
+    491 MB at the default size, so a fixed sample is written: DUMP_CLIPS whole clips (rows) drawn with a fixed seed, in ascending order, at
+    most DUMP_MAX_BYTES (clips longer than that are cut to a seeded, sorted subset of their samples).  Same arguments, same sample."""
+    B, T = y.shape
+    rng = np.random.default_rng(0)
+    rows = max(1, min(B, DUMP_CLIPS, DUMP_MAX_BYTES // (4 * T)))
+    ri = np.sort(rng.choice(B, rows, replace=False))
+    out = y[torch.from_numpy(ri).to(y.device)].float()
+    if rows * T * 4 > DUMP_MAX_BYTES:
+        ci = np.sort(rng.choice(T, DUMP_MAX_BYTES // (4 * rows), replace=False))
+        out = out[:, torch.from_numpy(ci).to(y.device)]
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "enhanced.npy"), np.ascontiguousarray(out.cpu().numpy(), dtype=np.float32))
+
+
+def _positive(v: str) -> int:
+    n = int(v)
+    if n < 1:
+        raise argparse.ArgumentTypeError(f"must be at least 1, got {n}")
+    return n
 
 
 def bench_streaming(dev, streams: int = 4096, calls: int = 1000) -> dict:

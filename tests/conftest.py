@@ -4,6 +4,11 @@ import sys
 import pytest
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# The persistent GRU phase needs one hardware queue per engine stream (include/dfx.h); deepfilternet_amd only sets 24 when the variable
+# is unset.  An inherited smaller value (ROCm's default is 4) would put every handle of the session, and of the child processes the
+# tests start, on the event-synchronised form, and the tests that check the persistent form would fail.  Set before HIP initialises.
+if int(os.environ.get("GPU_MAX_HW_QUEUES") or 0) < 24:
+    os.environ["GPU_MAX_HW_QUEUES"] = "24"
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 sys.dont_write_bytecode = False

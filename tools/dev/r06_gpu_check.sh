@@ -1,7 +1,8 @@
 #!/bin/bash
-# Dev: new concurrency tests, the two-handle rounds, the whole GPU suite and a bench line in one GPU call
-mkdir -p gpurun_out/r06
-python -m pytest tests/test_concurrency.py -m gpu -x -q -s > gpurun_out/r06/concurrency.txt 2>&1; tail -15 gpurun_out/r06/concurrency.txt
-python tools/dev/two_handles_diag.py --rounds 100 --max-dumps 2 --streams own > gpurun_out/r06/two_handles_own.log 2>&1; grep "handle\|SUMMARY" gpurun_out/r06/two_handles_own.log | tail -4
-python -m pytest tests -m gpu -x -q > gpurun_out/r06/gpu_tests.txt 2>&1; tail -3 gpurun_out/r06/gpu_tests.txt
-python bench.py > gpurun_out/r06/bench.json 2> gpurun_out/r06/bench.err; tail -c 700 gpurun_out/r06/bench.json
+# Dev: new concurrency tests, the two-handle rounds, the whole GPU suite and a bench line in one GPU call.  Usage: tools/dev/r06_gpu_check.sh <output dir>
+D=${1:?usage: $0 <output dir>}
+mkdir -p "$D"
+python -m pytest tests/test_concurrency.py -m gpu -x -q -s > "$D/concurrency.txt" 2>&1; tail -15 "$D/concurrency.txt"
+python tools/dev/two_handles_diag.py --rounds 100 --max-dumps 2 --streams own > "$D/two_handles_own.log" 2>&1; grep "handle\|SUMMARY" "$D/two_handles_own.log" | tail -4
+python -m pytest tests -m gpu -x -q > "$D/gpu_tests.txt" 2>&1; tail -3 "$D/gpu_tests.txt"
+python bench.py --full > "$D/bench.json" 2> "$D/bench.err"; tail -c 700 "$D/bench.json"
