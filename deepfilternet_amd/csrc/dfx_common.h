@@ -91,12 +91,27 @@ struct DfxKScope {
 // spec_stride: row stride of spec in complex elements (0: F)
 int dfx_launch_analysis(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_stride,
                         const float *mem_in, float *mem_out, float *spec, float *erb_db, hipStream_t s, int64_t x_len = -1,
-                        int64_t spec_stride = 0, bool x_i16 = false);   // x_i16: x points at int16_t PCM samples (x / 32768 on the way in; no memories)
+                        int64_t spec_stride = 0, bool x_i16 = false,   // x_i16: x points at int16_t PCM samples (x / 32768 on the way in; no memories)
+                        const int64_t *x_lens = nullptr);              // device [B]: the x_len of every row instead (no memories)
 // only the analysis memory (the last N - hop samples in front of the next call's first hop) of a call over T samples per row
 int dfx_launch_analysis_mem(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_stride, const float *mem_in, float *mem_out,
                             hipStream_t s);
 int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_len, int64_t x_stride, int nb_df,
-                        float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride = 0, bool x_i16 = false);
+                        float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride = 0, bool x_i16 = false,
+                        const int64_t *x_lens = nullptr);
+// dfx_enhance_varlen: the rows' sample counts (host) -> meta [3][B] on the device: samples, frames ((samples + pad_n) / hop), output samples.
+// The counts travel as kernel arguments: the caller's array is not read after the return.
+int dfx_launch_varlen_rows(const int64_t *lens, int64_t B, int64_t *meta, int hop, int pad_n, hipStream_t s);
+// up to three [B, stride] arrays of 4-byte elements (elem16: 2-byte): row b keeps its first keep[b] * unit elements (keep: device [B]), the
+// elements [keep[b] * unit, width) become zeros
+struct DfxTails {
+    void *p[3] = {nullptr, nullptr, nullptr};
+    int64_t stride[3] = {0, 0, 0}, width[3] = {0, 0, 0}, unit[3] = {0, 0, 0};
+    int n = 0;
+    bool elem16 = false;
+    void add(void *q, int64_t st, int64_t w, int64_t u) { p[n] = q, stride[n] = st, width[n] = w, unit[n] = u, ++n; }
+};
+int dfx_launch_zero_tails(const DfxTails &t, const int64_t *keep, int64_t B, hipStream_t s);
 // dfx_synthesis storing only stream samples [out_skip, out_skip + out_len) of every row, at out[row * out_stride + n - out_skip]
 int dfx_launch_synthesis(const dfx_state *st, const float *spec, int64_t B, int64_t Tf, const float *mem_in, float *mem_out,
                          float *out, int64_t out_stride, int64_t out_skip, int64_t out_len, hipStream_t s, int64_t f_begin = 0,

@@ -401,8 +401,9 @@ static int grid_for(int64_t work_groups, int per_cu = 8) {
 
 int dfx_launch_analysis(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_stride,
                         const float *mem_in, float *mem_out, float *spec, float *erb_db, hipStream_t s, int64_t x_len,
-                        int64_t spec_stride, bool x_i16) {
+                        int64_t spec_stride, bool x_i16, const int64_t *x_lens) {
     if (x_i16 && (mem_in || mem_out)) DFX_FAIL(DFX_ERR_INVALID_ARG, "analysis of 16-bit PCM input carries no memories (whole rows only)");
+    if (x_lens && (mem_in || mem_out)) DFX_FAIL(DFX_ERR_INVALID_ARG, "analysis of rows of different lengths carries no memories (whole rows only)");
     const int64_t Tf = T / st->hop;
     if (B > 0 && Tf > 0) {
         DfxAnaArgs A;
@@ -424,6 +425,7 @@ int dfx_launch_analysis(const dfx_state *st, const float *x, int64_t B, int64_t 
         A.Tf = Tf;
         A.x_stride = x_stride;
         A.x_len = x_len < 0 ? T : x_len;
+        A.x_lens = x_lens;
         A.spec_stride = spec_stride > 0 ? spec_stride : st->N / 2 + 1;
         A.hop = st->hop;
         A.nb = st->nb;
@@ -439,13 +441,55 @@ int dfx_launch_analysis(const dfx_state *st, const float *x, int64_t B, int64_t 
             dfx_launch(kern, dim3(grid), dim3(DFX_DSP_THREADS), smem, s, A);
             return DFX_OK;
         };
-        if (int rc = ip ? (x_i16 ? go(dfx_k_analysis<true, true>) : go(dfx_k_analysis<true, false>))
-                        : (x_i16 ? go(dfx_k_analysis<false, true>) : go(dfx_k_analysis<false, false>)))
+        if (int rc = x_lens ? (ip ? (x_i16 ? go(dfx_k_analysis<true, true, false, true>) : go(dfx_k_analysis<true, false, false, true>))
+                                  : (x_i16 ? go(dfx_k_analysis<false, true, false, true>) : go(dfx_k_analysis<false, false, false, true>)))
+                            : ip ? (x_i16 ? go(dfx_k_analysis<true, true>) : go(dfx_k_analysis<true, false>))
+                                 : (x_i16 ? go(dfx_k_analysis<false, true>) : go(dfx_k_analysis<false, false>)))
             return rc;
         DFX_LAUNCH_CHECK();
     }
     if (mem_out && B > 0) return dfx_launch_analysis_mem(st, x, B, T, x_stride, mem_in, mem_out, s);
     return DFX_OK;
+}
+
+int dfx_launch_varlen_rows(const int64_t *lens, int64_t B, int64_t *meta, int hop, int pad_n, hipStream_t s) {
+    // hipLaunchKernelGGL copies the argument block — the lengths with it — into the launch before it returns, like every kernel argument: the
+    // caller may overwrite its array as soon as the enhance call returns, though the pass has not run yet (a hipMemcpyAsync from pageable memory
+    // would instead depend on how the runtime stages such copies)
+    for (int64_t r0 = 0; r0 < B; r0 += DFX_VL_ROWS) {
+        DfxVlRows A;
+        A.meta = meta;
+        A.B = B, A.row0 = r0;
+        A.n = (int)(B - r0 < DFX_VL_ROWS ? B - r0 : DFX_VL_ROWS);
+        A.hop = hop, A.pad_n = pad_n;
+        for (int i = 0; i < A.n; ++i) A.len[i] = lens[r0 + i];
+        dfx_launch(dfx_k_varlen_rows, dim3(1), dim3(DFX_VL_ROWS), 0, s, A);
+        DFX_LAUNCH_CHECK();
+    }
+    return DFX_OK;
+}
+
+template <typename E>
+static int zero_tails_as(const DfxTails &t, const int64_t *keep, int64_t B, hipStream_t s) {
+    DfxTailArgs<E> A;
+    int64_t most = 0;
+    for (int a = 0; a < 3; ++a) {
+        const bool on = a < t.n;
+        A.p[a] = on ? reinterpret_cast<E *>(t.p[a]) : nullptr;
+        A.stride[a] = on ? t.stride[a] : 0;
+        A.width[a] = on ? t.width[a] : 0;
+        A.unit[a] = on ? t.unit[a] : 0;
+        A.items[a] = on ? dfx_ceil_div(t.width[a], DFX_ZT_ITEM) : 0;
+        if (B * A.items[a] > most) most = B * A.items[a];
+    }
+    A.keep = keep, A.B = B;
+    dfx_launch(dfx_k_zero_tails<E>, dim3((unsigned)grid_for(most), (unsigned)t.n), dim3(256), 0, s, A);
+    DFX_LAUNCH_CHECK();
+    return DFX_OK;
+}
+int dfx_launch_zero_tails(const DfxTails &t, const int64_t *keep, int64_t B, hipStream_t s) {
+    if (B <= 0 || t.n <= 0) return DFX_OK;
+    return t.elem16 ? zero_tails_as<int16_t>(t, keep, B, s) : zero_tails_as<float>(t, keep, B, s);
 }
 // the analysis memory after the T samples of a call (what dfx_launch_analysis does last when it is given mem_out; on its own for callers
 // that want it off the stream the spectra are waited for on: only the NEXT call reads it)
@@ -666,7 +710,8 @@ extern "C" int dfx_features(const dfx_state *st, const float *x, int64_t B, int6
 
 // dfx_features over rows of T samples of which only the first x_len exist in memory (the rest are zeros): enhance()'s end padding
 int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_len, int64_t x_stride, int nb_df,
-                        float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride, bool x_i16) {
+                        float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride, bool x_i16,
+                        const int64_t *x_lens) {
     if (spec_stride <= 0) spec_stride = st ? st->N / 2 + 1 : 0;
     if (!st || B < 0 || T < 0 || x_len < 0 || x_len > T || x_stride < x_len || nb_df <= 0 || nb_df > st->N / 2 + 1)
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_features: bad arguments");
@@ -675,7 +720,8 @@ int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t 
     if (B == 0 || Tf == 0) return DFX_OK;
     if (!x || !spec || !erb_feat || !spec_feat) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_features: null buffer");
     // enhance.py:190-197: spec = analysis(x); erb_norm(erb(spec)); unit_norm(spec[..., :nb_df])
-    if (int rc = dfx_launch_analysis(st, x, B, T, x_stride, nullptr, nullptr, spec, erb_feat, dfx_stream(stream), x_len, spec_stride, x_i16)) return rc;
+    if (int rc = dfx_launch_analysis(st, x, B, T, x_stride, nullptr, nullptr, spec, erb_feat, dfx_stream(stream), x_len, spec_stride, x_i16, x_lens))
+        return rc;
     return dfx_launch_norm_scan(erb_feat, erb_feat, st->nb, spec, spec_stride, spec_feat, nb_df, B, Tf, alpha, nullptr,
                                 nullptr, dfx_stream(stream));
 }

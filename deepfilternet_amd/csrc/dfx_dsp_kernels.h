@@ -700,6 +700,7 @@ struct DfxAnaArgs {
     int segcap = 0, segparts = 0;   // longest segment / most segments of a band when the fixed-trip band sums may be used (dfx_launch_analysis), else 0
     int64_t B, Tf, x_stride;
     int64_t x_len;        // samples that exist per row; positions >= x_len read as 0 (enhance()'s F.pad(audio, (0, n_fft)) without a copy)
+    const int64_t *x_lens = nullptr;   // VL instances: [B] the x_len of every row (dfx_enhance_varlen: clips of different lengths in one pass)
     int64_t spec_stride;  // row stride of spec in complex elements (>= F; the engine pads odd F to even so rows are 16-byte aligned)
     int hop, nb;
     float wnorm;
@@ -713,7 +714,8 @@ struct DfxAnaArgs {
 // IP: the 480-point plan, transformed in place (one LDS buffer per frame; a kernel of its own so that the generic plan's run-time loops
 // do not cost it registers: three workgroups = six waves per SIMD have to fit)
 // MF: the transform on the matrix pipe (dfx_fft480_mfma; its 30-point fragments, 8 KB, sit behind the window table; four waves per SIMD)
-template <bool IP, bool I16 = false, bool MF = false>
+// VL: every row has its own x_len (A.x_lens, one wave-uniform load per frame); the uniform instances keep their instruction stream
+template <bool IP, bool I16 = false, bool MF = false, bool VL = false>
 __global__ void __launch_bounds__(DFX_DSP_THREADS, IP ? (MF ? 4 : 6) : 4) dfx_k_analysis(DfxAnaArgs A) {
     static_assert(!MF || IP, "the matrix-pipe transform replaces the in-place 480-point plan");
     DFX_DYN_SMEM(unsigned char, smem);
@@ -790,10 +792,11 @@ __global__ void __launch_bounds__(DFX_DSP_THREADS, IP ? (MF ? 4 : 6) : 4) dfx_k_
             const int16_t *xs = reinterpret_cast<const int16_t *>(A.x) + b * A.x_stride;   // (I16)
             const int64_t pos0 = t * A.hop - ML;
             const float *xf = xb + pos0;
+            const int64_t x_len = VL ? A.x_lens[b] : A.x_len;
             int ll = lane;
             DFX_OPAQUE(ll);   // (addresses recomputed per frame instead of living in registers across the loop: see dfx_fft480_ip)
             DFX_ASSUME(ll >= 0 && ll < DFX_DSP_TEAM);
-            if (pos0 >= 0 && pos0 + N <= A.x_len && (I16 ? (reinterpret_cast<uintptr_t>(xs + pos0) & 3) == 0 : (reinterpret_cast<uintptr_t>(xf) & 7) == 0)) {
+            if (pos0 >= 0 && pos0 + N <= x_len && (I16 ? (reinterpret_cast<uintptr_t>(xs + pos0) & 3) == 0 : (reinterpret_cast<uintptr_t>(xf) & 7) == 0)) {
                 // interior frame (wave-uniform test; all but the first of a clip and the ones reaching into the implicit zero padding):
                 // 8-byte loads, 8 per lane in flight before the first LDS store (M = 480: one pass) — a load -> store loop would
                 // wait out one memory latency per iteration.  (Requesting the NEXT frame before this one's FFT, as the synthesis
@@ -826,7 +829,7 @@ __global__ void __launch_bounds__(DFX_DSP_THREADS, IP ? (MF ? 4 : 6) : 4) dfx_k_
                         const int i = 2 * k + h;
                         const int64_t pos = pos0 + i;
                         float s = 0.f;
-                        if (pos >= 0) s = pos < A.x_len ? (I16 ? dfx_pcm16_in(xs[pos]) : xb[pos]) : 0.f;
+                        if (pos >= 0) s = pos < x_len ? (I16 ? dfx_pcm16_in(xs[pos]) : xb[pos]) : 0.f;
                         else if (A.mem_in) s = A.mem_in[b * ML + (ML + pos)];
                         v[h] = s * win[i];
                     }
@@ -1027,6 +1030,53 @@ __global__ void dfx_k_analysis_mem_out(const float *x, const float *mem_in, floa
     if (pos >= 0) v = x[b * x_stride + pos];
     else if (mem_in) v = mem_in[b * ML + (ML + pos)];
     mem_out[i] = v;
+}
+
+// ---- clips of different lengths in one enhance() pass (dfx_enhance_varlen) ----------------------------------------------------------------
+// The rows' sample counts reach the device as a kernel argument (the launch copies its argument block, so the caller's array is free again when
+// the launching call returns); this kernel derives the rest.  meta [3][B]: samples, frames ((samples + pad_n) / hop) and output samples (the
+// clip's own length with enhance()'s padding, whole hops without, enhance.py:243-249) of every row.
+#define DFX_VL_ROWS 256
+struct DfxVlRows {
+    int64_t *meta;
+    int64_t B, row0;   // this launch's rows: row0 .. row0 + n - 1 of the pass's B
+    int n, hop, pad_n;
+    int64_t len[DFX_VL_ROWS];
+};
+__global__ void __launch_bounds__(DFX_VL_ROWS) dfx_k_varlen_rows(DfxVlRows A) {
+    const int i = (int)threadIdx.x;
+    if (i >= A.n) return;
+    const int64_t b = A.row0 + i, n = A.len[i], tf = (n + A.pad_n) / A.hop;
+    A.meta[b] = n;
+    A.meta[A.B + b] = tf;
+    A.meta[2 * A.B + b] = A.pad_n ? n : tf * A.hop;
+}
+
+// Tails of up to three [B, stride] arrays (blockIdx.y picks the array): row b keeps its first keep[b] * unit elements, the elements
+// [keep[b] * unit, width) become zeros.  Items of DFX_ZT_ITEM elements of one row, grid-strided; an item wholly inside the kept part ends at once.
+#define DFX_ZT_ITEM 2048
+template <typename E>
+struct DfxTailArgs {
+    E *p[3];
+    int64_t stride[3], width[3], unit[3], items[3];
+    const int64_t *keep;   // [B]
+    int64_t B;
+};
+template <typename V>
+static __device__ __forceinline__ V dfx_pick3(const V (&v)[3], int a) { return a == 0 ? v[0] : (a == 1 ? v[1] : v[2]); }   // (constant indices)
+template <typename E>
+__global__ void __launch_bounds__(256) dfx_k_zero_tails(DfxTailArgs<E> A) {
+    const int a = (int)blockIdx.y;
+    E *p = dfx_pick3(A.p, a);
+    const int64_t stride = dfx_pick3(A.stride, a), width = dfx_pick3(A.width, a), unit = dfx_pick3(A.unit, a), items = dfx_pick3(A.items, a);
+    for (int64_t it = blockIdx.x; it < A.B * items; it += gridDim.x) {
+        const int64_t b = it / items, i0 = (it - b * items) * DFX_ZT_ITEM;
+        const int64_t k = A.keep[b] * unit;
+        if (i0 + DFX_ZT_ITEM <= k) continue;
+        E *row = p + b * stride;
+        const int64_t i1 = i0 + DFX_ZT_ITEM < width ? i0 + DFX_ZT_ITEM : width;
+        for (int64_t i = (k > i0 ? k : i0) + threadIdx.x; i < i1; i += 256) row[i] = E(0);
+    }
 }
 
 struct DfxSynArgs {

@@ -1,4 +1,5 @@
-// dfx: enhance() as one C call (dfx_enhance / dfx_enhance_pcm16: workspace plan, STFT features, forward pass with the fused finishing kernel).
+// dfx: enhance() as one C call (dfx_enhance / dfx_enhance_pcm16, and dfx_enhance_varlen[_pcm16] for clips of different lengths: workspace
+// plan, STFT features, forward pass with the fused finishing kernel).
 // A part of dfx_model.hip (one translation unit: included from there, in this order — launch helpers, forward pass, streaming, enhance()).
 #pragma once
 
@@ -35,6 +36,21 @@ EnhWs plan_enh(const dfx_model *m, const dfx_state *st, int64_t B, int64_t T, in
     return w;
 }
 }  // namespace
+
+// Clips of different lengths (dfx_enhance_varlen).  Every row runs the Tf frames of the pass's longest row, and frames t >= Tf_b of row b may
+// hold anything without reaching frames < Tf_b: every stage between the features and the finishing kernel is causal in time (time convolutions
+// pad at the front, forward GRUs, df_convp and the norm scans look back only), the network's lookahead enters only through the features and
+// the deep filter's only through the spectrum.  So a row gets the bits of a pass of its own when (1) the STFT reads its samples [0, len_b) and
+// zeros behind them, (2) its spectrum and normalised features are zero from frame Tf_b on — MF.DF's zero padding behind a clip
+// (multiframe.py:72-76) and pad_feat's (deepfilternet3.py:359,409-410) — and (3) its output holds out_len_b samples, then zeros: output hop k
+// depends only on frames <= k (lib.rs:396-427).  (1) is the VL instance of the analysis kernel; (2) and (3) are one dfx_k_zero_tails launch
+// each, behind the features and behind the finishing kernels, and only where a row is shorter than the pass: the norm scans and the finishing
+// kernels are the uniform ones.  The per-row metadata sits in front of the chunks' workspaces: [3][B] int64 (dfx_k_varlen_rows).
+static inline size_t enh_rows_bytes(int64_t B) { return ((size_t)B * 3 * sizeof(int64_t) + 255) & ~(size_t)255; }
+struct EnhRows {
+    const int64_t *len = nullptr, *frames = nullptr;   // device, the chunk's rows (null: the uniform pass)
+    bool short_frames = false;                         // a row of the chunk has fewer frames than the pass
+};
 
 static int enh_chunks(const dfx_model *m, int64_t B, int64_t *sizes) {
     int nc = 1;
@@ -76,7 +92,8 @@ extern "C" int dfx_enhance_workspace_bytes(const dfx_model *m, const dfx_state *
 // pcm16: x and y point at int16_t samples (same strides in samples); the conversions of df/io.py run in the STFT kernel's loads and the
 // ISTFT kernel's stores
 static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x, int64_t B, int64_t T, int pad, float lim,
-                         float *y, unsigned char *base, hipStream_t s, const DfxLane *ln, bool signal_front, bool pcm16) {
+                         float *y, unsigned char *base, hipStream_t s, const DfxLane *ln, bool signal_front, bool pcm16,
+                         int64_t x_stride, int64_t y_stride, const EnhRows &rows) {
     const dfx_model_cfg &c = m->cfg;
     const EnhWs w = plan_enh(m, st, B, T, pad);
     const int64_t Tp = pad ? T + st->N : T, Tf = Tp / st->hop;
@@ -84,8 +101,15 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
     float *fe = reinterpret_cast<float *>(base + w.feat_erb), *fs = reinterpret_cast<float *>(base + w.feat_spec);
     // F.pad(audio, (0, n_fft)) (enhance.py:230-233) is implicit: the analysis reads zeros past the T samples of a row
     const int64_t sstride = enh_spec_stride(st);
-    int rc = dfx_features_padded(st, x, B, Tp, T, T, c.nb_df, c.norm_alpha, spec, fe, fs, (void *)s, sstride, pcm16);
+    int rc = dfx_features_padded(st, x, B, Tp, T, x_stride, c.nb_df, c.norm_alpha, spec, fe, fs, (void *)s, sstride, pcm16, rows.len);
     if (rc) return rc;
+    if (rows.short_frames) {   // (2) above: spectrum and features of the frames behind a shorter row's end
+        DfxTails t;
+        t.add(spec, Tf * sstride * 2, Tf * sstride * 2, sstride * 2);
+        t.add(fe, Tf * c.nb_erb, Tf * c.nb_erb, c.nb_erb);
+        t.add(fs, Tf * c.nb_df * 2, Tf * c.nb_df * 2, c.nb_df * 2);
+        if ((rc = dfx_launch_zero_tails(t, rows.frames, B, s))) return rc;
+    }
     int64_t mb = 0;
     dfx_model_workspace_bytes(m, B, Tf, &mb);
     // the synthesis is enqueued by the model forward (per time chunk when the GRU phase is pipelined); with pad it stores exactly
@@ -93,7 +117,7 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
     DfxFinish fin;
     fin.st = st;
     fin.y = y;
-    fin.out_stride = pad ? T : Tf * st->hop;
+    fin.out_stride = y_stride;
     fin.out_skip = pad ? st->N - st->hop : 0;
     fin.out_len = pad ? T : Tf * st->hop;
     fin.spec_stride = sstride;
@@ -102,26 +126,33 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
                               signal_front, &fin);
 }
 
+// lens (dfx_enhance_varlen): host [B], the samples of every row, T their maximum; rows of x / y x_stride / y_stride apart.  Null: the uniform pass
+// (rows T / its output apart).
 static int enhance_any(const dfx_model *m, const dfx_state *st, const float *x, int64_t B, int64_t T, int pad,
-                       float atten_lim_db, float *y, void *workspace, int64_t workspace_bytes, void *stream, bool pcm16) {
+                       float atten_lim_db, float *y, void *workspace, int64_t workspace_bytes, void *stream, bool pcm16,
+                       const int64_t *lens = nullptr, int64_t x_stride = 0, int64_t y_stride = 0) {
     if (!m || !st || B < 0 || T < 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance: bad arguments");
     const dfx_model_cfg &c = m->cfg;
     if (st->N != c.fft_size || st->hop != c.hop_size || st->nb != c.nb_erb)
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance: DF state does not match the model configuration");
     if (pad && st->N % st->hop) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance: pad requires fft_size %% hop_size == 0 (enhance.py:247)");
+    const int64_t Tp = pad ? T + st->N : T, Tf = Tp / st->hop;
+    const int64_t out_len = pad ? T : Tf * st->hop;
+    const int64_t xs = lens ? x_stride : T, ys = lens ? y_stride : out_len;
+    if (lens && (xs < T || ys < out_len))
+        DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance_varlen: x_stride %lld / y_stride %lld below the longest clip (%lld) / its output (%lld)",
+                 (long long)xs, (long long)ys, (long long)T, (long long)out_len);
     if (int rc = dfx_require_device()) return rc;
     if (B == 0) return DFX_OK;
     if (!x || !y || !workspace) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance: null buffer");
     int64_t sizes[DFX_MAX_LANES];
     const int nc = enh_chunks(m, B, sizes);
-    int64_t need = 0;
+    int64_t need = lens ? (int64_t)enh_rows_bytes(B) : 0;
     for (int i = 0; i < nc; ++i) need += (int64_t)plan_enh(m, st, sizes[i], T, pad).total;
     if (workspace_bytes < need) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance: workspace too small");
     unsigned char *base = reinterpret_cast<unsigned char *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
     hipStream_t s = dfx_stream(stream);
-    const int64_t Tp = pad ? T + st->N : T, Tf = Tp / st->hop;
-    const int64_t out_len = pad ? T : Tf * st->hop;
-    if (Tf == 0) {
+    if (Tf == 0) {   // (no pad, every row shorter than a hop: nothing to store)
         if (out_len > 0) DFX_HIP(hipMemsetAsync(y, 0, (size_t)B * out_len * (pcm16 ? 2 : 4), s));
         return DFX_OK;
     }
@@ -132,8 +163,32 @@ static int enhance_any(const dfx_model *m, const dfx_state *st, const float *x, 
     }
     if (int rc = pass_begin(m, B * Tf)) return rc;
     DfxTurn turn(m, s, true);
+    int64_t *meta = nullptr;
+    bool short_out = false;
+    if (lens) {
+        meta = reinterpret_cast<int64_t *>(base);
+        base += enh_rows_bytes(B);
+        if (int rc = dfx_launch_varlen_rows(lens, B, meta, st->hop, pad ? st->N : 0, s)) return rc;
+        for (int64_t b = 0; b < B; ++b) short_out |= (pad ? lens[b] : lens[b] / st->hop * st->hop) < out_len;
+    }
+    auto rows_of = [&](int64_t row, int64_t n) {
+        EnhRows r;
+        if (!lens) return r;
+        r.len = meta + row, r.frames = meta + B + row;
+        for (int64_t b = row; b < row + n; ++b) r.short_frames |= (lens[b] + (pad ? st->N : 0)) / st->hop < Tf;
+        return r;
+    };
+    // (3) above: a shorter row's output is followed by zeros up to the pass's widest output, once every chunk has joined back into s
+    auto tails = [&]() -> int {
+        if (!short_out) return DFX_OK;
+        DfxTails t;
+        t.add(y, ys, out_len, 1);
+        t.elem16 = pcm16;
+        return dfx_launch_zero_tails(t, meta + 2 * B, B, s);
+    };
     if (nc == 1) {
-        if (int rc = enhance_chunk(m, st, x, B, T, pad, lim, y, base, s, &m->lanes[0], false, pcm16)) return rc;
+        if (int rc = enhance_chunk(m, st, x, B, T, pad, lim, y, base, s, &m->lanes[0], false, pcm16, xs, ys, rows_of(0, B))) return rc;
+        if (int rc = tails()) return rc;
         turn.passed();
         return pass_end(m, B * Tf, s);
     }
@@ -145,14 +200,16 @@ static int enhance_any(const dfx_model *m, const dfx_state *st, const float *x, 
         DFX_HIP(hipStreamWaitEvent(ln->main, m->ev_fork, 0));
         if (i > 0) DFX_HIP(hipStreamWaitEvent(ln->main, m->lanes[i - 1].ev[EV_FRONT], 0));
         // (16-bit samples: the float-typed pointers advance by half as many elements)
-        const float *xi = pcm16 ? reinterpret_cast<const float *>(reinterpret_cast<const int16_t *>(x) + row * T) : x + row * T;
-        float *yi = pcm16 ? reinterpret_cast<float *>(reinterpret_cast<int16_t *>(y) + row * out_len) : y + row * out_len;
-        if (int rc = enhance_chunk(m, st, xi, sizes[i], T, pad, lim, yi, base, ln->main, ln, true, pcm16)) return rc;
+        const float *xi = pcm16 ? reinterpret_cast<const float *>(reinterpret_cast<const int16_t *>(x) + row * xs) : x + row * xs;
+        float *yi = pcm16 ? reinterpret_cast<float *>(reinterpret_cast<int16_t *>(y) + row * ys) : y + row * ys;
+        if (int rc = enhance_chunk(m, st, xi, sizes[i], T, pad, lim, yi, base, ln->main, ln, true, pcm16, xs, ys, rows_of(row, sizes[i])))
+            return rc;
         DFX_HIP(hipEventRecord(ln->ev[EV_DONE], ln->main));
         base += (plan_enh(m, st, sizes[i], T, pad).total + 255) & ~(size_t)255;
         row += sizes[i];
     }
     for (int i = 0; i < nc; ++i) DFX_HIP(hipStreamWaitEvent(s, m->lanes[i].ev[EV_DONE], 0));
+    if (int rc = tails()) return rc;
     turn.passed();
     return pass_end(m, B * Tf, s);
 }
@@ -164,4 +221,38 @@ extern "C" int dfx_enhance_pcm16(const dfx_model *m, const dfx_state *st, const 
                                  float atten_lim_db, int16_t *y, void *workspace, int64_t workspace_bytes, void *stream) {
     return enhance_any(m, st, reinterpret_cast<const float *>(x), B, T, pad, atten_lim_db, reinterpret_cast<float *>(y), workspace, workspace_bytes,
                        stream, true);
+}
+
+// the lengths of a dfx_enhance_varlen call, checked before anything else happens, and their maximum
+static int varlen_longest(int64_t B, const int64_t *lengths, int64_t *T) {
+    if (B < 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance_varlen: B < 0");
+    if (B > 0 && !lengths) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance_varlen: null lengths");
+    *T = 0;
+    for (int64_t b = 0; b < B; ++b) {
+        if (lengths[b] < 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_enhance_varlen: lengths[%lld] = %lld", (long long)b, (long long)lengths[b]);
+        if (lengths[b] > *T) *T = lengths[b];
+    }
+    return DFX_OK;
+}
+extern "C" int dfx_enhance_varlen_workspace_bytes(const dfx_model *m, const dfx_state *st, int64_t B, const int64_t *lengths, int pad,
+                                                  int64_t *bytes) {
+    int64_t T = 0;
+    if (int rc = varlen_longest(B, lengths, &T)) return rc;
+    if (int rc = dfx_enhance_workspace_bytes(m, st, B, T, pad, bytes)) return rc;
+    *bytes += (int64_t)enh_rows_bytes(B);
+    return DFX_OK;
+}
+extern "C" int dfx_enhance_varlen(const dfx_model *m, const dfx_state *st, const float *x, int64_t B, int64_t x_stride, const int64_t *lengths,
+                                  int pad, float atten_lim_db, float *y, int64_t y_stride, void *workspace, int64_t workspace_bytes, void *stream) {
+    int64_t T = 0;
+    if (int rc = varlen_longest(B, lengths, &T)) return rc;
+    return enhance_any(m, st, x, B, T, pad, atten_lim_db, y, workspace, workspace_bytes, stream, false, B > 0 ? lengths : nullptr, x_stride, y_stride);
+}
+extern "C" int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int16_t *x, int64_t B, int64_t x_stride,
+                                        const int64_t *lengths, int pad, float atten_lim_db, int16_t *y, int64_t y_stride, void *workspace,
+                                        int64_t workspace_bytes, void *stream) {
+    int64_t T = 0;
+    if (int rc = varlen_longest(B, lengths, &T)) return rc;
+    return enhance_any(m, st, reinterpret_cast<const float *>(x), B, T, pad, atten_lim_db, reinterpret_cast<float *>(y), workspace, workspace_bytes,
+                       stream, true, B > 0 ? lengths : nullptr, x_stride, y_stride);
 }

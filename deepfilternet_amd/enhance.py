@@ -61,6 +61,11 @@ def init_df(
             from .model import read_onnx_targz
 
             p, state_dict = read_onnx_targz(model_base_dir)
+        elif os.path.isfile(model_base_dir) and model_base_dir.endswith(".dfx"):
+            # extension: a .dfx model file (export_dfx; what the C API's df_create reads)
+            from .model import read_dfx
+
+            p, state_dict = read_dfx(model_base_dir)
         elif not os.path.isdir(model_base_dir):
             raise NotADirectoryError("Base directory not found at {}".format(model_base_dir))
         else:
@@ -197,22 +202,228 @@ def enhance(model: DfNet, df_state: DF, audio: torch.Tensor, pad: bool = True, a
     return out
 
 
+# Rows (clip channels) per pass of enhance_batch: tools/bench_varlen.py's sweep of 128 / 256 / 512 on its mixed set (profiles/r07_varlen.txt).
+_BATCH_ROWS = 256
+# Rows enhance_files gathers before it enhances them: enough for several passes of similar lengths once the window is sorted.
+_FILE_WINDOW_ROWS = 4 * _BATCH_ROWS
+
+
+def _varlen_ws_bytes(model: DfNet, df_state: DF, lens, pad: bool) -> int:
+    arr = (C.c_int64 * len(lens))(*lens)
+    nbytes = C.c_int64()
+    _lib.check(_lib.lib().dfx_enhance_varlen_workspace_bytes(model.handle, df_state.handle, len(lens), arr, int(bool(pad)), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def _plan_passes(model: DfNet, df_state: DF, lens, pad: bool):
+    """[(first row, rows, workspace bytes)] over rows sorted longest first: at most _BATCH_ROWS rows per pass, and — the rule of enhance() — a
+    workspace within _workspace_cap (fewer rows, whole groups of 16, when the cap says so)."""
+    passes, r = [], 0
+    while r < len(lens):
+        n = min(_BATCH_ROWS, len(lens) - r)
+        need = _varlen_ws_bytes(model, df_state, lens[r:r + n], pad)
+        cap = _workspace_cap(model, need)
+        if cap is not None and need > cap:
+            if _varlen_ws_bytes(model, df_state, lens[r:r + 1], pad) > cap:
+                raise MemoryError(f"enhance_batch(): a clip of {lens[r]} samples needs more workspace than the {cap} bytes available")
+            lo, hi = 1, n
+            while lo < hi:
+                mid = (lo + hi + 1) // 2
+                if _varlen_ws_bytes(model, df_state, lens[r:r + mid], pad) <= cap:
+                    lo = mid
+                else:
+                    hi = mid - 1
+            n = lo if lo < 16 else lo - lo % 16
+            need = _varlen_ws_bytes(model, df_state, lens[r:r + n], pad)
+        passes.append((r, n, need))
+        r += n
+    return passes
+
+
+def _copy_rows(dst, src) -> None:
+    """dst[i].copy_(src[i]) for every i, on one device: one multi-tensor launch instead of one per row."""
+    if dst:
+        torch._foreach_copy_(dst, src)
+
+
+@torch.no_grad()
+def enhance_batch(model: DfNet, df_state: DF, clips, pad: bool = True, atten_lim_db: Optional[float] = None) -> list:
+    """``enhance()`` of many clips of different lengths, batched.  ``clips``: a sequence of ``[C_i, T_i]`` (or ``[T_i]``) float32 / int16
+    tensors, on the host (page-locked or not) or on the device.  Result i is what ``enhance(model, df_state, clips[i], pad, atten_lim_db)``
+    returns — shape, dtype, device and samples, bit for bit — and a 1-D clip gives a 1-D result.
+
+    The channels of every clip become consecutive rows; the rows are sorted longest first and cut into passes of at most _BATCH_ROWS rows
+    (fewer under the workspace cap of enhance()), one ``dfx_enhance_varlen[_pcm16]`` call each (include/dfx.h).  Every row of a pass runs the
+    frames of its longest row, so similar lengths share a pass.  16-bit and float clips go into separate passes."""
+    if not isinstance(model, DfNet):
+        raise TypeError("enhance_batch() of deepfilternet_amd needs a deepfilternet_amd.DfNet (see init_df)")
+    clips = list(clips)
+    dev = _lib.device()
+    cuda = dev.type == "cuda"
+    hop = df_state.hop_size()
+    lim_db = float(atten_lim_db) if atten_lim_db is not None else 0.0
+    L = _lib.lib()
+    views, results = [], []
+    for a in clips:
+        if a.dim() not in (1, 2):
+            raise ValueError("enhance_batch(): every clip must have shape [C, T] or [T]")
+        v = a.unsqueeze(0) if a.dim() == 1 else a
+        T = v.shape[1]
+        dt = torch.int16 if a.dtype == torch.int16 else torch.float32
+        pinned = cuda and a.device.type == "cpu" and a.is_pinned()
+        views.append(v)
+        results.append(torch.empty((v.shape[0], T if pad else T // hop * hop), dtype=dt, device=a.device, pin_memory=pinned))
+    for pcm16 in (True, False):
+        dt = torch.int16 if pcm16 else torch.float32
+        order = sorted((i for i in range(len(views)) if (results[i].dtype == torch.int16) == pcm16), key=lambda i: -views[i].shape[1])
+        rows = [(i, ch) for i in order for ch in range(views[i].shape[0])]
+        if not rows:
+            continue
+        lens = [views[i].shape[1] for i, _ in rows]
+        passes = _plan_passes(model, df_state, lens, pad)
+        ws = model.workspace(max(p[2] for p in passes))
+        pending = None
+        for r0, n, _ in passes:
+            prow, plen = rows[r0:r0 + n], lens[r0:r0 + n]
+            outs = [t if pad else t // hop * hop for t in plen]
+            x = _pack_rows(views, prow, plen, dt, dev, cuda)
+            y = torch.empty((n, max(max(outs), 1)), dtype=dt, device=dev)
+            arr = (C.c_int64 * n)(*plen)
+            _lib.check((L.dfx_enhance_varlen_pcm16 if pcm16 else L.dfx_enhance_varlen)(
+                model.handle, df_state.handle, _lib.ptr(x), n, x.shape[1], arr, int(bool(pad)), lim_db, _lib.ptr(y), y.shape[1], _lib.ptr(ws),
+                ws.numel(), _lib.stream()))
+            # rows of device clips are copied out on the device; rows of host clips come back in one copy, unpacked once the next pass is enqueued
+            on_dev = [j for j, (i, _) in enumerate(prow) if _lib.on_device(results[i])]
+            _copy_rows([results[prow[j][0]][prow[j][1]] for j in on_dev], [y[j, : outs[j]] for j in on_dev])
+            if pending is not None:
+                _unpack_host(*pending)
+                pending = None
+            if len(on_dev) < n:
+                yh = torch.empty(y.shape, dtype=dt, pin_memory=cuda)
+                yh.copy_(y, non_blocking=cuda)
+                ev = torch.cuda.Event() if cuda else None
+                if ev is not None:
+                    ev.record()
+                pending = (results, prow, outs, yh, ev, set(on_dev))
+            model.poll()
+        if pending is not None:
+            _unpack_host(*pending)
+    model.poll()
+    return [r[0] if a.dim() == 1 else r for r, a in zip(results, clips)]
+
+
+def _pack_rows(views, prow, plen, dt, dev, cuda):
+    """The rows of a pass as one [rows, longest] array on the device (what lies behind a row's own samples is never read): rows of host
+    clips through one page-locked buffer and one copy, rows of device clips copied on the device."""
+    n, T = len(prow), max(plen[0], 1)
+    on_dev = [_lib.on_device(views[i]) for i, _ in prow]
+    if all(on_dev):
+        x = torch.empty((n, T), dtype=dt, device=dev)
+    else:
+        h = torch.empty((n, T), dtype=dt, pin_memory=cuda)
+        for j, (i, ch) in enumerate(prow):
+            if not on_dev[j]:
+                h[j, : plen[j]].copy_(views[i][ch])
+        x = h.to(dev, non_blocking=cuda)
+    d = [j for j in range(n) if on_dev[j]]
+    _copy_rows([x[j, : plen[j]] for j in d], [views[prow[j][0]][prow[j][1]] for j in d])
+    return x
+
+
+def _unpack_host(results, prow, outs, yh, ev, done):
+    if ev is not None:
+        ev.synchronize()
+    for j, (i, ch) in enumerate(prow):
+        if j not in done:
+            results[i][ch].copy_(yh[j, : outs[j]])
+
+
 def enhance_files(model: DfNet, df_state: DF, input_files, output_dir: Optional[str] = None, suffix: Optional[str] = None,
                   compensate_delay: bool = True, atten_lim_db: Optional[float] = None, method: str = "sinc_fast"):
     """The body of the reference's file loop, ``df.enhance.main`` (enhance.py:73-89), without its argument parser: every file is
     decoded, brought to the model's sampling rate, enhanced, brought back to its own rate and written next to the input (or into
     ``output_dir``) as ``<name>_<suffix>.wav``.  A file that already has the model's rate moves as 16-bit PCM all the way (the two
     conversions of df/io.py run inside the STFT / ISTFT kernels: ``enhance()`` on an int16 tensor); one that has to be resampled takes the
-    float path (int16 -> float, resample, enhance, resample, float -> int16, all on the device).  Channels of a file are the batch, as in
-    the reference.  Returns the written paths."""
+    float path (int16 -> float, resample, enhance, resample, float -> int16, all on the device).  Returns the written paths, in input order.
+
+    The files are read in order and gathered into windows of at most _FILE_WINDOW_ROWS channels whose workspace, as one pass, fits the cap of
+    ``enhance()``; a window is enhanced with ``enhance_batch`` — every file gets the samples ``enhance()`` gives it alone, so the files written
+    are byte for byte those of one ``enhance()`` per file — and written before the next window is read."""
     from .io import load_audio, resample, save_audio
 
     sr = df_state.sr()
-    out = []
+    out, win, lens = [], [], []
+
+    def flush():
+        enhanced = enhance_batch(model, df_state, [a for _, a, _ in win], pad=compensate_delay, atten_lim_db=atten_lim_db)
+        for (file, _, meta), e in zip(win, enhanced):
+            if e.dtype != torch.int16:
+                e = resample(e, sr, meta.sample_rate, method=method)
+            out.append(save_audio(file, e, sr=meta.sample_rate, output_dir=output_dir, suffix=suffix))
+        win.clear()
+        lens.clear()
+
     for file in input_files:
         audio, meta = load_audio(file, sr=sr, verbose=False, method=method, pcm16=True)   # int16 when no resampling is needed
-        enhanced = enhance(model, df_state, audio, pad=compensate_delay, atten_lim_db=atten_lim_db)
-        if enhanced.dtype != torch.int16:
-            enhanced = resample(enhanced, sr, meta.sample_rate, method=method)
-        out.append(save_audio(file, enhanced, sr=meta.sample_rate, output_dir=output_dir, suffix=suffix))
+        more = lens + [audio.shape[-1]] * audio.shape[0]
+        if win and len(more) > _FILE_WINDOW_ROWS:
+            flush()
+        elif win:
+            need = _varlen_ws_bytes(model, df_state, more, compensate_delay)
+            cap = _workspace_cap(model, need)
+            if cap is not None and need > cap:
+                flush()
+        win.append((file, audio, meta))
+        lens.extend([audio.shape[-1]] * audio.shape[0])
+    if win:
+        flush()
     return out
+
+
+def _parse_epoch(value: str):
+    """df/enhance.py parse_epoch_type: 'best', 'latest' or an epoch number."""
+    try:
+        return int(value)
+    except ValueError:
+        if value not in ("best", "latest"):
+            raise ValueError(f"epoch must be 'best', 'latest' or a number, not {value!r}") from None
+        return value
+
+
+def main(argv=None):
+    """``python -m deepfilternet_amd.enhance``: the reference's ``deepFilter`` command (df/enhance.py:299-379) — arguments, then ``init_df``
+    and ``enhance_files``.  Returns the written paths."""
+    import argparse
+    import glob
+
+    ap = argparse.ArgumentParser(prog="python -m deepfilternet_amd.enhance", description="Enhance noisy audio files with DeepFilterNet on the GPU.")
+    ap.add_argument("--model-base-dir", "-m", type=str, default=None,
+                    help="model directory (config.ini + checkpoints/), a .dfx model file or the reference's <model>_onnx.tar.gz")
+    ap.add_argument("--pf", action="store_true", help="post-filter that slightly over-attenuates very noisy sections")
+    ap.add_argument("--output-dir", "-o", type=str, default=None, help="directory for the enhanced files (default: the current one)")
+    ap.add_argument("--epoch", "-e", default="best", type=_parse_epoch, help="checkpoint to load: 'best', 'latest' or an epoch number")
+    ap.add_argument("--no-delay-compensation", dest="compensate_delay", action="store_false",
+                    help="do not pad to compensate the delay of the real-time STFT / ISTFT")
+    ap.add_argument("--atten-lim", "-a", type=int, default=None, help="attenuation limit in dB (mixes the noisy signal back in)")
+    ap.add_argument("noisy_audio_files", type=str, nargs="*", help="noisy audio files")
+    ap.add_argument("--noisy-dir", "-i", type=str, default=None, help="directory of noisy audio files, instead of noisy_audio_files")
+    ap.add_argument("--no-suffix", action="store_false", dest="suffix", help="do not add the model suffix to the enhanced files")
+    ap.add_argument("--no-df-stage", action="store_true", help="mask only: no deep-filter stage")
+    args = ap.parse_args(argv)
+    if args.noisy_dir is not None:
+        if args.noisy_audio_files:
+            ap.error("only one of noisy_audio_files or --noisy-dir can be given")
+        files = sorted(glob.glob(os.path.join(args.noisy_dir, "*")))
+    elif not args.noisy_audio_files:
+        ap.error("no audio files given")
+    else:
+        files = args.noisy_audio_files
+    model, df_state, suffix, _ = init_df(args.model_base_dir, post_filter=args.pf, epoch=args.epoch, mask_only=args.no_df_stage)
+    out_dir = args.output_dir or "."
+    os.makedirs(out_dir, exist_ok=True)
+    return enhance_files(model, df_state, files, output_dir=out_dir, suffix=suffix if args.suffix else None,
+                         compensate_delay=args.compensate_delay, atten_lim_db=args.atten_lim)
+
+
+if __name__ == "__main__":
+    main()

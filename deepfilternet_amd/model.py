@@ -242,6 +242,30 @@ def read_onnx_targz(path: str) -> Tuple[ModelParams, Dict[str, np.ndarray]]:
     _lib.check(L.dfx_onnx_targz_read(os.fsencode(path), C.byref(cfg), None, 0, C.byref(n)))
     blob = np.empty(n.value, dtype=np.float32)
     _lib.check(L.dfx_onnx_targz_read(os.fsencode(path), C.byref(cfg), blob.ctypes.data_as(C.POINTER(C.c_float)), n.value, C.byref(n)))
+    return _from_cfg_blob(cfg, blob)
+
+
+def read_dfx(path: str) -> Tuple[ModelParams, Dict[str, np.ndarray]]:
+    """A ``.dfx`` model file (:func:`export_dfx`, ``dfx_model_save_file``: magic, version, configuration, float32 blob) as (ModelParams,
+    state-dict).  Version 1 files lack the last three configuration fields (all "none" / off), as ``dfx_model_load_file`` reads them."""
+    import struct
+
+    with open(path, "rb") as f:
+        data = f.read()
+    if data[:4] != b"DFXM" or len(data) < 12:
+        raise ValueError(f"{path}: not a .dfx model file")
+    ver, csz = struct.unpack_from("<II", data, 4)
+    if ver not in (1, 2) or csz > C.sizeof(_lib.ModelCfg) or len(data) < 20 + csz:
+        raise ValueError(f"{path}: .dfx model file of version {ver} / configuration size {csz}: re-export it with export_dfx")
+    cfg = _lib.ModelCfg()
+    C.memmove(C.addressof(cfg), data[12:12 + csz], csz)
+    (n,) = struct.unpack_from("<q", data, 12 + csz)
+    if n < 0 or len(data) < 20 + csz + 4 * n:
+        raise ValueError(f"{path}: truncated .dfx model file")
+    return _from_cfg_blob(cfg, np.frombuffer(data, dtype="<f4", count=n, offset=20 + csz))
+
+
+def _from_cfg_blob(cfg: _lib.ModelCfg, blob: np.ndarray) -> Tuple[ModelParams, Dict[str, np.ndarray]]:
     skip = {0: "none", 1: "identity", 2: "groupedlinear"}
     p = ModelParams(sr=cfg.sr, fft_size=cfg.fft_size, hop_size=cfg.hop_size, nb_erb=cfg.nb_erb, nb_df=cfg.nb_df,
                     min_nb_freqs=cfg.min_nb_freqs, df_order=cfg.df_order, df_lookahead=cfg.df_lookahead, lsnr_min=cfg.lsnr_min,

@@ -257,6 +257,21 @@ int dfx_enhance(const dfx_model *m, const dfx_state *st, const float *x, int64_t
  * launches, and bit-identical samples to dfx_pcm16_to_f32 -> dfx_enhance -> dfx_f32_to_pcm16.  Same workspace, same asynchrony. */
 int dfx_enhance_pcm16(const dfx_model *m, const dfx_state *st, const int16_t *x, int64_t B, int64_t T, int pad,
                       float atten_lim_db, int16_t *y, void *workspace, int64_t workspace_bytes, void *stream);
+/* enhance() of B clips of different lengths in one pass: row b of x holds lengths[b] samples (x_stride >= max lengths[b]; what lies behind
+ * them is never read); row b of y receives exactly what dfx_enhance(x row b, T = lengths[b]) stores, bit for bit (DFX_EXACT_FP32=1: within
+ * that mode's 1e-6 RMS, its kernels' bits depend on the pass's frame count) — out_len_b = lengths[b]
+ * (pad) or (lengths[b]/hop)*hop (no pad) samples — then zeros up to max_b out_len_b (y_stride >= that; y is not written behind it).
+ * lengths: host memory, read during the call (the caller may reuse it when the call returns).  Every row runs the frames of the longest
+ * one — the padded frames of a shorter row still cost their GRU steps —, so pass clips of similar lengths together.  Same asynchrony, pacing,
+ * fault reporting and workspace rules as dfx_enhance, with the workspace from dfx_enhance_varlen_workspace_bytes; a faulted pass stores its
+ * poison (NaN, 16-bit PCM: zeros) in the out_len_b samples of every row, the zeros behind them stay zeros.  DFX_ERR_INVALID_ARG,
+ * before any device work, for a negative length, x_stride < max length, y_stride < max out_len, a workspace too small, or a null buffer
+ * (lengths included) when B > 0. */
+int dfx_enhance_varlen_workspace_bytes(const dfx_model *m, const dfx_state *st, int64_t B, const int64_t *lengths, int pad, int64_t *bytes);
+int dfx_enhance_varlen(const dfx_model *m, const dfx_state *st, const float *x, int64_t B, int64_t x_stride, const int64_t *lengths,
+                       int pad, float atten_lim_db, float *y, int64_t y_stride, void *workspace, int64_t workspace_bytes, void *stream);
+int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int16_t *x, int64_t B, int64_t x_stride, const int64_t *lengths,
+                             int pad, float atten_lim_db, int16_t *y, int64_t y_stride, void *workspace, int64_t workspace_bytes, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Streaming: the frame loop of the reference's real-time runtime, libDF/src/tract.rs `DfTract::process` (:509-642), exported by
