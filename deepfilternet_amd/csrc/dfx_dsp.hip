@@ -385,7 +385,7 @@ static bool ana_in_place(const dfx_state *st) {
     const DfxFftPlan &pl = st->plan;   // (the 48 kHz / 20 ms plan transforms in place; any other plan takes the two-buffer passes)
     return pl.M == 480 && pl.nstage == 5 && pl.radix[0] == 4 && pl.radix[1] == 4 && pl.radix[2] == 2 && pl.radix[3] == 3 && pl.radix[4] == 5;
 }
-// the 480-point transform on the matrix pipe (dfx_fft480_mfma) instead of the radix passes: DFX_FFT_MFMA=1.  Not the default: built, validated
+// the 480-point transform on the matrix pipe (dfx_fft480_mfma) instead of the radix passes.  Rejected: built, validated
 // and measured in round 5 — analysis 0.535 vs 0.478 ms, the finishing kernel 0.74 vs 0.63 (profiles/r05_dft_mfma.log)
 // (round 6: no switch any more and no instance of the MF forms in the library; dfx_fft480_mfma stays in dfx_dsp_kernels.h as the record of the
 // experiment, with its tables)

@@ -416,36 +416,29 @@ struct dfx_model {
     size_t lsnr_w = 0;
     float lsnr_b = 0.f;
     // dfx_k_emb_fan (one pass over the encoder GRU's output for emb and its consumers): fragments [chunks][8][64] float4, 0 chunks = the
-    // grouped linears of this model do not nest the way the kernel needs (then the separate grouped GEMMs run); DFX_FUSE_EMB=0: off
+    // grouped linears of this model do not nest the way the kernel needs (then the separate grouped GEMMs run)
     size_t fan_w = 0;
     int fan_chunks = 0;            // super-chunks of 32 hidden columns (0: not available)
     int fan_kind[3] = {0, 0, 0};   // per consumer (dec_in, dfg_in, df_skip): 0 absent, 1 narrow (32 -> 16 groups), 2 wide (64 -> 32 groups)
-    bool fuse_emb = true;
     // dfx_k_enc_fan (df_fc_emb + the encoder GRU's linear_in in one pass over c1): fragment offsets, 0 groups = shapes do not nest
     size_t efan_w1 = 0, efan_w2 = 0;
     int efan_groups = 0;
     // dfx_k_df_enc_h3 (df_conv0 -> df_conv1 -> df_fc_emb -> linear_in in one kernel, c1 never stored): fc / linear_in fragments; 0 chunks = the
-    // shapes do not fit (then dfx_k_df_conv01_h3 + dfx_k_enc_fan run); DFX_FUSE_DFENC=0: off
+    // shapes do not fit (then dfx_k_df_conv01_h3 + dfx_k_enc_fan run)
     size_t dfenc_fc = 0, dfenc_in = 0;
     int dfenc_chunks = 0;
     float dfenc_fc_unscale = 1.f, dfenc_in_unscale = 1.f;
-    bool fuse_dfenc = true;
     // dfx_k_df_out_h3 (df_out + tanh + c0p as a row-streaming kernel of its own): fragments [G][ceil(Ng / 16)]; 0 = shapes do not fit
-    // (dfx_k_ggemm then); DFX_DFOUT_LEAN=0: off
+    // (dfx_k_ggemm then)
     size_t dfo_h3 = 0;
     int dfo_nu = 0;
     float dfo_unscale = 1.f;
-    bool dfout_lean = true;
-    bool fuse_encfan = true;       // DFX_FUSE_ENCFAN=0 (dev A/B): df_fc_emb and linear_in as two grouped GEMMs while the rest of DFX_FUSE_EMB stays on
-    bool fuse_dfa = true;          // DFX_FUSE_DFA=0: deep filter and ISTFT of enhance() as two kernels with spec_e between them
-    // The ERB decoder's convolutions as ONE launch (dfx_k_erb_tail: d3 / d2 / d1 stay in LDS, -12 KB per frame beside the GRU chain);
-    // DFX_FUSE_TAIL=0: three launches (convt3, convt2, convt1 + conv0_out).  Measured at config 2 (profiles/r03_fusion_ab.log): the first
-    // version (8 waves per CU) 2.19 ms alone against 1.5 ms for the three launches and +0.37 ms per step; the second (12 waves per CU, 8.5 KB
+    // The ERB decoder's convolutions as ONE launch (dfx_k_erb_tail: d3 / d2 / d1 stay in LDS, -12 KB per frame beside the GRU chain) where
+    // erb_tail_ok() holds; otherwise three launches (convt3, convt2, convt1 + conv0_out).  Measured at config 2 (profiles/r03_fusion_ab.log): the
+    // first version (8 waves per CU) 2.19 ms alone against 1.5 ms for the three launches and +0.37 ms per step; the second (12 waves per CU, 8.5 KB
     // of strips per wave, fragments read from LDS per k-chunk) 1.32 ms alone and -0.25 ... -0.45 ms per step.
-    bool fuse_tail = true;
-    // e0 = erb_conv0's output (8 KB per frame) is not stored: the fused decoder tail recomputes it from the three feature rows it depends on
-    // (DFX_E0_RECOMPUTE=0: written by dfx_k_erb_enc, read back by dfx_k_erb_tail)
-    bool e0_recompute = true;
+    // e0 = erb_conv0's output (8 KB per frame) is then not stored: the fused decoder tail recomputes it from the three feature rows it depends on
+    // (rejected: written by dfx_k_erb_enc, read back by dfx_k_erb_tail)
     size_t cp_w1 = 0, cp_w2 = 0, cp_b = 0;   // df_convp, tiled form (kt > 5)
     size_t cp_weff = 0, cp_b16 = 0;          // df_convp, folded sliding-window form (kt <= 5)
     size_t cin_weff = 0, cin_b = 0;          // enc.df_conv0 folded into a dense 3x3 conv 2 -> C
@@ -472,18 +465,15 @@ struct dfx_model {
     mutable bool pass_pending = false;
     bool enqueue_ahead = false;
     bool concurrent = false;
-    bool have_streams = false;
-    int max_chunks = 1;       // batch chunks pipelined by dfx_enhance (DFX_CHUNKS; measured: no gain over time-chunk pipelining)
+    int max_chunks = 1;       // batch chunks pipelined by dfx_enhance (dfx_model_set_pipeline; measured: no gain over time-chunk pipelining)
     int tchunks = 12;         // time chunks of the layer-pipelined GRU phase (DFX_TCHUNKS)
     int tchunk_min = 32;      // shortest chunk worth a launch (frames)
     bool run_df = true;       // DfNet(run_df=False): mask only (dfx_model_set_run_df)
     bool exact_fp32 = false;  // DFX_EXACT_FP32=1: keep the dense contractions on the exact fp32 MFMA path
     // df_conv0's output c0 is recomputed by its consumers instead of being stored when the pathway conv has the sliding-window kernel
-    // (kt <= 5); DFX_FUSE_C0=0 restores the materialised c0 (dfx_k_conv_in_df -> dfx_k_pwconv / dfx_k_df_convp2).
+    // (kt <= 5, df_order <= 8); otherwise c0 is materialised (dfx_k_conv_in_df -> dfx_k_pwconv / dfx_k_df_convp2 / dfx_k_df_convp).
     bool fuse_c0 = true;
     bool c0_batch_unfused = false;   // exact mode: batch passes materialise c0 (below)
-    // frame-resident ERB encoder head / decoder tail (dfx_k_erb_enc, dfx_k_erb_dec10); DFX_FUSE_ERB=0: layer-by-layer kernels
-    bool fuse_erb = true;
     // persistent GRU phase (dfx_k_gru_seq): flag words [ready: 8][emb: 1][pad][done: 8 * DFX_SEQ_GMAX], monotonic over the model's life
     unsigned int *d_sync = nullptr;
     unsigned int *d_psync = nullptr;    // pair form of the persistent GRU phase: [DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX / 2][48] words
@@ -493,32 +483,18 @@ struct dfx_model {
     unsigned long long *d_trace = nullptr;   // dev aid (DFX_SEQ_TRACE=1): chunk timestamps of the last persistent GRU launch
     mutable int trace_dims[3] = {0, 0, 0};
     bool gru_seq = true;                // DFX_GRU_SEQ=0: one launch per (layer, time chunk) synchronised with events (round-1 form)
-    bool phase_late = true;             // DFX_PHASE_LATE=0: the GRU phase is enqueued right behind the front (no staged enqueue)
-    int proj_rt = 0;                    // DFX_PROJ_RT=1|2|3: one form of the projection kernel for every launch size
     // switches of the persistent GRU phase and its side work, read when the handle is created like the rest; -1 = "the default"
     struct {
-        int follow = 2;                 // DFX_SEQ_FOLLOW (see seq_follow_mode)
-        int chunks = 0, ramp = 0;       // DFX_SEQ_CHUNKS (0: 12, or 16 without followers), DFX_SEQ_RAMP
-        bool publish = true;            // DFX_SEQ_PUBLISH
-        bool xcd_light = true;          // DFX_SEQ_XCD_LIGHT
+        int chunks = 0;                 // DFX_SEQ_CHUNKS (0: 12)
         bool gru_pair_far = false;      // DFX_GRU_PAIR_FAR=1 (test hook): the pairs' hand-overs in their agent-scope form, as if the halves sat on different XCDs
         bool gru_pair = true;           // DFX_GRU_PAIR=0: every 16-clip group's recurrence on one CU (W_hh streamed from the L2) instead of 32 clips on a pair of CUs (dfx_gru_pair.h)
         int convp_late = -1;            // DFX_CONVP_LATE (percent)
-        int convp_after_p0 = -1;        // DFX_CONVP_AFTER_P0
         int p0_ahead = 3;               // DFX_SEQ_P0_AHEAD
         int tail_every = 1;             // DFX_SEQ_TAIL_EVERY
         int dftail_every = 0;           // DFX_SEQ_DFTAIL_EVERY (0: the rule in forward_impl)
         bool tail_split = true;         // the ERB decoder's linear_out on a stream of its own beside the decoder tail (round 6; DFX_TAIL_SPLIT=0 in -DDFX_DEV builds)
-        int64_t fan_few_rows = 4096;    // DFX_FAN_FEW_ROWS
         int64_t convp_elems = (int64_t)1 << 29;   // DFX_CONVP_ELEMS (test hook)
     } sw;
-    // DFX_FRONT_GRAIN=k[,kp]: k (kp) times as many, shorter workgroups for df_conv0->1 (df_convp).  df_convp owns whole SIMDs (one wave of
-    // 512 registers each) and is needed last (by df_out, deep in the GRU phase): as a persistent grid of long workgroups it held every SIMD
-    // for 4.7 ms while the kernels on the front's critical path (ERB encoder convs -> embedding GEMMs) waited for slots (erb_conv2: 1.8 ms
-    // instead of 0.3).  In 16 x shorter workgroups (40-frame segments, 10 % warm-up overhead) its slots come free every ~35 us and the
-    // dispatcher lets the other queues in: the front ends 1.1 ms earlier, df_convp finishes under the first 2 ms of the GRU phase;
-    // 17.7 -> 17.15 ms per step (8 ... 32: the same; df_conv0->1's own grain: no effect).
-    int front_grain = 1, front_grain_p = 16;
     // Error words, written by kernels, read by the host (page-locked host memory the device can store to: dfx_env_err_words_alloc):
     // [0] unused, [1] fp16-split range, [2] a flag wait of the persistent GRU phase timed out.
     // The host looks at them wherever it waits for the device anyway (pass_begin, dfx_model_check) and at the start of every call
@@ -1201,14 +1177,13 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
         m->concurrent = !(e && e[0] == '0');
         const char *x = getenv("DFX_EXACT_FP32");
         m->exact_fp32 = x && x[0] == '1';
-        // (round 6: the DFX_FUSE_* / DFX_E0_RECOMPUTE / DFX_DFOUT_LEAN / DFX_PROJ_RT / DFX_SEQ_* ... switches of rounds 2-5 are gone — the forms they
-        // selected were measured and lost; what remains below are properties of the model's shape, and tools/dev/patches/ keeps the experiments)
+        // (the forms that rounds 2-5 could select by environment were measured and lost; which kernel runs is decided by the model's shape and
+        // the arithmetic mode alone, and tools/dev/patches/ keeps the experiments)
         m->fuse_c0 = m->cfg.df_pathway_kernel_size_t <= 5 && 2 * m->cfg.df_order <= 16;
         // Exact mode, batch passes: c0 is written once and read by its two consumers instead of being recomputed by both — on fp32 matrix ops a c0
         // tile is 20 ops of 32 cycles (3 of 16 on the fp16-split path), and the two recomputing kernels side by side are the exact front's 10 ms:
         // 28.65 vs 29.45 ms per step (the frame-by-frame runtime always uses the recomputing forms)
         m->c0_batch_unfused = m->exact_fp32 && m->fuse_c0;
-        m->fuse_erb = true;
         const char *gq = getenv("DFX_GRU_SEQ");
         {
             const char *gp = getenv("DFX_GRU_PAIR");
@@ -1217,12 +1192,9 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
             m->sw.gru_pair_far = gf && gf[0] == '1';
         }
         m->gru_seq = !(gq && gq[0] == '0') && !dfx_env_is_emulator();
-        m->fuse_emb = m->fuse_encfan = m->fuse_dfa = m->fuse_tail = m->e0_recompute = m->fuse_dfenc = m->dfout_lean = true;
         const char *cep = getenv("DFX_CHECK_EVERY_PASS"), *spl = getenv("DFX_SYNC_SPIN_LIMIT");
         m->check_every_pass = cep && cep[0] == '1';
         if (spl && atoi(spl) > 0) m->spin_limit = atoi(spl);
-        m->phase_late = true;
-        m->proj_rt = 0;
         {
             const char *cel = getenv("DFX_CONVP_ELEMS");   // test hook: the 32-bit-offset split of df_convp at small sizes
             if (cel && atoll(cel) > 0) m->sw.convp_elems = atoll(cel);
@@ -1271,7 +1243,6 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
                 dfx_model_free(m);
                 DFX_FAIL(DFX_ERR_HIP, "dfx_model_create: could not create the auxiliary streams/events");
             }
-            m->have_streams = true;
         }
         // The persistent GRU phase synchronises through device flags and needs its streams to run concurrently: checked with a handshake
         // (hwq_probe_run) — not here but before the first pass that would use the persistent form, or when DFX_Q_HWQ_PROBE /
@@ -1313,7 +1284,7 @@ extern "C" void dfx_model_free(dfx_model *m) {
 }
 extern "C" int dfx_model_set_streams(dfx_model *m, int enable) {
     if (!m) DFX_FAIL(DFX_ERR_INVALID_ARG, "null");
-    m->concurrent = enable != 0 && m->have_streams;
+    m->concurrent = enable != 0;
     return DFX_OK;
 }
 extern "C" int dfx_model_set_run_df(dfx_model *m, int enable) {
@@ -1326,7 +1297,7 @@ extern "C" int dfx_model_set_pipeline(dfx_model *m, int time_chunks, int min_chu
     m->tchunks = time_chunks < DFX_MAX_TCHUNKS ? time_chunks : DFX_MAX_TCHUNKS;
     m->tchunk_min = min_chunk_frames;
     m->max_chunks = batch_chunks < DFX_MAX_LANES ? batch_chunks : DFX_MAX_LANES;
-    for (int l = 1; l < m->max_chunks && m->have_streams; ++l)
+    for (int l = 1; l < m->max_chunks; ++l)
         if (!dfx_create_lane(m, l)) DFX_FAIL(DFX_ERR_HIP, "dfx_model_set_pipeline: could not create the streams of lane %d", l);
     return DFX_OK;
 }

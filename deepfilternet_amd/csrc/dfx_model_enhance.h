@@ -76,7 +76,7 @@ extern "C" int dfx_enhance_workspace_bytes(const dfx_model *m, const dfx_state *
     // sized for the finest chunking the handle may use, so toggling dfx_model_set_streams never needs a bigger workspace
     int64_t sizes[DFX_MAX_LANES];
     int64_t total = (int64_t)plan_enh(m, st, B, T, pad).total;
-    if (m->max_chunks > 1 && m->have_streams) {
+    if (m->max_chunks > 1) {
         const bool was = m->concurrent;
         const_cast<dfx_model *>(m)->concurrent = true;
         const int nc = enh_chunks(m, B, sizes);

@@ -74,7 +74,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     // dfx_k_emb_fan: emb = enc_out_skip(y) and its consumers in one pass.  emb itself is only written when something outside the kernel
     // still reads it (the ERB decoder's skip connection, an identity skip around the DF GRU).  df_skip(emb) lands in xdf WITHOUT the
     // DF GRU's output (which does not exist yet): df_out then takes its operand as the sum y_df + xdf (DfxGgArgs::a2).
-    const bool fan = m->fuse_emb && m->fan_chunks > 0 && !c.enc_concat && emb == 64 * m->fan_chunks;   // (exact fp32 matrix ops: also with DFX_EXACT_FP32=1)
+    const bool fan = m->fan_chunks > 0 && !c.enc_concat && emb == 64 * m->fan_chunks;   // (exact fp32 matrix ops: also with DFX_EXACT_FP32=1)
     const bool fan_skp = fan && run_df && c.df_gru_skip == DFX_SKIP_GROUPEDLINEAR && m->fan_kind[2] == 1;
     auto emb_fan = [&](const float *y, float *dec_x, int64_t M, hipStream_t st, DfxRowMap rm, const DfxPublish *pub = nullptr) -> int {
         const float *res = nullptr;
@@ -88,7 +88,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     };
     // c = tanh(df_out(c)).view(b,t,F',2O) + c0p   (:329-330) of M rows; cfeat (+ cfeat2) is df_out's operand
     auto df_out_rows = [&](const float *cfeat, const float *cfeat2, int64_t M, hipStream_t st, DfxRowMap rm) -> int {
-        if (m->dfout_lean && m->dfo_nu > 0 && !m->exact_fp32 && M > 0 && R * (int64_t)NO * Fd < ((int64_t)1 << 31)) {   // row-streaming form (dfx_k_df_out_h3)
+        if (m->dfo_nu > 0 && !m->exact_fp32 && M > 0 && R * (int64_t)NO * Fd < ((int64_t)1 << 31)) {   // row-streaming form (dfx_k_df_out_h3)
             DfxDfOutArgs A;
             A.a = cfeat, A.a2 = cfeat2;
             A.wf = reinterpret_cast<const dfx_h8 *>(m->p(m->dfo_h3));
@@ -136,16 +136,17 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     if (sc && sc->df_post && !post_behind_convp && (rc = sc->df_post(x1))) return rc;
     // ---- Encoder, DF branch on x1 (deepfilternet3.py:176-179).  By default c0 = df_conv0(feat_spec) never exists in HBM: its two
     // consumers (df_conv1 here, df_convp below) recompute the tiles they need from feat_spec on the matrix core.
-    const bool fuse_c0 = m->fuse_c0 && !(m->c0_batch_unfused && !sc);
-    if (sc && !fuse_c0) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8, DFX_FUSE_C0 unset)");
-    const float *cp_feat = fuse_c0 ? feat_spec : nullptr;
-    const bool fuse_h3 = fuse_c0 && !m->exact_fp32 && C % 32 == 0 && m->cp_h3;  // fp16-split matrix ops (default)
-    const bool fuse_dec = E % 2 == 0 && m->fuse_erb && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
+    const bool c0_fused = m->fuse_c0 && !(m->c0_batch_unfused && !sc);   // this pass (m->fuse_c0: the model's shape allows it)
+    if (sc && !c0_fused) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
+    const float *cp_feat = c0_fused ? feat_spec : nullptr;
+    const bool fuse_h3 = c0_fused && !m->exact_fp32 && C % 32 == 0 && m->cp_h3;  // fp16-split matrix ops (default)
+    // frame-resident ERB encoder head / decoder tail (dfx_k_erb_enc, dfx_k_erb_dec10 / dfx_k_erb_tail) where a frame fits the LDS; else layer by layer
+    const bool fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
     const bool fuse_tail = fuse_dec && erb_tail_ok<C>(m, E);
-    const bool fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && m->fuse_erb && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
-    const bool no_e0 = fuse_tail && fuse_enc && m->e0_recompute && R < ((int64_t)1 << 31);   // e0 never exists in HBM
+    const bool fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
+    const bool no_e0 = fuse_tail && fuse_enc;   // e0 never exists in HBM
     const float *e0r = no_e0 ? nullptr : e0;   // what the decoder tail is handed
-    if (sc && !fuse_enc) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused ERB encoder head (DFX_FUSE_ERB unset)");
+    if (sc && !fuse_enc) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
     const DfxGate *gate = sc ? sc->gate : nullptr;
     if (gate && T - t_begin != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "gated streaming passes carry exactly one new frame");
     // ---- How the GRU phase will run — decided before the front, because its persistent form starts UNDER the front.
@@ -177,38 +178,27 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     int sb[DFX_GS_MAX_CHUNKS + 1];   // chunk boundaries of the persistent form
     int Ks = 0;
     if (use_seq) {
-        // short chunks at the start (the next layer can begin after the first chunk + its preparation: the
+        // Uniform chunks.  Rejected: short chunks at the start (the next layer can begin after the first chunk + its preparation: the
         // pipeline of 3 layers fills in ~3 short chunks instead of 3 long ones) and at the end (what is left to do after the last
-        // recurrence step is one short chunk's decoder tail), uniform in between
+        // recurrence step is one short chunk's decoder tail), uniform in between;
         // measured at batch 256 x 1002 frames (ms per step): 8 body chunks + ramp from 32: 21.28; 12 + 16: 21.91; 12, no ramp: 21.47;
         // 6 + 32: 21.35; 4 + 32: 22.45; 16 + 16: 22.69 (the event-based form: 22.07); after the decoder convolutions went to the
         // staged fp16-split kernels (lighter background): 8 + 32: 20.1; 10 + 32: 19.85; 12 + 32: 19.99; 12 + 16: 20.27; 16 + 32: 21.0
         // round 4, after e0 / c1 / the grouped-GEMM df_out left the phase (lighter side work, shorter hand-overs), same-box A/B: 10 + ramp 32: 14.47;
         // 12 uniform chunks, no ramp: 14.12; 13: 14.17; 14: 14.14; 12 + ramp 48: 14.20; 15 + 48: 14.27; 16: 15.1 (chunks of < 16384 rows take the
         // small-launch forms of the fan-out kernels) -> 12 uniform chunks
-        const int ramp0 = m->sw.ramp;
-        // 16 chunks where the producers raise their flags themselves (DfxPublish: 17 launches per chunk), 12 where a one-thread launch does
-        // (22 per chunk: the exact mode, DFX_SEQ_PUBLISH=0) — measured 13.24-13.28 (16) vs 13.37-13.49 (12) ms per step, measurements R5.10
-        const int kenv = m->sw.chunks;
-        const bool kpub = m->sw.publish;
-        // (with followers only the encoder layer's projections and the decoder tails are still per chunk: 12 again, 12.98 vs 13.12 ms at 16)
-        const int kbody = kenv > 0 ? kenv : (kpub && !m->exact_fp32 && seq_follow_mode(m) <= 0 ? 16 : 12);
-        const int64_t body = std::max<int64_t>(dfx_ceil_div(T, (int64_t)kbody), m->tchunk_min);   // uniform chunk length: DFX_SEQ_CHUNKS=n gives n chunks (ceil: 1002 / 12 -> 84, not 83 and a 13th chunk)
-        std::vector<int> sizes;
-        int64_t left = T;
-        for (int64_t r = ramp0; ramp0 > 0 && r < body && left > 4 * body; r *= 2) sizes.push_back((int)r), left -= r;   // up
-        std::vector<int> down;
-        for (int64_t r = ramp0; ramp0 > 0 && r < body && left > 3 * body; r *= 2) down.push_back((int)r), left -= r;     // down (round 5, the ramp at the end alone, 16 / 32 frames: 13.09-13.22 vs 13.11-13.18 ms, noise)
-        const int nbody = (int)std::max<int64_t>(1, std::min<int64_t>(dfx_ceil_div(left, body), DFX_GS_MAX_CHUNKS - (int64_t)sizes.size() - (int64_t)down.size()));
-        for (int i = 0; i < nbody; ++i) sizes.push_back((int)(left * (i + 1) / nbody - left * i / nbody));
-        for (auto it = down.rbegin(); it != down.rend(); ++it) sizes.push_back(*it);
-        Ks = (int)sizes.size();
-        sb[0] = 0;
-        for (int i = 0; i < Ks; ++i) sb[i + 1] = sb[i] + sizes[i];
+        // Rejected: 16 chunks without followers (the producers raise their flags themselves, DfxPublish: 17 launches per chunk instead of 22 with a
+        // one-thread launch per flag) — 13.24-13.28 (16) vs 13.37-13.49 (12) ms per step, measurements R5.10; with followers only the encoder
+        // layer's projections and the decoder tails are still per chunk: 12 again, 12.98 vs 13.12 ms at 16.  A ramp at the end alone (round 5,
+        // 16 / 32 frames): 13.09-13.22 vs 13.11-13.18 ms, noise.
+        const int kbody = m->sw.chunks > 0 ? m->sw.chunks : 12;
+        const int64_t body = std::max<int64_t>(dfx_ceil_div(T, (int64_t)kbody), m->tchunk_min);   // uniform chunk length: DFX_SEQ_CHUNKS=n (dev builds) gives n chunks (ceil: 1002 / 12 -> 84, not 83 and a 13th chunk)
+        Ks = (int)std::max<int64_t>(1, std::min<int64_t>(dfx_ceil_div(T, body), DFX_GS_MAX_CHUNKS));
+        for (int i = 0; i <= Ks; ++i) sb[i] = (int)(T * i / Ks);
     }
     const int kt = c.df_pathway_kernel_size_t;
-    int64_t convp_split = T;   // frames [convp_split, T) of df_convp are enqueued under the GRU phase (DFX_CONVP_LATE)
-    // df_conv0 -> df_conv1 of frames [t0, t1) (fuse_c0)
+    int64_t convp_split = T;   // frames [convp_split, T) of df_convp are enqueued under the GRU phase
+    // df_conv0 -> df_conv1 of frames [t0, t1) (c0_fused)
     auto df1_range = [&](int64_t t0, int64_t t1, hipStream_t st) -> int {
         if (fuse_h3) return launch_conv01_h3<C>(m, m->dfc1, feat_spec, c1, B, T, Fd, Fd / 2, 2, st, t0, Lk, t1, featT);
         return launch_conv01<C>(m, m->dfc1, feat_spec, c1, B, T, Fd, Fd / 2, 2, st, t0, Lk, t1);
@@ -322,8 +312,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         return launch_pw<C>(DFX_PW_MODE_DW3, m, m->erb3, e2, nullptr, e3, Rk, E / 4, E / 4, 1, st, rm);
     };
     // cemb = relu(df_fc_emb(c1.flatten)); emb_in = e3.flatten + cemb (:179-182), then enc.emb_gru's linear_in (SqueezedGRU_S :149-158).
-    // (DFX_FUSE_EMB=0 also restores the two grouped GEMMs of the front)
-    const bool enc_fan = m->fuse_emb && m->fuse_encfan && m->efan_groups > 0 && !c.enc_concat && emb == 16 * m->efan_groups;
+    const bool enc_fan = m->efan_groups > 0 && !c.enc_concat && emb == 16 * m->efan_groups;
     auto emb_range = [&](int64_t Rk, DfxRowMap rm, hipStream_t st) -> int {
         int r;
         if (enc_fan) return launch_enc_fan(m, c1, e3, c.emb_gru_skip_enc != DFX_SKIP_NONE ? emb_in : nullptr, xa, Rk, st, rm);
@@ -336,10 +325,10 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         return launch_glin(m, m->enc_in, emb_in, DFX_ACT_RELU, nullptr, xa, Rk, st, rm);
     };
     // the DF branch of the encoder as one kernel behind the ERB convolutions (it adds e3), c1 never stored
-    const bool dfenc = m->fuse_dfenc && fuse_h3 && enc_fan && m->dfenc_chunks > 0 && B * T * (int64_t)emb < ((int64_t)1 << 31) &&
+    const bool dfenc = fuse_h3 && enc_fan && m->dfenc_chunks > 0 && B * T * (int64_t)emb < ((int64_t)1 << 31) &&
                        B * (featT > 0 ? featT : T) * Fd < ((int64_t)1 << 29);   // (32-bit element offsets inside the kernel; beyond: the two kernels)
     {   // ---- the front: the frames [t_begin, T) that this pass computes
-        if (fuse_c0) {
+        if (c0_fused) {
             if ((rc = signal(EV_C0, x1)) || (rc = wait(EV_C0, x2))) return rc;  // df_convp only needs feat_spec
             if (!dfenc && dfx_dev_stage(3) && (rc = df1_range(t_begin, T, x1))) return rc;
         } else {
@@ -369,11 +358,11 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             // Round 5: with the persistent GRU phase the pathway conv is released only when the front has run, i.e. it runs UNDER the phase: the
             // front's critical path (ERB convolutions -> DF encoder) has the chip to itself, and since the decoder tail got 0.4 ms lighter the
             // phase has the room: 13.50 / 13.54 -> 13.18 / 13.22 ms per step (same box; 30 / 50 / 70 % of the frames deferred: 13.41 / 13.41 /
-            // 13.48; in round 4, with the heavier tail, the same move measured as noise).  DFX_CONVP_LATE=p defers the last p percent (0: as before).
-            // Exact mode with followers: in front of the phase, beside the (long) exact front — under the phase it starves the encoder layer's first
+            // 13.48; in round 4, with the heavier tail, the same move measured as noise).  DFX_CONVP_LATE=p (dev builds) defers the last p percent.
+            // Exact mode: in front of the phase, beside the (long) exact front — under the phase it starves the encoder layer's first
             // projections on the CUs the followers leave (25.9 vs 30.3 ms per step).
             const int late_env = m->sw.convp_late;
-            const int late_pct = late_env >= 0 ? late_env : (m->exact_fp32 && seq_follow_mode(m) >= 2 ? 0 : 100);
+            const int late_pct = late_env >= 0 ? late_env : (m->exact_fp32 ? 0 : 100);
             convp_split = use_seq && late_pct > 0 ? T - (T - t_begin) * late_pct / 100 : T;
             if (convp_split > t_begin && dfx_dev_stage(1) && (rc = convp_range(t_begin, convp_split, x2))) return rc;
             if (post_behind_convp && (rc = sc->df_post(x2))) return rc;
@@ -499,44 +488,39 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             unsigned int *ready = m->d_sync, *embf = m->d_sync + 8, *done = m->d_sync + 16;
             unsigned int *pcnt = m->d_sync + 16 + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;   // one completion counter per producing stream (layer), [8] = emb
             // a layer's input projection of chunk k, and ready[l] = chunk k + 1 behind it: raised by the projection kernel's last workgroup
-            // (DfxPublish; DFX_SEQ_PUBLISH=0 or the exact mode: by a one-thread launch behind it, as before round 5)
-            const bool publish = m->sw.publish;
-            // Follower workgroups (dfx_k_proj_follow) feed the decoder layers in blocks of 16 steps instead of time chunks (seq_follow_mode; default 2:
-            // all of them — a follower of the encoder GRU, dfx_k_emb_follow, runs dfx_k_emb_fan's arithmetic per block of 8 steps and the stacks' first
-            // layers' projection followers read what it wrote; 1: only the layers whose input is the output of the layer below; 0: launches per chunk).
-            const int follow_env = seq_follow_mode(m);
+            // (DfxPublish; the exact mode: by a one-thread launch behind it, as before round 5)
+            // Follower workgroups (dfx_k_proj_follow) feed the decoder layers in blocks of 16 steps instead of time chunks, all of them or none:
+            // a follower of the encoder GRU, dfx_k_emb_follow, runs dfx_k_emb_fan's arithmetic per block of 8 steps and the stacks' first
+            // layers' projection followers read what it wrote (since the same-XCD hand-over, measurements R5.12; rejected: followers for the
+            // layers whose input is the output of the layer below only, for the first layers only, launches per chunk for all).
             unsigned int *yprog = pcnt + 16, *giprog = yprog + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
             unsigned int *embprog = yprog + (size_t)(DFX_MAX_GRU_LAYERS - 1) * DFX_SEQ_GMAX;   // (the row of a layer that cannot exist: nl < 8 below)
-            // same-XCD hand-overs (DfxXcd; DFX_SEQ_XCD_LIGHT=0: every block hand-over with the agent-scope release / acquire)
-            const bool xcd_light = m->sw.xcd_light;
-            unsigned int *xtab = xcd_light ? giprog + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX : nullptr;
-            unsigned int *xstat = xtab ? xtab + 3 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX : nullptr;
+            // same-XCD hand-overs (DfxXcd; rejected: every block hand-over with the agent-scope release / acquire)
+            unsigned int *xtab = giprog + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
+            unsigned int *xstat = xtab + 3 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
             const unsigned int xtag = (m->seq_pbase & 0x0fffffffu) << 4;
             auto xword = [&](int kind, int layer) { return xtab + ((size_t)kind * DFX_MAX_GRU_LAYERS + layer) * DFX_SEQ_GMAX; };
             const unsigned int pbase = m->seq_pbase;
             bool followed[DFX_MAX_GRU_LAYERS] = {};
             int nfollow = 0;
             const int lfirst_df = 1 + ndec;
-            const bool follow_emb = follow_env >= 2 && fan && c.emb_gru_skip_enc != DFX_SKIP_GROUPEDLINEAR && nl < DFX_MAX_GRU_LAYERS &&
+            const bool follow_emb = fan && c.emb_gru_skip_enc != DFX_SKIP_GROUPEDLINEAR && nl < DFX_MAX_GRU_LAYERS &&
                                     (nl + nl) * groups <= dfx_env_num_cus() * 3 / 4 && nl - 1 <= DFX_PF_MAX;
-            if (follow_env >= 1) {
-                for (int l = 1; l < nl; ++l) {
-                    const bool first = l == 1 || l == lfirst_df;   // a stack's first layer reads a grouped linear of emb, the others the layer below
-                    if (first ? follow_emb : follow_env != 3) followed[l] = true, ++nfollow;   // (3: the first layers only)
-                }
-                if (nfollow > DFX_PF_MAX || (nl + nfollow + 1) * groups > dfx_env_num_cus() * 3 / 4) {   // all of them or none (every workgroup must be resident; passes of other handles never overlap this one: PassTurn)
-                    nfollow = 0;
-                    for (int l = 0; l < nl; ++l) followed[l] = false;
-                }
+            for (int l = 1; l < nl; ++l) {
+                const bool first = l == 1 || l == lfirst_df;   // a stack's first layer reads a grouped linear of emb, the others the layer below
+                if (!first || follow_emb) followed[l] = true, ++nfollow;
+            }
+            if (nfollow > DFX_PF_MAX || (nl + nfollow + 1) * groups > dfx_env_num_cus() * 3 / 4) {   // all of them or none (every workgroup must be resident; passes of other handles never overlap this one: PassTurn)
+                nfollow = 0;
+                for (int l = 0; l < nl; ++l) followed[l] = false;
             }
             // the recurrences on pairs of CUs (dfx_gru_pair.h): 32 clips per pair, W_hh resident; fp16-split arithmetic only (the exact form's fragments are the same bytes, its matrix ops are not)
             const bool use_pair = m->sw.gru_pair && !m->exact_fp32 && groups >= 2 && m->d_psync;
             if (nfollow || use_pair) m->seq_pbase += (unsigned int)T + 1u;
             auto proj_chunk = [&](const GruW &g, int l, int k, const float *xin, hipStream_t st) -> int {
                 const unsigned int val = base + (unsigned int)k + 1u;
-                if (m->exact_fp32 || !publish) {
-                    const int r = m->exact_fp32 ? launch_proj(xin, m->p(g.wih_t), m->p(g.bias_i), ws + w.pgi[l], Mk(k), 768, st, rmk(k))
-                                                : launch_proj_h3(m, g, xin, ws + w.pgi[l], Mk(k), 768, st, rmk(k));
+                if (m->exact_fp32) {
+                    const int r = launch_proj(xin, m->p(g.wih_t), m->p(g.bias_i), ws + w.pgi[l], Mk(k), 768, st, rmk(k));
                     return r ? r : launch_flag_set(ready + l, val, st);
                 }
                 DfxPublish pub;
@@ -550,14 +534,14 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             hipStream_t G = ln->gs[1], Eq = ln->ts[0], Dq = ln->ts[1], Pq = ln->ps[0];
             const int ev_go = EV_XA;   // the front is complete
             if ((rc = signal(EV_XA, s))) return rc;
-            // Staged enqueue (big passes; off with DFX_ENQUEUE_AHEAD=1 or DFX_PHASE_LATE=0): the host enqueues the phase only once the front
+            // Staged enqueue (big passes; off with DFX_ENQUEUE_AHEAD=1): the host enqueues the phase only once the front
             // has run, so that no barrier packets sit at the head of the phase's ~10 queues while the front's kernels run — measured
             // 18.83 -> 18.20 ms per step (the same effect as between passes, dfx_model::ev_pass).  The persistent launch goes out first
             // and the rest follows chunk-major, faster than the chain consumes it.
-            if (m->phase_late && !m->enqueue_ahead && R >= DFX_THROTTLE_MIN_FRAMES) DFX_HIP(hipEventSynchronize(ln->ev[EV_XA]));
+            if (!m->enqueue_ahead && R >= DFX_THROTTLE_MIN_FRAMES) DFX_HIP(hipEventSynchronize(ln->ev[EV_XA]));
             if ((rc = wait(ev_go, G)) || (rc = wait(ev_go, Eq)) || (rc = wait(ev_go, Dq)) || (rc = wait(ev_go, Pq))) return rc;
             // (the followers' claim counters, dfx_xcd_claim: zeroed in front of the recurrences, whose registrations every follower waits for)
-            if (nfollow && xtab) DFX_HIP(hipMemsetAsync(xstat + 8, 0, (size_t)(DFX_PF_MAX + 1) * 8 * sizeof(unsigned int), G));
+            if (nfollow) DFX_HIP(hipMemsetAsync(xstat + 8, 0, (size_t)(DFX_PF_MAX + 1) * 8 * sizeof(unsigned int), G));
             {   // the recurrences
                 DfxGsArgs S;
                 for (int l = 0; l < DFX_GS_MAX_LAYERS; ++l) S.gi[l] = nullptr, S.y[l] = nullptr, S.whf[l] = nullptr, S.bhn[l] = nullptr, S.unscale[l] = 1.f;
@@ -575,7 +559,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                 S.trace = m->d_trace;
                 S.spin_limit = m->spin_limit;
                 S.pbase = pbase, S.sblk = 16;
-                if (xtab) S.xtab = xtab, S.xstride = DFX_SEQ_GMAX, S.xstat = xstat;
+                S.xtab = xtab, S.xstride = DFX_SEQ_GMAX, S.xstat = xstat;
                 S.xtag = xtag, S.psync = m->d_psync, S.pair_far = m->sw.gru_pair_far ? 1 : 0;
                 for (int l = 1; l < nl; ++l) {
                     if (!followed[l]) continue;
@@ -605,14 +589,12 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                     F.x[f] = first ? (l == 1 ? xb : xa2) : ws + w.py[l - 1], F.gi[f] = ws + w.pgi[l];
                     F.wf[f] = reinterpret_cast<const dfx_h8 *>(m->p(m->exact_fp32 ? g.wih_t : g.wih_h3)), F.bias[f] = m->p(g.bias_i), F.unscale[f] = g.wih_unscale;
                     F.yprog[f] = first ? embprog : yprog + (size_t)(l - 1) * DFX_SEQ_GMAX, F.giprog[f] = giprog + (size_t)l * DFX_SEQ_GMAX;
-                    if (xtab) F.xme[f] = xword(1, l), F.xprod[f] = first ? xword(2, 0) : xword(0, l - 1), F.xcons[f] = xword(0, l);
+                    F.xme[f] = xword(1, l), F.xprod[f] = first ? xword(2, 0) : xword(0, l - 1), F.xcons[f] = xword(0, l);
                     ++f;
                 }
                 for (; f < DFX_PF_MAX; ++f) F.x[f] = nullptr, F.gi[f] = nullptr, F.wf[f] = nullptr, F.bias[f] = nullptr, F.unscale[f] = 1.f, F.yprog[f] = nullptr, F.giprog[f] = nullptr;
                 F.xtag = xtag, F.xstat = xstat;
-                if (xtab) {   // the followers choose their groups by XCD (dfx_xcd_claim): counters zeroed in front of the launches
-                    F.xrec = xword(0, 0), F.xclaim = xstat + 8;
-                }
+                F.xrec = xword(0, 0), F.xclaim = xstat + 8;   // the followers choose their groups by XCD (dfx_xcd_claim): counters zeroed in front of the launches
                 F.B = B, F.T = T, F.nf = nfollow, F.groups = groups, F.pbase = pbase, F.err = m->d_err, F.spin_limit = m->spin_limit;
                 int lq = -1;
                 for (int l = nl - 1; l >= 2 && lq < 0; --l)
@@ -632,11 +614,9 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                 float *dfg_x = run_df ? xa2 : nullptr, *skp = fan_skp ? xdf : nullptr;
                 DfxFanArgs EA = emb_fan_args(m, ws + w.py[0], res, need_emb ? embv : nullptr, xb, dfg_x, skp, lsnr);
                 DfxFollowSync EY;
-                if (xtab) {
-                    EY.x.me = xword(2, 0), EY.x.prod = xword(0, 0), EY.x.cons = xword(1, 1), EY.x.cons2 = followed[lfirst_df] ? xword(1, lfirst_df) : nullptr;
-                    EY.x.tag = xtag, EY.x.stat = xstat;
-                    EY.xclaim = xstat + 8 + 8 * DFX_PF_MAX, EY.groups = groups;
-                }
+                EY.x.me = xword(2, 0), EY.x.prod = xword(0, 0), EY.x.cons = xword(1, 1), EY.x.cons2 = followed[lfirst_df] ? xword(1, lfirst_df) : nullptr;
+                EY.x.tag = xtag, EY.x.stat = xstat;
+                EY.xclaim = xstat + 8 + 8 * DFX_PF_MAX, EY.groups = groups;
                 EY.src = yprog, EY.dst = embprog, EY.pbase = pbase, EY.err = m->d_err, EY.spin_limit = m->spin_limit, EY.B = B, EY.T = T;
                 hipStream_t Eq2 = ln->ps[1];
                 if ((rc = wait(ev_go, Eq2))) return rc;
@@ -654,8 +634,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             // 0.3 ms shorter and the layers then wait as long for the inputs of their next chunks: 13.20-13.23 vs 13.21 ms, not kept)
             // With followers the encoder layer's first projections go out in front of it: on the CUs the followers leave, a kernel that is enqueued
             // behind df_convp waits for it (exact mode: 6.4 ms for the first chunk's projection).
-            const int convp_order = m->sw.convp_after_p0;
-            const bool convp_after_p0 = convp_order >= 0 ? convp_order != 0 : nfollow > 0;
+            const bool convp_after_p0 = nfollow > 0;
             auto convp_late = [&]() -> int {
                 if (!(run_df && convp_split < T)) return DFX_OK;
                 int r;
@@ -694,7 +673,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                 if ((r = launch_wait_ge(m, donep(l - 1), groups, tgt(k), st))) return r;
                 const float *xin = ws + w.py[l - 1];
                 if (j == 0 && fan) {   // emb, lsnr and the inputs of both decoders' GRU stacks in one pass over the encoder GRU's chunk
-                    if (publish && !m->exact_fp32) {
+                    if (!m->exact_fp32) {
                         DfxPublish pub;
                         pub.cnt = pcnt + 8, pub.flag = embf, pub.value = tgt(k);
                         if ((r = emb_fan(ws + w.py[0], xb, Mk(k), st, rmk(k), &pub))) return r;
@@ -711,7 +690,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                 return DFX_OK;
             };
             // ---- ERB tail, chunk k
-            // (tails consume: they may take several hand-over chunks [k0, k1] in one launch — DFX_SEQ_TAIL_EVERY — when the chain is cut finer
+            // (tails consume: they may take several hand-over chunks [k0, k1] in one launch — DFX_SEQ_TAIL_EVERY in dev builds — when the chain is cut finer
             // than a decoder tail's launch is worth)
             auto erb_tail = [&](int k0, int k) -> int {
                 const int64_t Rk = B * (tb(k + 1) - tb(k0));
@@ -794,7 +773,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                     if ((rc = erb_tail(k0, k))) return rc;
                 }
                 // the DF tail waits for ALL of df_convp, which — deferred under the phase, beside followers — ends with the phase: its launches then run
-                // behind the chain anyway, and few large ones are through sooner than twelve small ones (DFX_SEQ_DFTAIL_EVERY=n chunks per launch)
+                // behind the chain anyway, and few large ones are through sooner than twelve small ones (dev builds: DFX_SEQ_DFTAIL_EVERY=n chunks per launch)
                 const int dft_env = m->sw.dftail_every;
                 // (12.47-12.52 ms per step at 4 chunks per launch against 12.69-12.83 at 1, same box; 6: 12.49-12.57)
                 const int dft_every = dft_env > 0 ? dft_env : (nfollow > 0 && convp_split < T && tail_every < 4 ? 4 : tail_every);
@@ -976,9 +955,9 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
                                    sc->channels > 0 ? sc->channels : 1);
     }
     // enhance(): the deep filter + gains are applied on the way into the inverse transform (dfx_k_synthesis_rows): spec_e never exists.
-    // DFX_FUSE_DFA=0: dfx_k_df_apply_rows -> spec_e -> dfx_k_synthesis (the stand-alone deep-filter kernel stays the API of
-    // dfx_model_forward / dfx_df_apply and the roofline kernel of bench.py)
-    if (fin && m->fuse_dfa && dfx_synthesis_rows_ok(fin->st, true, O, run_df ? Fd : 0, E) && bands == fin->st->bands && sstride % 2 == 0 && sstride > 0) {
+    // Where the transform cannot take them (dfx_synthesis_rows_ok) and without a transform: dfx_k_df_apply_rows -> spec_e -> dfx_k_synthesis (the
+    // stand-alone deep-filter kernel stays the API of dfx_model_forward / dfx_df_apply and the roofline kernel of bench.py)
+    if (fin && dfx_synthesis_rows_ok(fin->st, true, O, run_df ? Fd : 0, E) && bands == fin->st->bands && sstride % 2 == 0 && sstride > 0) {
         if ((rc = dfx_launch_synthesis_rows(fin->st, spec, sstride, run_df ? coefs : nullptr, run_df ? Fd : 0, O, c.df_lookahead, mask,
                                             c.mask_pf ? c.pf_beta : 0.f, atten_lim, B, T, fin->y, fin->out_stride, fin->out_skip, fin->out_len, fin_s, fin->out_i16, m->d_err, m->d_sync ? m->d_sync + 14 : nullptr)))   // (d_sync[14]: a spare word of the flag block)
             return rc;
@@ -1051,7 +1030,6 @@ struct DfxTurn {
     hipStream_t s;
     bool big, recorded = false;
     DfxTurn(const dfx_model *m_, hipStream_t s_, bool big_pass) : m(m_), s(s_), big(big_pass && m_->concurrent && m_->ev_gate) {
-        if (!m->have_streams) return;
         lk = std::unique_lock<std::mutex>(dfx_enqueue_mu());
         PassGate &g = pass_gate();
         if (big && g.owner && g.owner != m && g.done) (void)hipStreamWaitEvent(s, g.done, 0);

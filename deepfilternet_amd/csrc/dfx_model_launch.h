@@ -118,6 +118,13 @@ static int launch_convp2(const dfx_model *m, const float *c0, const float *feat_
     return DFX_OK;
 }
 
+// df_convp runs as DFX_CONVP_GRAIN times as many, shorter workgroups as fill the chip once.  It owns whole SIMDs (one wave of 512 registers
+// each) and is needed last (by df_out, deep in the GRU phase): as a persistent grid of long workgroups it held every SIMD for 4.7 ms while
+// the kernels on the front's critical path (ERB encoder convs -> embedding GEMMs) waited for slots (erb_conv2: 1.8 ms instead of 0.3).  In
+// 16 x shorter workgroups (40-frame segments, 10 % warm-up overhead) its slots come free every ~35 us and the dispatcher lets the other
+// queues in: the front ends 1.1 ms earlier, df_convp finishes under the first 2 ms of the GRU phase; 17.7 -> 17.15 ms per step (8 ... 32:
+// the same; a finer grain for df_conv0->1 as well: no effect, rejected).
+constexpr int DFX_CONVP_GRAIN = 16;
 template <int C, int KT>
 static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *out, int64_t B, int64_t T, int Fd, int NO,
                            hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0) {
@@ -160,7 +167,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
         A.unscale = m->cp_unscale;
         A.err = m->d_err;
         A.nfb = (Fd + 15) / 16;
-        const int64_t want = (int64_t)dfx_env_num_cus() * 4 * 4 * m->front_grain_p;  // two resident waves per SIMD, two rounds
+        const int64_t want = (int64_t)dfx_env_num_cus() * 4 * 4 * DFX_CONVP_GRAIN;  // two resident waves per SIMD, two rounds
         int64_t nseg = dfx_ceil_div(want, B * A.nfb);
         const int64_t Tn = t_end - t_begin;  // frames produced
         const int64_t max_seg = dfx_ceil_div(Tn, (int64_t)8 * KT);
@@ -173,7 +180,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
         // (capping the launch at 64 ... 192 resident workgroups, so that the rest of the chip is free for the front's critical path, measured
         // +0.1 ... +0.5 ms per step: profiles/r04_exact_and_convp_cap.log)
         DfxKScope ks(DFX_K_DF_CONVP, s);
-        dfx_launch((dfx_k_df_convp_h3<C, KT>), dim3(nn_grid(dfx_ceil_div(nruns, 4), 2 * m->front_grain_p)), dim3(256), 0, s, A);
+        dfx_launch((dfx_k_df_convp_h3<C, KT>), dim3(nn_grid(dfx_ceil_div(nruns, 4), 2 * DFX_CONVP_GRAIN)), dim3(256), 0, s, A);
         DFX_LAUNCH_CHECK();
         return DFX_OK;
     }
@@ -240,7 +247,7 @@ static int launch_conv01_h3(const dfx_model *m, const PwW &w, const float *feat_
         A.unscale0 = m->c0_unscale;
         A.unscale = m->dfc1_unscale;
         A.err = m->d_err;
-        const int grid = nn_grid(dfx_ceil_div(B * (t_end - t_begin) * Fout, 64), 3 * m->front_grain);   // three resident workgroups per CU
+        const int grid = nn_grid(dfx_ceil_div(B * (t_end - t_begin) * Fout, 64), 3);   // three resident workgroups per CU
         DfxKScope ks(DFX_K_PWCONV, s);
         dfx_launch(dfx_k_df_conv01_h3<C>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
         DFX_LAUNCH_CHECK();
@@ -303,7 +310,7 @@ static int launch_erb_dec10(const dfx_model *m, const float *d2, const float *e1
 template <int C>
 static bool erb_tail_ok(const dfx_model *m, int E) {
     if constexpr (C % 32 != 0) return false;
-    return m->fuse_tail && m->fuse_erb && !m->exact_fp32 && m->ct3.wt_h3 && m->ct2.wt_h3 && m->ct1.wt_h3 && m->tail_w0h3 && m->tail_woh3 && dfx_tail_ok(C, E);
+    return !m->exact_fp32 && m->ct3.wt_h3 && m->ct2.wt_h3 && m->ct1.wt_h3 && m->tail_w0h3 && m->tail_woh3 && dfx_tail_ok(C, E);
 }
 template <int C>
 // e0 == null: recomputed in the kernel from feat_erb (rows of T frames per clip, feat_T frames per clip in feat_erb, lookahead L)
@@ -502,16 +509,9 @@ static int launch_proj_h3(const dfx_model *m, const GruW &g, const float *a, flo
     DfxKScope ks(DFX_K_PROJ, s);
     // two row tiles per wave (256-row workgroups: half the fragment reads per row, 0.36 vs 0.40 ms for 256 k rows) unless the launch is a
     // single round of workgroups anyway — then the one-tile kernel's shorter workgroup latency wins (49 vs 79 us: the frame-by-frame
-    // streaming runtime, 4096 rows per call).  DFX_PROJ_RT=1 / 2 / 3 forces one form.
-    const int row_tiles = m->proj_rt;
-    if (row_tiles == 3) {   // two workgroups of 4 waves per CU on 32-column chunks (measured 0.375 vs 0.363 ms: not the default)
-        DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_proj256_h3x2<4, 2>, DFX_PH_SMEM / 2));
-        if (pub) A.pub = *pub, A.pub.nblocks = (unsigned)dfx_ceil_div(M, 128);
-        dfx_launch((dfx_k_proj256_h3x2<4, 2>), dim3((unsigned)dfx_ceil_div(M, 128)), dim3(256), DFX_PH_SMEM / 2, s, A);
-        DFX_LAUNCH_CHECK();
-        return DFX_OK;
-    }
-    if (row_tiles == 2 || (row_tiles == 0 && M > 8192)) {
+    // streaming runtime, 4096 rows per call).  (Rejected: two workgroups of 4 waves per CU on 32-column chunks, dfx_k_proj256_h3x2<4, 2>:
+    // 0.375 vs 0.363 ms; tools/dev/proj_h3_bench.hip still times it.)
+    if (M > 8192) {
         DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_proj256_h3x2<8, 4>, DFX_PH_SMEM));
         if (pub) A.pub = *pub, A.pub.nblocks = (unsigned)dfx_ceil_div(M, 256);
         dfx_launch((dfx_k_proj256_h3x2<8, 4>), dim3((unsigned)dfx_ceil_div(M, 256)), dim3(512), DFX_PH_SMEM, s, A);
@@ -539,13 +539,10 @@ static int launch_glin(const dfx_model *m, const GlinW &g, const float *a, int a
     return launch_ggemm(a, g.G * g.Kg, m->p(g.w), g.G, g.Kg, g.Ng, nullptr, act, res, out, g.G * g.Ng, M, s, 0, 0, 1, rm, a2);
 }
 
-// DFX_SEQ_FOLLOW (persistent GRU phase): 0 = every input projection a launch per time chunk; 1 = follower workgroups for the stacks' second layers;
-// 2 (default since the same-XCD hand-over, M§R5.12) = followers for every decoder layer + the emb fan-out; 3 = the first layers + emb only.
-static int seq_follow_mode(const dfx_model *m) { return m->sw.follow; }
 // Row count up to which the fan-out kernels take their few-rows forms (one row tile per wave, a tile's chunks dealt to separate waves): made
 // for a streaming hop (4096 rows).  Round 5: the time chunks of the persistent GRU phase (10-20 k rows at 16-24 chunks) take the large-launch
 // forms — at the old bound of 16384 rows every chunking finer than 15 chunks fell onto the hop's forms (15.1 vs 14.1 ms per step).
-static int64_t fan_few_rows(const dfx_model *m) { return m->sw.fan_few_rows; }
+constexpr int64_t DFX_FEW_ROWS_MAX = 4096;
 // df_fc_emb (+ e3) and the encoder GRU's linear_in in one pass over c1 (dfx_k_enc_fan)
 static int launch_enc_fan(const dfx_model *m, const float *c1, const float *e3, float *emb_out, float *xa, int64_t M, hipStream_t s, DfxRowMap rm) {
     DfxEncFanArgs A;
@@ -559,7 +556,7 @@ static int launch_enc_fan(const dfx_model *m, const float *c1, const float *e3, 
     A.ng = m->efan_groups;
     A.rm = rm;
     DfxKScope ks(DFX_K_GGEMM, s);
-    if (M > fan_few_rows(m)) {
+    if (M > DFX_FEW_ROWS_MAX) {
         constexpr int RT = 2;
         A.parts = 1;
         dfx_launch(dfx_k_enc_fan<RT>, dim3((unsigned)nn_grid(dfx_ceil_div(dfx_ceil_div(M, 16 * RT), 4), 8)), dim3(256), 0, s, A);
@@ -634,7 +631,7 @@ static int launch_emb_fan(const dfx_model *m, const float *y, const float *res, 
     A.rm = rm;
     // few rows (a streaming hop): one wave per (16 rows, super-chunk) instead of a wave walking all super-chunks — emb is then written out
     // (embv: 2 KB per row of a few thousand rows) and lsnr, the one consumer that needs all of a row's features, is a launch of its own
-    const bool split = M <= fan_few_rows(m) && lsnr && embv_for_split;
+    const bool split = M <= DFX_FEW_ROWS_MAX && lsnr && embv_for_split;
     if (split) {
         A.parts = A.nj;
         A.emb_out = embv_for_split;
@@ -643,7 +640,7 @@ static int launch_emb_fan(const dfx_model *m, const float *y, const float *res, 
     {
     DfxKScope ks(DFX_K_EMB_FAN, s);
     // (the kinds are what pack_fan accepted: dec_in narrow, dfg_in wide, df_skip narrow; a consumer that is not wanted drops out)
-    if (M > fan_few_rows(m)) {
+    if (M > DFX_FEW_ROWS_MAX) {
         constexpr int RT = 2;
         const dim3 grid((unsigned)nn_grid(dfx_ceil_div(dfx_ceil_div(M, 16 * RT), 4), 8));
         if (pub) A.pub = *pub, A.pub.nblocks = grid.x;

@@ -100,7 +100,7 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: the DF state does not match the model (fft/hop/nb_erb)");
     if (c.conv_lookahead != c.df_lookahead)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: conv_lookahead != df_lookahead is not supported by the streaming path");
-    if (!m->fuse_c0 || !m->fuse_erb || m->exact_fp32 || !m->run_df)
+    if (!m->fuse_c0 || m->exact_fp32 || !m->run_df)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the default (fused, fp16-split, DF stage on) engine configuration");
     if (int rc = dfx_require_device()) return rc;
     dfx_stream_state *s = new dfx_stream_state();
@@ -448,10 +448,9 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
     unsigned char *gflags = gated ? S->gate_buf + S->g_flags : nullptr;
     int *gcount = gated ? reinterpret_cast<int *>(S->gate_buf + S->g_counter) : nullptr;
     // one new hop, plain launches: every GRU layer is ONE launch (projection + recurrence + gates) that leaves the new states in the
-    // other buffer (DFX_STREAM_STEP=0: the projection and the recurrence kernel of the batch path, in place)
-    constexpr bool step_env = true;
+    // other buffer (several new hops: the projection and the recurrence kernel of the batch path, in place)
     const int64_t skip_early = S->frames < L ? ((L - S->frames) < n ? (L - S->frames) : n) : 0;
-    const bool step_all = step_env && n - skip_early == 1;
+    const bool step_all = n - skip_early == 1;
     if (gated) {
         // silent-input shortcut (tract.rs:513-525) + a copy of the in-place state, so that the streams that turn out not to advance
         // (frozen, or a decoder stage skipped) can be given their state back after the pass

@@ -1421,7 +1421,7 @@ static __host__ __device__ __forceinline__ bool dfx_pwf_ok(int C, int Fin, int F
 }
 
 template <int C, int MODE, bool SKIP, int NVI /* input float4s per lane and item: 4 or DFX_PWF_MAXV */, bool H3 = false>
-__global__ void __launch_bounds__(DFX_PW_THREADS, (SKIP && NVI == DFX_PWF_MAXV) ? 1 : 2) dfx_k_pwconv_f(DfxPwArgs A) {   // (pathway + 8 loads in flight: 44 registers over the budget of two waves per SIMD; only the unfused decoder tail, DFX_FUSE_TAIL=0, runs that form)
+__global__ void __launch_bounds__(DFX_PW_THREADS, (SKIP && NVI == DFX_PWF_MAXV) ? 1 : 2) dfx_k_pwconv_f(DfxPwArgs A) {   // (pathway + 8 loads in flight: 44 registers over the budget of two waves per SIMD; only the unfused decoder tail, where erb_tail_ok() does not hold, runs that form)
     constexpr int NT = C / 16, CPL = C / 4, LD = C + 4, C4 = C / 4, KC = H3 ? C / 32 : 1;
     DFX_DYN_SMEM(float4, dfx_pwf_smem4);
     float4 *dws = dfx_pwf_smem4, *sks = dfx_pwf_smem4 + 3 * C4;
@@ -2236,7 +2236,7 @@ __global__ void __launch_bounds__(64 * DFX_TAIL_WAVES, 1) dfx_k_erb_tail(DfxTail
                     const int idx = lane + 64 * i;
                     if (idx < N0T) {
                         const int row = idx / C4, c4 = idx - row * C4;
-                        // (e0 from HBM — DFX_E0_RECOMPUTE=0 or an encoder that is not fused — is read where it is used: requested a stage
+                        // (e0 from HBM — an encoder that is not fused — is read where it is used: requested a stage
                         // ahead, its 16 registers were 48 bytes of scratch per lane at this kernel's three waves per SIMD)
                         *reinterpret_cast<float4 *>(X + row * LD + 4 * c4) = path(p0[(r * 2 + t) * N0T + idx], a0, b0);
                     }
@@ -4048,7 +4048,7 @@ __global__ void __launch_bounds__(DFX_GRU_THREADS, 2) dfx_k_gru_rec(const float 
 // ---------------------------------------------------------------------------------------------------------------------
 #define DFX_GH_ROWS 16
 #define DFX_GS_MAX_LAYERS 8   /* layers one persistent dfx_k_gru_seq launch can carry */
-#define DFX_GS_MAX_CHUNKS 96  /* time chunks of the persistent GRU phase (the default is 12; without followers 16: finer cuts lose to the hand-overs, profiles/r05_gru_chain.log) */
+#define DFX_GS_MAX_CHUNKS 96  /* time chunks of the persistent GRU phase (the default is 12: finer cuts lose to the hand-overs, profiles/r05_gru_chain.log) */
 #ifndef DFX_GH_ABLATE
 #define DFX_GH_ABLATE 0  /* dev ablations (tools/dev/gru_h3_bench.hip): 1 no stream refill, 2 no gi loads, 4 no matrix ops, 8 no gate math, 16 no y stores */
 #endif
@@ -4528,7 +4528,7 @@ __global__ void __launch_bounds__(DFX_GH_THREADS, DFX_GH_NW / 4) dfx_k_gru_seq_x
 
 // ---------------------------------------------------------------------------------------------------------------------
 // dfx_k_proj_follow: the input projection of a decoder GRU layer as persistent FOLLOWER workgroups of the recurrences instead of one launch
-// per time chunk (round 5; the default, DFX_SEQ_FOLLOW).  The layer's input is the output of the layer below (the stacks' second layers) or what the
+// per time chunk (round 5; the default).  The layer's input is the output of the layer below (the stacks' second layers) or what the
 // emb follower wrote behind the encoder GRU (their first layers: dfx_k_emb_follow).  Workgroup (f, g) serves 16 clips of layer f — the group whose
 // recurrence runs on ITS XCD (dfx_xcd_claim), with L2-local hand-overs (DfxXcd) — : it waits until its producer has completed the next block of 16
 // steps of those clips (a step counter: yprog / embprog), runs dfx_k_proj256_h3x2<8, 4>'s arithmetic on the block's 256 rows (wave w, tile t: step 2 w + t of the

@@ -1,5 +1,5 @@
 """Dev: the bits of enhance() under the engine switches of the environment — one digest per call.
-    DFX_SEQ_FOLLOW=0 python tools/dev/follow_check.py [calls [clips [samples]]]     (compare the digests with those of a run without the switch;
+    DFX_GRU_PAIR=0 python tools/dev/follow_check.py [calls [clips [samples]]]     (compare the digests with those of a run without the switch;
     default: the bench size, 256 clips x 480000 samples)"""
 import hashlib
 import os

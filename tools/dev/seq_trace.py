@@ -31,17 +31,10 @@ nl, ng, K = dims[0], dims[1], dims[2]
 t = buf[: nl * ng * K * 3].reshape(nl, ng, K, 3).astype(np.float64) / 100.0   # microseconds
 t0 = t[..., 0].min()
 t -= t0
-def bounds(T=1002, K0=int(os.environ.get("DFX_SEQ_CHUNKS", "16" if os.environ.get("DFX_SEQ_FOLLOW", "2") == "0" else "12")), ramp0=int(os.environ.get("DFX_SEQ_RAMP", "0"))):
-    body, sizes, down, left = max(-(-T // K0), 32), [], [], T
-    r = ramp0
-    while ramp0 > 0 and r < body and left > 4 * body:
-        sizes.append(r); left -= r; r *= 2
-    r = ramp0
-    while ramp0 > 0 and r < body and left > 3 * body:
-        down.append(r); left -= r; r *= 2
-    nbody = max(1, min(-(-left // body), 96 - len(sizes) - len(down)))
-    sizes += [left * (i + 1) // nbody - left * i // nbody for i in range(nbody)]
-    return np.array(sizes + down[::-1], dtype=np.float64)
+def bounds(T=1002, K0=int(os.environ.get("DFX_SEQ_CHUNKS", "12"))):   # forward_impl's uniform chunks (DFX_SEQ_CHUNKS: dev builds)
+    body = max(-(-T // K0), 32)
+    n = max(1, min(-(-T // body), 96))
+    return np.array([T * (i + 1) // n - T * i // n for i in range(n)], dtype=np.float64)
 
 
 steps = bounds()

@@ -1,12 +1,12 @@
 """Dev: which buffer of a pass goes wrong first when two model handles run their passes at the same time (round-5 review, item 1).
 
-Two handles (same weights), one host thread each, every round started together from a barrier.  (Written against the round-5 library, where
-DFX_PASS_TURN=0 switched the pass gate off; since the handles share the process's streams the enqueue lock cannot be switched off any more — the
+Two handles (same weights), one host thread each, every round started together from a barrier.  (Written against the round-5 library, whose
+pass gate could be switched off; since the handles share the process's streams the enqueue lock cannot be switched off any more — the
 tool still shows which buffer differs first should a pass ever come back wrong.)
 After a round whose output differs from the solo run, every buffer of the failing handle's workspace is compared with the snapshot of its
 solo run: name, differing elements, clips, frames.  The earliest buffer in the dependency order that differs names the kernel.
 
-  python tools/dev/two_handles_diag.py [--B 256] [--T 96000] [--rounds 8] [--streams shared|own] [--env2 K=V ...] [--keep-gate]
+  python tools/dev/two_handles_diag.py [--B 256] [--T 96000] [--rounds 8] [--streams shared|own] [--env2 K=V ...]
 """
 import argparse
 import os
@@ -19,12 +19,9 @@ ap.add_argument("--T", type=int, default=96000)
 ap.add_argument("--rounds", type=int, default=8)
 ap.add_argument("--streams", default="shared")
 ap.add_argument("--env2", nargs="*", default=[])
-ap.add_argument("--keep-gate", action="store_true")
 ap.add_argument("--max-dumps", type=int, default=2)
 ap.add_argument("--stagger-us", type=int, default=0)
 args = ap.parse_args()
-if not args.keep_gate:
-    os.environ["DFX_PASS_TURN"] = "0"
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 import numpy as np  # noqa: E402
@@ -216,4 +213,4 @@ for rnd in range(args.rounds):
             cols = (d.amax(dim=0) > 0).nonzero().flatten()
             print(f"  handle {i}: max diff {float(d.max()):.3e}, clips {bad[:16]} ({len(bad)}), samples {int(cols.min())}..{int(cols.max())} ({len(cols)})")
             diff_ws(models[i][0]._ws, refs[i][1], models[i][0]._ws.data_ptr(), refs[1 - i][1])
-print(f"SUMMARY streams={args.streams} env2={args.env2} gate={'on' if args.keep_gate else 'off'}: {bad_rounds} of {args.rounds} rounds wrong")
+print(f"SUMMARY streams={args.streams} env2={args.env2}: {bad_rounds} of {args.rounds} rounds wrong")
