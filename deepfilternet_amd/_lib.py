@@ -108,6 +108,8 @@ SIGNATURES = {
     "dfx_stream_create": (_i, [_vp, _vp, _i64, _i, C.POINTER(_vp)]),
     "dfx_stream_free": (None, [_vp]),
     "dfx_stream_reset": (_i, [_vp, _vp]),
+    "dfx_stream_reset_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp]),
+    "dfx_stream_frames": (_i, [_vp, C.POINTER(_i64)]),
     "dfx_stream_frame_length": (_i, [_vp]),
     "dfx_stream_delay_frames": (_i, [_vp]),
     "dfx_stream_set_atten_lim": (_i, [_vp, _f]),

@@ -135,6 +135,7 @@ struct DfxFinish {
 struct DfxStreamCtx {
     int64_t H;         // history frames in front of the new ones
     int64_t t_zero;    // local frames < t_zero precede the start of the stream (df_convp sees zero padding there)
+    const int *t_zero_rows = nullptr;   // non-null: t_zero per stream [B] (some streams started over later than the handle: dfx_stream_reset_streams)
     int64_t spec_T;    // frames per clip of the spec array
     int64_t spec_stride = 0;   // > 0: bins per row of spec and out (padded rows)
     int64_t feat_T = 0;    // > 0: frames per clip of feat_erb and feat_spec (windows inside the linear buffers; both share it)

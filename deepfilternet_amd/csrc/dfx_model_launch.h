@@ -80,9 +80,10 @@ static int launch_pw(int mode, const dfx_model *m, const PwW &w, const float *x,
 
 template <int C, int KT>
 static int launch_convp2(const dfx_model *m, const float *c0, const float *feat_spec, float *out, int64_t B, int64_t T, int Fd,
-                         int NO, hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1) {
+                         int NO, hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1, const int *t_zero_rows = nullptr) {
     if (t_end < 0) t_end = T;
     DfxCp2Args A;
+    A.t_zero_rows = t_zero_rows;
     A.t_end = t_end;
     A.c0 = c0;
     A.feat = feat_spec;  // non-null: df_conv0 is recomputed on the fly, c0 is not read
@@ -127,7 +128,8 @@ static int launch_convp2(const dfx_model *m, const float *c0, const float *feat_
 constexpr int DFX_CONVP_GRAIN = 16;
 template <int C, int KT>
 static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *out, int64_t B, int64_t T, int Fd, int NO,
-                           hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0) {
+                           hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0,
+                           const int *t_zero_rows = nullptr) {
     if constexpr (C % 32 != 0) {
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "fp16-split df_convp needs conv_ch %% 32 == 0");
     } else {
@@ -141,7 +143,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
                 for (int64_t b0 = 0; b0 < B; b0 += bmax) {
                     const int64_t nb = B - b0 < bmax ? B - b0 : bmax;
                     if (int r = launch_convp_h3<C, KT>(m, feat_spec + b0 * per_clip * 2, out + b0 * (int64_t)(NO / 2) * T * Fd * 2, nb, T, Fd, NO, s, t_begin, t_zero, L,
-                                                       t_end, feat_T))
+                                                       t_end, feat_T, t_zero_rows ? t_zero_rows + b0 : nullptr))
                         return r;
                 }
                 return DFX_OK;
@@ -163,6 +165,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
         A.L = L < 0 ? m->cfg.conv_lookahead : L;
         A.t_begin = t_begin;
         A.t_zero = t_zero;
+        A.t_zero_rows = t_zero_rows;
         A.unscale0 = m->c0_unscale;
         A.unscale = m->cp_unscale;
         A.err = m->d_err;
@@ -190,7 +193,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
 template <int C, int KT>
 static int launch_convp_step(const dfx_model *m, const float *feat_spec, float *out, int64_t B, int64_t T, int Fd, int NO, hipStream_t s,
                              int64_t t_zero, int L, void *ring, int slot, bool rebuild, int64_t feat_T = 0, const unsigned char *par = nullptr,
-                             const int *cnt = nullptr) {
+                             const int *cnt = nullptr, const int *t_zero_rows = nullptr) {
     if constexpr (C % 32 != 0 || KT < 2) {
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "df_convp step kernel: conv_ch %% 32 == 0 and kt >= 2");
     } else {
@@ -205,7 +208,7 @@ static int launch_convp_step(const dfx_model *m, const float *feat_spec, float *
         A.out = out;
         A.B = B, A.T = T, A.Fd = Fd, A.NO = NO;
         A.L = L;
-        A.t_begin = T - 1, A.t_zero = t_zero;
+        A.t_begin = T - 1, A.t_zero = t_zero, A.t_zero_rows = t_zero_rows;
         A.unscale0 = m->c0_unscale, A.unscale = m->cp_unscale;
         A.err = m->d_err;
         A.nfb = (Fd + 15) / 16;

@@ -36,6 +36,85 @@ __global__ void dfx_k_fill_rows(float *dst, int64_t dst_stride, int64_t len, int
     }
 }
 
+// ---- streams of one handle that start over on their own (dfx_stream_reset_streams) -----------------------------------------------------
+// DfxRowClear lists, per state array of the handle, the part of a row that a stream's start zeroes: entry e covers bytes[e] bytes at
+// p[e] + rep * rep_stride[e] + row * stride[e], rep < reps[e] (the GRU layers).  The same table form serves the reset itself (rows = the
+// caller's ids) and the warm-up of a reset stream (rows = the streams that are younger than the lookahead: dfx_k_stream_warm).
+#define DFX_ROWS_MAX_ENTRIES 32
+#define DFX_RESET_IDS 512   /* stream indices per launch of the reset kernel (they travel as kernel arguments: no upload, no wait) */
+struct DfxRowClear {
+    unsigned char *p[DFX_ROWS_MAX_ENTRIES];
+    int64_t stride[DFX_ROWS_MAX_ENTRIES], bytes[DFX_ROWS_MAX_ENTRIES], rep_stride[DFX_ROWS_MAX_ENTRIES];
+    int reps[DFX_ROWS_MAX_ENTRIES];
+    int n;
+    // host: appends an entry; false when the table is full (the callers report that: the table travels by value as a kernel argument)
+    bool add(void *ptr, int64_t stride_, int64_t bytes_, int reps_ = 1, int64_t rep_stride_ = 0) {
+        if (bytes_ <= 0) return true;
+        if (n >= DFX_ROWS_MAX_ENTRIES) return false;
+        p[n] = static_cast<unsigned char *>(ptr), stride[n] = stride_, bytes[n] = bytes_, reps[n] = reps_, rep_stride[n] = rep_stride_;
+        ++n;
+        return true;
+    }
+};
+struct DfxRowIds {
+    int n;
+    int id[DFX_RESET_IDS];
+};
+// part / parts: the workgroups that share one row
+static __device__ __forceinline__ void dfx_clear_row(const DfxRowClear &R, int64_t row, int part, int parts) {
+    const int64_t i0 = (int64_t)part * blockDim.x + threadIdx.x, step = (int64_t)parts * blockDim.x;
+    for (int e = 0; e < R.n; ++e)
+        for (int r = 0; r < R.reps[e]; ++r) {
+            unsigned char *p = R.p[e] + r * R.rep_stride[e] + row * R.stride[e];
+            const int64_t nb = R.bytes[e];
+            if ((((uintptr_t)p | (uintptr_t)nb) & 15) == 0) {
+                float4 *q = reinterpret_cast<float4 *>(p);
+                for (int64_t i = i0; i < (nb >> 4); i += step) q[i] = make_float4(0.f, 0.f, 0.f, 0.f);
+            } else if ((((uintptr_t)p | (uintptr_t)nb) & 3) == 0) {
+                float *q = reinterpret_cast<float *>(p);
+                for (int64_t i = i0; i < (nb >> 2); i += step) q[i] = 0.f;
+            } else {
+                for (int64_t i = i0; i < nb; i += step) p[i] = 0;
+            }
+        }
+}
+
+// Workgroups (k * ch + c, part): channel c of stream I.id[k] starts over — its rows of every state array are zeroed, its running means take
+// the initial values of a fresh erb_norm / unit_norm (the expressions of dfx_stream_reset, evaluated with the same roundings) and
+// birth[row] = the handle's hop count.  Duplicate ids write the same values twice.
+__global__ void __launch_bounds__(256) dfx_k_stream_reset_rows(DfxRowClear R, DfxRowIds I, int ch, float *erb_state, int E, float erb_step,
+                                                               float *unit_state, int Fd, float unit_step, int64_t *birth, int64_t now) {
+    const int k = (int)blockIdx.x / ch;
+    if (k >= I.n) return;
+    const int64_t row = (int64_t)I.id[k] * ch + (int)blockIdx.x % ch;
+    dfx_clear_row(R, row, (int)blockIdx.y, (int)gridDim.y);
+    if (blockIdx.y != 0) return;
+    for (int i = threadIdx.x; i < E; i += blockDim.x) erb_state[row * E + i] = __fadd_rn(-60.f, __fmul_rn(erb_step, (float)i));
+    for (int i = threadIdx.x; i < Fd; i += blockDim.x) unit_state[row * Fd + i] = __fadd_rn(0.001f, __fmul_rn(unit_step, (float)i));
+    if (threadIdx.x == 0) birth[row] = now;
+}
+
+// Per-stream start of the network time inside this pass's window: tz[b] = local index of stream b's net position 0 (DfxStreamCtx::t_zero
+// with the stream's own age now - birth[b] in place of the handle's hop count), 0 once the stream is older than the window.
+__global__ void dfx_k_stream_tzero(const int64_t *birth, int64_t now, int64_t Hs, int *tz, int64_t B) {
+    const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (b >= B) return;
+    const int64_t age = now - birth[b];
+    tz[b] = age < Hs ? (int)(Hs - age) : 0;
+}
+
+// Warm-up of a stream that started over while the others run on (one new hop per pass): the hop has no net position yet (tz[b] > H: the new
+// frame, local index H, lies before the stream's position 0), so — like the first `lookahead` hops of a fresh handle — its features enter
+// the windows as zeros, its network state (GRU rows, df_convp's sums / delay line) and its enhanced spectrum are zero again after the
+// pass; STFT memory, running means and rolling spectra have advanced.  Gated handles: no stage decision was taken for the stream — its
+// flags are cleared and its silent-input counter is lowered by the one dfx_k_gate_finish then adds for "gains absent".
+__global__ void __launch_bounds__(256) dfx_k_stream_warm(DfxRowClear R, const int *tz, int H, int *gate_counter, int64_t B) {
+    const int64_t b = blockIdx.x;
+    if (b >= B || tz[b] <= H) return;
+    dfx_clear_row(R, b, (int)blockIdx.y, (int)gridDim.y);
+    if (gate_counter && blockIdx.y == 0 && threadIdx.x == 0) gate_counter[b] -= 1;
+}
+
 // ------------------------------------------------------------------------------------------------ streaming (dfx_stream_*)
 // Frame loop of DfTract::process (tract.rs:509-642) for many lockstep streams: every call runs the batch kernels on a window of
 // H history + n new frames per stream (DfxStreamCtx), with all recurrent state carried in the handle.
@@ -44,7 +123,15 @@ struct dfx_stream_state {
     const dfx_state *st = nullptr;
     int64_t B = 0;
     int nmax = 0, H = 0, L = 0, layers = 0;
-    int64_t frames = 0;       // hops consumed since the last reset
+    int64_t frames = 0;       // hops consumed since the last reset of the whole handle: the lockstep network time of all streams
+    // The start-of-stream position is per stream: birth[row] = `frames` when the row last started over (dfx_stream_reset_streams; 0 after
+    // a reset of the whole handle), on the host and — for the kernels — on the device.  While frames < mixed_until some stream is younger
+    // than the window (H + L hops) and younger than the handle: passes then compute the per-row t_zero (dfx_k_stream_tzero); while
+    // frames < warm_until some such stream is younger than the lookahead: passes carry one hop and end with dfx_k_stream_warm.  Past both, a
+    // pass enqueues exactly what a handle without individual resets enqueues.
+    std::vector<int64_t> birth;
+    int64_t mixed_until = 0, warm_until = 0;
+    size_t birth_dev = 0, tz_rows = 0;   // byte offsets into buf: int64 [B], int [B]
     float lim = 0.f;          // linear attenuation limit: 0 = off, 1 = bypass (tract.rs:387-398)
     float pf_beta = -1.f;     // < 0: the model's setting
     unsigned char *buf = nullptr;
@@ -139,7 +226,8 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     s->work_spec = take((size_t)B * (Hs + n) * F * 8);
     s->out_spec = take((size_t)B * n * F * 8);
     {   // linear rolling-spectra buffer: slack of at least one window (so that the move back to the front never overlaps), at most ~1 GB
-        static const int lin_env = [] { const char *e = getenv("DFX_STREAM_LINEAR"); return e ? atoi(e) : 1; }();   // test hook: 0 = ring form, n > 1 = slack of n frames (the wrap of the linear buffers every few hops)
+        const char *lin_e = getenv("DFX_STREAM_LINEAR");   // test hook, read at every create: 0 = ring form, n > 1 = slack of n frames (the wrap of the linear buffers every few hops)
+        const int lin_env = lin_e ? atoi(lin_e) : 1;
         int64_t slack = lin_env > 1 ? lin_env : 32;   // (DFX_STREAM_LINEAR=0: ring form only; = n > 1: slack of n frames, tests)
         while (slack > Hs + n && (size_t)B * (Hs + n + slack) * F * 8 > ((size_t)1 << 30)) slack /= 2;
         if (slack < Hs + n) slack = Hs + n;
@@ -166,6 +254,9 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         }
     }
     s->lsnr = take((size_t)B * (H + n) * 4);
+    s->birth_dev = take((size_t)B * 8);
+    s->tz_rows = take((size_t)B * 4);
+    s->birth.assign((size_t)B, 0);
     dfx_model_workspace_bytes(m, B, H + n, &s->model_ws_bytes);
     s->model_ws = take((size_t)s->model_ws_bytes);
     s->bytes = off;
@@ -214,12 +305,98 @@ extern "C" int dfx_stream_reset(dfx_stream_state *s, void *stream) {
     DFX_HIP(hipMemcpy(s->buf + s->unit_state, us.data(), us.size() * 4, hipMemcpyHostToDevice));
     if (s->gate_buf) DFX_HIP(hipMemset(s->gate_buf, 0, s->gate_bytes));  // skip counters, c0 windows (zero = the causal padding)
     s->frames = 0;
+    s->birth.assign((size_t)s->B, 0);   // (the device copy is part of buf: zeros)
+    s->mixed_until = s->warm_until = 0;
     s->flip = 0;
     s->lin_pos = 0;
     s->lin_owns = false;   // (both forms are all zeros now)
     s->feat_owns = false;
     s->hflip = 0;
     s->c0ring_ok = true;   // (zeros = the causal padding in front of the stream)
+    return DFX_OK;
+}
+
+// The rows of every state array that a stream's start zeroes, in whichever form currently holds the state (both ring parities, the
+// linear windows' history at lin_pos, both GRU buffers, the pending sums, the gate arrays and shadow copies).
+static int stream_state_rows(const dfx_stream_state *S, DfxRowClear &R) {
+    const dfx_model_cfg &c = S->m->cfg;
+    const int64_t B = S->B, H = S->H, Hs = S->H + S->L, E = c.nb_erb, Fd = c.nb_df, ML = S->st->N - S->st->hop, Fp = S->Fp;
+    R.n = 0;
+    bool ok = true;
+    auto add = [&](unsigned char *p, int64_t stride, int64_t bytes, int reps = 1, int64_t rep_stride = 0) { ok = R.add(p, stride, bytes, reps, rep_stride) && ok; };
+    for (int i = 0; i < 2; ++i) {
+        add(S->buf + S->ana_mem[i], ML * 4, ML * 4);
+        add(S->buf + S->syn_mem[i], ML * 4, ML * 4);
+        add(S->buf + S->hist_fe[i], H * E * 4, H * E * 4);
+        add(S->buf + S->hist_fs[i], H * Fd * 8, H * Fd * 8);
+        add(S->buf + S->hist_spec[i], Hs * Fp * 8, Hs * Fp * 8);
+    }
+    if (S->lin_cap > 0) add(S->buf + S->spec_lin + S->lin_pos * Fp * 8, S->lin_cap * Fp * 8, Hs * Fp * 8);
+    if (S->lin_cap > 0 && S->feat_cap > 0) {
+        add(S->buf + S->fe_lin + S->lin_pos * E * 4, S->feat_cap * E * 4, H * E * 4);
+        add(S->buf + S->fs_lin + S->lin_pos * Fd * 8, S->feat_cap * Fd * 8, H * Fd * 8);
+    }
+    add(S->buf + S->h_state, 1024, 1024, S->layers, B * 1024);
+    add(S->buf + S->h_state2, 1024, 1024, S->layers, B * 1024);
+    if (S->c0ring_bytes) add(S->buf + S->c0ring, (int64_t)(S->c0ring_bytes / (size_t)B), (int64_t)(S->c0ring_bytes / (size_t)B));
+    if (S->gate_buf) {
+        unsigned char *g = S->gate_buf;
+        const int kt = c.df_pathway_kernel_size_t;
+        add(g + S->g_flags, 1, 1);
+        add(g + S->g_counter, 4, 4);
+        add(g + S->g_sh_erb, E * 4, E * 4);
+        add(g + S->g_sh_unit, Fd * 4, Fd * 4);
+        add(g + S->g_sh_h, 1024, 1024, S->layers, B * 1024);
+        if (S->g_pend2_ok) {
+            const int64_t pb = (int64_t)2 * (kt - 1) * ((Fd + 15) / 16) * 64 * 16;
+            add(g + S->g_pend2, pb, pb);
+            add(g + S->g_par, 1, 1);
+            add(g + S->g_cnt, 4, 4);
+        } else if (kt > 1) {
+            const int64_t wb = (int64_t)(H + 1) * Fd * c.conv_ch * 4;
+            add(g + S->g_c0_win, wb, wb);
+        }
+    }
+    if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream reset: more state arrays than DFX_ROWS_MAX_ENTRIES");
+    return DFX_OK;
+}
+
+extern "C" int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, void *stream) {
+    if (!s || count < 0 || (count > 0 && !ids)) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_reset_streams: null handle or id list");
+    const int ch = s->channels;
+    const int64_t ns = s->B / ch;
+    for (int64_t i = 0; i < count; ++i)
+        if (ids[i] < 0 || ids[i] >= ns)
+            DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_reset_streams: stream index %lld is not in [0, %lld)", (long long)ids[i], (long long)ns);
+    if (count == 0) return DFX_OK;
+    if (int rc = dfx_require_device()) return rc;
+    hipStream_t hs = dfx_stream(stream);
+    const dfx_model_cfg &c = s->m->cfg;
+    const int E = c.nb_erb, Fd = c.nb_df;
+    const float erb_step = E > 1 ? (-90.f - -60.f) / (float)(E - 1) : 0.f, unit_step = Fd > 1 ? (0.0001f - 0.001f) / (float)(Fd - 1) : 0.f;
+    DfxRowClear R;
+    if (int rc = stream_state_rows(s, R)) return rc;
+    for (int64_t i0 = 0; i0 < count; i0 += DFX_RESET_IDS) {
+        DfxRowIds I;
+        I.n = (int)(count - i0 < DFX_RESET_IDS ? count - i0 : DFX_RESET_IDS);
+        for (int i = 0; i < I.n; ++i) I.id[i] = (int)ids[i0 + i];
+        dfx_launch(dfx_k_stream_reset_rows, dim3((unsigned)(I.n * ch), 4), dim3(256), 0, hs, R, I, ch, reinterpret_cast<float *>(s->buf + s->erb_state), E,
+                   erb_step, reinterpret_cast<float *>(s->buf + s->unit_state), Fd, unit_step, reinterpret_cast<int64_t *>(s->buf + s->birth_dev), s->frames);
+        DFX_LAUNCH_CHECK();
+    }
+    for (int64_t i = 0; i < count; ++i)
+        for (int k = 0; k < ch; ++k) s->birth[(size_t)(ids[i] * ch + k)] = s->frames;
+    if (s->frames > 0) {   // (frames == 0: every stream of the handle is at its start anyway)
+        s->mixed_until = s->frames + s->H + s->L;
+        s->warm_until = s->frames + s->L;
+    }
+    return DFX_OK;
+}
+
+extern "C" int dfx_stream_frames(const dfx_stream_state *s, int64_t *frames_out) {
+    if (!s || !frames_out) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_frames: null argument");
+    const int64_t ns = s->B / s->channels;
+    for (int64_t k = 0; k < ns; ++k) frames_out[k] = s->frames - s->birth[(size_t)(k * s->channels)];
     return DFX_OK;
 }
 
@@ -475,6 +652,10 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
     // padding of pad_feat, deepfilternet3.py:357-361) and they are not computed.
     const int64_t a0 = S->frames, T = H + n;
     const int64_t skip = a0 < L ? ((L - a0) < n ? (L - a0) : n) : 0;
+    // streams that started over on their own (dfx_stream_reset_streams): mixed — one of them is still younger than the window, the pass takes
+    // t_zero per stream; warm — one of them is younger than the lookahead (the caller passes one hop at a time then): dfx_k_stream_warm
+    const bool mixed = skip < n && a0 < S->mixed_until, warm = mixed && a0 < S->warm_until;
+    if (warm && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "warm-up hops of a reset stream are passed one at a time");
     float *work_fe = fp(S->work_fe), *work_fs = fp(S->work_fs), *work_spec = fp(S->work_spec);
     struct Ring { size_t *hist; float *nw, *work; int64_t h, row; bool zero_skipped; } rings[2] = {
         {S->hist_fe, new_fe, work_fe, H, E, true}, {S->hist_fs, new_fs, work_fs, H, Fd * 2, true}};
@@ -550,6 +731,13 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         sc.H = H + skip;
         const int64_t pos0 = Hs - a0;  // local index of net position 0
         sc.t_zero = pos0 > 0 ? pos0 : 0;
+        if (mixed) {
+            int *tz = reinterpret_cast<int *>(S->buf + S->tz_rows);
+            dfx_launch(dfx_k_stream_tzero, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const int64_t *)reinterpret_cast<int64_t *>(S->buf + S->birth_dev),
+                       a0, Hs, tz, B);
+            DFX_LAUNCH_CHECK();
+            sc.t_zero_rows = tz;
+        }
         sc.spec_T = spec_win_T;
         sc.spec_stride = Fp;
         sc.feat_T = feat_T;
@@ -599,6 +787,37 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
                 dfx_launch(dfx_k_gate_c0_shift, dim3((unsigned)B, 4), dim3(256), 0, s, (const unsigned char *)gflags, gp(S->g_c0_win), B, T,
                            c.df_pathway_kernel_size_t, frame);
             }
+            DFX_LAUNCH_CHECK();
+        }
+        if (warm) {   // the streams of this pass that have no net position yet: zero features, network state and enhanced spectrum
+            DfxRowClear R;
+            R.n = 0;
+            bool ok = true;
+            auto add = [&](void *ptr, int64_t stride, int64_t bytes, int reps = 1, int64_t rep_stride = 0) { ok = R.add(ptr, stride, bytes, reps, rep_stride) && ok; };
+            add(out_spec, Fp * 8, Fp * 8);
+            if (flin) {
+                add(fp(S->fe_lin) + (lin_pos0 + H) * E1, capf * E1 * 4, E1 * 4);
+                add(fp(S->fs_lin) + (lin_pos0 + H) * D2, capf * D2 * 4, D2 * 4);
+            } else {
+                add(fp(S->hist_fe[S->flip ^ 1]) + (H - 1) * E1, H * E1 * 4, E1 * 4);
+                add(fp(S->hist_fs[S->flip ^ 1]) + (H - 1) * D2, H * D2 * 4, D2 * 4);
+            }
+            add(fp(S->hflip ? S->h_state2 : S->h_state), 1024, 1024, S->layers, B * 1024);   // (the buffer that holds the states after this pass)
+            if (S->c0ring_bytes) add(S->buf + S->c0ring, (int64_t)(S->c0ring_bytes / (size_t)B), (int64_t)(S->c0ring_bytes / (size_t)B));
+            if (gated) {
+                const int kt = c.df_pathway_kernel_size_t;
+                add(gflags, 1, 1);
+                if (S->g_pend2_ok) {
+                    const int64_t pb = (int64_t)2 * (kt - 1) * ((Fd + 15) / 16) * 64 * 16;
+                    add(S->gate_buf + S->g_pend2, pb, pb);
+                    add(S->gate_buf + S->g_par, 1, 1);
+                    add(S->gate_buf + S->g_cnt, 4, 4);
+                } else if (kt > 1) {
+                    add(gp(S->g_c0_win), T * Fd * c.conv_ch * 4, T * Fd * c.conv_ch * 4);
+                }
+            }
+            if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream warm-up: more state arrays than DFX_ROWS_MAX_ENTRIES");
+            dfx_launch(dfx_k_stream_warm, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount, B);
             DFX_LAUNCH_CHECK();
         }
     }
@@ -674,8 +893,20 @@ static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, f
         }
         return DFX_OK;
     }
-    if (int rc = stream_body(S, x, n, y, lsnr_out, s)) return rc;
-    if (advances) S->frames += n;
+    // hops inside the warm-up of a stream that started over on its own (dfx_stream_reset_streams) are passed one at a time, the rest as one pass
+    int64_t done = 0;
+    for (; advances && done < n && S->frames < S->warm_until; ++done) {
+        if (int rc = stream_body(S, x + done * hop, 1, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n)) return rc;
+        S->frames += 1;
+        S->flip ^= 1;
+    }
+    if (done == n) return DFX_OK;
+    if (done > 0) {
+        if (int rc = stream_body(S, x + done * hop, n - done, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n)) return rc;
+    } else if (int rc = stream_body(S, x, n, y, lsnr_out, s)) {
+        return rc;
+    }
+    if (advances) S->frames += n - done;
     S->flip ^= 1;
     return DFX_OK;
 }
@@ -691,6 +922,8 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
                                       void *stream) {
     if (!S || !spec || !gains || !coefs || !stages) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_raw: null argument");
     if (!S->gated || !S->gate_buf) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_raw: switch gating on first (dfx_stream_set_gating)");
+    if (S->frames < S->mixed_until)
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_process_raw: a stream reset by dfx_stream_reset_streams is younger than the window (the raw path has one start for all streams)");
     if (int rc = dfx_require_device()) return rc;
     if (int rc = model_poll(S->m)) return rc;
     hipStream_t s = dfx_stream(stream);

@@ -995,6 +995,7 @@ struct DfxCphArgs {
     int64_t t_begin, t_zero, t_end;  // as in DfxCp2Args
     unsigned int *err;        // as in DfxC01hArgs
     int64_t feat_T = 0;       // as in DfxC01hArgs
+    const int *t_zero_rows = nullptr;   // non-null: t_zero per clip (streams of a handle that started over at different hops); null: the scalar
 };
 
 // (Two 16-bin blocks per wave side by side — two independent tiles in one instruction stream, df_conv0's fragments in LDS to make room for the
@@ -1064,6 +1065,7 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         const int64_t t0 = A.t_begin + (int64_t)seg * A.tseg;
         const int64_t t1 = (t0 + A.tseg < A.t_end) ? t0 + A.tseg : A.t_end;
         const unsigned cbase = (unsigned)b * (unsigned)fT * (unsigned)Fd;   // scalar
+        const int64_t tz = A.t_zero_rows ? (int64_t)A.t_zero_rows[b] : A.t_zero;   // scalar
         // the patch of frame t (scalar) and this lane's bin: four taps, zero outside the clip / the bins / the causal padding
         auto patch = [&](int t, bool ok, float2 (&rw)[4]) {
             const unsigned pbase = cbase + (unsigned)(t * Fd + f);
@@ -1082,7 +1084,7 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         auto make_frame = [&](dfx_h8 (&dh)[KC], dfx_h8 (&dl)[KC], int64_t tau, const float2 (&rw)[4]) {
             float c0v[CPL];
             // frames before the clip are the zero padding of c0 itself (wave-uniform test)
-            dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, rw, fvalid && tau >= A.t_zero, c0v, amax);
+            dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, rw, fvalid && tau >= tz, c0v, amax);
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) dfx_split8_g(c0v + 8 * kc, dh[kc], dl[kc], amax);
         };
@@ -1177,6 +1179,7 @@ __global__ void __launch_bounds__(256, REBUILD ? 1 : 2) dfx_k_df_convp_step(DfxC
         const int64_t b = run / A.nfb;
         const int f = fb * 16 + jl;
         const bool fvalid = f < A.Fd;
+        const int64_t tz = A.t_zero_rows ? (int64_t)A.t_zero_rows[dfx_wave_uniform((int)b)] : A.t_zero;   // (a wave owns one stream: a scalar load)
         const int half_in = par ? (int)(par[b] & 1) : 0, half_out = par ? half_in ^ 1 : 0, halves = par ? 2 : 1;
         const int slot0 = cnt ? cnt[b] % NS : slot_new;
         auto slot_ptr = [&](int j, int half) { return pend + ((((size_t)b * halves + half) * NS + (slot0 + j) % NS) * A.nfb + fb) * 64 + lane; };   // sum of out[t + j]
@@ -1195,7 +1198,7 @@ __global__ void __launch_bounds__(256, REBUILD ? 1 : 2) dfx_k_df_convp_step(DfxC
             float2 raw[4];
             dfx_c0_patch_load(A.feat, b, tau, f, fvalid && tau >= 0, A.T, A.Fd, A.L, q, raw, A.feat_T);
             float c0v[CPL];
-            dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, raw, fvalid && tau >= A.t_zero, c0v, amax);
+            dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, raw, fvalid && tau >= tz, c0v, amax);
             dfx_h8 xh[KC], xl[KC];
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) dfx_split8_g(c0v + 8 * kc, xh[kc], xl[kc], amax);
@@ -2408,6 +2411,7 @@ struct DfxCp2Args {
     float *out;         // [B, NO/2, T, Fd, 2]  (tap-major, DFX_COEF_BOTF)
     int64_t B, T;
     int Fd, NO, nfb, nseg, tseg;  // nfb = ceil(Fd/16) bin blocks, nseg segments of tseg frames (tseg % kt == 0)
+    const int *t_zero_rows = nullptr;   // non-null: t_zero per clip (as in DfxCphArgs); null: the scalar
 };
 
 // FUSE_C0: the window frames are not loaded but recomputed from feat_spec (dfx_c0_tile above): no c0 tensor exists and the kernel's
@@ -2445,10 +2449,11 @@ __global__ void __launch_bounds__(256) dfx_k_df_convp2(DfxCp2Args A) {
         const bool fvalid = f < A.Fd;
         const int64_t t0 = A.t_begin + (int64_t)seg * A.tseg;
         const int64_t t1 = (t0 + A.tseg < A.t_end) ? t0 + A.tseg : A.t_end;
+        const int64_t tz = A.t_zero_rows ? (int64_t)A.t_zero_rows[dfx_wave_uniform((int)b)] : A.t_zero;   // (a wave owns one clip: a scalar load)
         float win[KT][CPL];
         auto load_frame = [&](float (&dst)[CPL], int64_t tau) {
             if (FUSE_C0) {
-                if (tau >= A.t_zero) {  // wave-uniform; frames before the clip are the zero padding of c0 itself
+                if (tau >= tz) {  // wave-uniform; frames before the clip are the zero padding of c0 itself
                     float bv[5];
                     dfx_c0_patch(A.feat, b, tau, f, fvalid, A.T, A.Fd, A.L, q, bv);
                     dfx_c0_tile<C>(areg0, bias0, bv, fvalid, dst);
@@ -2456,7 +2461,7 @@ __global__ void __launch_bounds__(256) dfx_k_df_convp2(DfxCp2Args A) {
 #pragma unroll
                     for (int i = 0; i < CPL; ++i) dst[i] = 0.f;
                 }
-            } else if (fvalid && tau >= A.t_zero) {
+            } else if (fvalid && tau >= tz) {
                 const float4 *p = reinterpret_cast<const float4 *>(A.c0 + ((b * A.T + tau) * A.Fd + f) * C + 4 * q);
 #pragma unroll
                 for (int v = 0; v < V4; ++v) {  // float4 v of this lane = channels 16*v + 4*q .. +3 (k-steps 4v .. 4v+3)

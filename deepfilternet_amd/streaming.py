@@ -18,6 +18,8 @@ zeros without being processed.
 ``channels=k`` makes every k consecutive rows the channels of one stream (``RuntimeParams::n_ch``): per-channel STFT / network state,
 one ERB mask per stream (``reduce_mask`` = "mean" (reference default) | "max" | "none", tract.rs:96-118,868-902), one stage decision
 per stream (taken from its first channel's local SNR).
+
+``rt.reset([3, 17])`` makes single streams start over (a new caller in a used slot) while all others run on; ``rt.frames`` are the per-stream ages in hops.
 """
 from __future__ import annotations
 
@@ -87,8 +89,25 @@ class DfStream:
         _lib.check(_lib.lib().dfx_stream_set_thresholds(self._h, float(min_db_thresh), float(max_db_erb_thresh),
                                                         float(max_db_df_thresh)))
 
-    def reset(self) -> None:
-        _lib.check(_lib.lib().dfx_stream_reset(self._h, _lib.stream()))
+    def reset(self, streams=None) -> None:
+        """``None``: the whole handle goes back to the state after creation.  A sequence or integer tensor of stream indices: those
+        streams start over like the streams of a fresh handle (``delay_frames`` hops of silence, then their own signal since the reset,
+        enhanced and delayed), every other stream is untouched; settings are handle-wide and stay.  Does not wait for the device."""
+        if streams is None:
+            _lib.check(_lib.lib().dfx_stream_reset(self._h, _lib.stream()))
+            return
+        ids = torch.as_tensor(streams).reshape(-1)
+        if ids.numel() and (ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool):
+            raise TypeError("stream indices must be integers")
+        ids = ids.to("cpu", torch.int64).contiguous()
+        _lib.check(_lib.lib().dfx_stream_reset_streams(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), _lib.stream()))
+
+    @property
+    def frames(self) -> torch.Tensor:
+        """Hops of network time every stream has consumed since its own last reset: CPU int64 [streams / channels]."""
+        out = torch.zeros(self.streams // self.channels, dtype=torch.int64)
+        _lib.check(_lib.lib().dfx_stream_frames(self._h, C.cast(out.data_ptr(), C.POINTER(C.c_int64))))
+        return out
 
     def process(self, frames: torch.Tensor, return_lsnr: bool = False):
         """df_process_frame (capi.rs:161) for every stream: ``frames`` [streams, n*hop] float32 -> enhanced [streams, n*hop]

@@ -298,11 +298,27 @@ int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int1
  *   taken from the first channel's local SNR (:468), one decision and one skip counter per stream.
  * lsnr (optional) receives the local SNR estimate [streams, n] in dB (df_process_frame's return value); not meaningful for the
  * warm-up hops.
+ *   Slots (dfx_stream_reset_streams): the start-of-stream position is per stream.  A stream that is reset while the others run on
+ *   behaves, from the next dfx_stream_process call, like a stream of a freshly created handle with the same settings: `lookahead`
+ *   hops of silence, then dfx_enhance(pad=0) of its own signal since the reset, delayed; the other streams do not notice.  While a
+ *   reset stream is inside its first `lookahead` hops, a call of several hops is cut by the library into one-hop passes for those
+ *   hops and one pass for the rest (the results do not depend on the cut beyond rounding, as for any other cut).
+ *   dfx_stream_process_raw has one start for all streams: it refuses (DFX_ERR_UNSUPPORTED) while such a stream is younger than the
+ *   window of history + lookahead hops.  A refused call does not advance the handle, so on a handle that is driven through the raw
+ *   entry point alone the refusal lasts until dfx_stream_process has carried the handle past that window or dfx_stream_reset has
+ *   reset all of it: do not reset single streams of such a handle.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dfx_stream_state dfx_stream_state;
 int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out);
 void dfx_stream_free(dfx_stream_state *s);
 int dfx_stream_reset(dfx_stream_state *s, void *stream);                 /* back to the state after create */
+/* Streams ids[0..count) start over as after dfx_stream_create; every other stream is untouched.  ids: HOST array of stream
+ * indices in [0, rows / channels) (a multi-channel stream is reset as a whole), duplicates allowed.  Settings (attenuation limit,
+ * post-filter beta, gating, thresholds, channels) are handle-wide and stay.  Enqueued on `stream`, ordered with dfx_stream_process
+ * calls on the same stream; does not wait for the device. */
+int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, void *stream);
+/* hops of network time each stream has consumed since its own last reset (host array, [rows / channels]); host bookkeeping, no device access */
+int dfx_stream_frames(const dfx_stream_state *s, int64_t *frames_out);
 int dfx_stream_frame_length(const dfx_stream_state *s);                  /* hop size in samples (df_get_frame_length) */
 int dfx_stream_delay_frames(const dfx_stream_state *s);                  /* lookahead in hops */
 int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db);         /* df_set_atten_lim: |dB| >= 100 off, < 0.01 bypass */

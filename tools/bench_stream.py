@@ -1,7 +1,10 @@
 #!/usr/bin/env python3
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
-    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200]
+    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K]
+
+--churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
+callers come and go.
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
 one GPU sustains at that call size (a stream needs 100 hops/s)."""
@@ -25,6 +28,7 @@ def main() -> None:
     ap.add_argument("--model", default="df3", choices=["df3", "df3_ll", "defaults"],
                     help="df3_ll: DeepFilterNet3 without lookahead (the reference's low-latency LADSPA model, ladspa/README.md:3)")
     ap.add_argument("--gating", action="store_true", help="per-stream stage gating + silent-input shortcut (tract.rs:513-525,658-672)")
+    ap.add_argument("--churn", type=int, default=0, help="reset this many streams before every call, rotating through the pool")
     args = ap.parse_args()
     from deepfilternet_amd import _lib
     from deepfilternet_amd.config import ModelParams
@@ -41,12 +45,22 @@ def main() -> None:
         rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating)
         hop = rt.frame_length
         x = 0.1 * torch.randn((args.streams, n * hop), device=dev)
+        nslots, churn_pos = args.streams, 0
+
+        def churn():   # the next K slots of the pool get a new caller
+            nonlocal churn_pos
+            if args.churn > 0:
+                rt.reset([(churn_pos + k) % nslots for k in range(args.churn)])
+                churn_pos = (churn_pos + args.churn) % nslots
+
         for _ in range(10):
+            churn()
             rt.process(x)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         dev_sync = int(os.environ.get("DFX_BENCH_DEV_SYNC", "0"))   # dev: the host waits after every n-th call (enqueue depth experiment)
         for i in range(args.calls):
+            churn()
             y = rt.process(x)
             if dev_sync and (i + 1) % dev_sync == 0:
                 torch.cuda.synchronize()
@@ -63,7 +77,7 @@ def main() -> None:
         ms_call = dt / args.calls * 1e3
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
-                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating),
+                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         del rt
 
