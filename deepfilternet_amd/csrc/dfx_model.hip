@@ -89,6 +89,8 @@ struct GruW {
     float whh_unscale = 1.f;
     size_t whh_pj = 0;      // W_hh in the projection kernel's fragment order (dfx_k_gru_step_h3: one time step of many streams), same scale
     size_t whh_x32 = 0;     // W_hh as fp32 fragments in dfx_k_gru_rec_h3's order (dfx_k_gru_rec_x32: the exact recurrence of the layer-pipelined phase)
+    size_t wih_x32 = 0;     // W_ih in the same fp32 fragment order, exact models only (dfx_k_gru_step_x32: one time step of many streams; it reads W_hh from whh_x32)
+    bool has_wih_x32 = false;
 };
 struct GlinW {
     size_t w = 0;
@@ -516,6 +518,7 @@ struct Prep {
     const DfxManifest &man;
     std::vector<float> out;
     std::string err;
+    bool exact_fp32 = false;   // the model is created under DFX_EXACT_FP32=1: weights that only the exact kernels read are packed
     const float *get(const std::string &name, const DfxTensor **tt = nullptr) {
         const DfxTensor *t = man.find(name);
         if (!t) {
@@ -792,9 +795,10 @@ bool prep_gru(Prep &P, const std::string &name, int layers, std::vector<GruW> &o
                                 dst[((frag + 1) * 64 + l) * 8 + i] = lb;
                             }
         }
-        {   // the same fragment order in fp32: [16-unit tile][k-chunk][gate][half][lane][4], half h = weights 32 kc + 8 q + 4 h + 0..3 of the lane's unit
-            g.whh_x32 = P.alloc((size_t)3 * H * H);
-            float *dst = &P.out[g.whh_x32];
+        // the same fragment order in fp32: [16-unit tile][k-chunk][gate][half][lane][4], half h = weights 32 kc + 8 q + 4 h + 0..3 of the lane's unit
+        auto pack_x32 = [&](const float *w) {
+            const size_t off = P.alloc((size_t)3 * H * H);
+            float *dst = &P.out[off];
             for (int ut = 0; ut < 16; ++ut)
                 for (int kc = 0; kc < 8; ++kc)
                     for (int gate = 0; gate < 3; ++gate)
@@ -803,9 +807,12 @@ bool prep_gru(Prep &P, const std::string &name, int layers, std::vector<GruW> &o
                                 for (int i = 0; i < 4; ++i) {
                                     const int unit = 16 * ut + (l & 15), k = 32 * kc + 8 * (l >> 4) + 4 * half + i;
                                     const size_t frag = (((size_t)ut * 8 + kc) * 3 + gate) * 2 + half;
-                                    dst[(frag * 64 + l) * 4 + i] = whh[(size_t)(gate * H + unit) * H + k];
+                                    dst[(frag * 64 + l) * 4 + i] = w[(size_t)(gate * H + unit) * H + k];
                                 }
-        }
+            return off;
+        };
+        g.whh_x32 = pack_x32(whh);
+        if (P.exact_fp32) g.wih_x32 = pack_x32(wih), g.has_wih_x32 = true;   // (fp16-split models do not carry it)
         out.push_back(g);
     }
     return true;
@@ -966,6 +973,10 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
     const dfx_model_cfg &c = *cfg;
     const DfxManifest man = dfx_build_manifest(c);
     Prep P{blob, man, {}, {}};
+    {   // (read here as well as below: the weights that only the exact kernels read are packed for exact models alone)
+        const char *x = getenv("DFX_EXACT_FP32");
+        P.exact_fp32 = x && x[0] == '1';
+    }
     dfx_model *m = new dfx_model();
     m->cfg = c;
     const int C = c.conv_ch, O = c.df_order;
@@ -1176,8 +1187,7 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
     {   // independent branches of the forward pass run on two auxiliary streams (DFX_STREAMS=0 keeps everything serial)
         const char *e = getenv("DFX_STREAMS");
         m->concurrent = !(e && e[0] == '0');
-        const char *x = getenv("DFX_EXACT_FP32");
-        m->exact_fp32 = x && x[0] == '1';
+        m->exact_fp32 = P.exact_fp32;   // DFX_EXACT_FP32=1
         // (the forms that rounds 2-5 could select by environment were measured and lost; which kernel runs is decided by the model's shape and
         // the arithmetic mode alone, and tools/dev/patches/ keeps the experiments)
         m->fuse_c0 = m->cfg.df_pathway_kernel_size_t <= 5 && 2 * m->cfg.df_order <= 16;

@@ -403,8 +403,9 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             DFX_LAUNCH_CHECK();
         }
         if (gate) {  // stage decisions of the newest frame (tract.rs:658-672)
+            // (a mask-only model has no stage 2: no stream is ever flagged for it, so its DF decoder's state and delay line never move)
             dfx_launch(dfx_k_gate_post, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const float *)lsnr, T, gate->thr[0],
-                       gate->thr[1], gate->thr[2], gate->flags, B, gate->channels);
+                       gate->thr[1], run_df ? gate->thr[2] : -INFINITY, gate->flags, B, gate->channels);
             DFX_LAUNCH_CHECK();
         }
         // ---- DfDecoder on x1 (:323-331)
@@ -945,8 +946,9 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             DFX_LAUNCH_CHECK();
         }
         if (gate) {
+            // (mask-only model: the finishing kernel reads no coefficients, and a caller's coefficient array stays the zeros written above)
             dfx_launch(dfx_k_gate_edit, dim3((unsigned)B), dim3(128), 0, s, (const unsigned char *)gate->flags, mask, coefs,
-                       (const unsigned char *)bands->d_bin2band, B, T, E, Fd, O, O - 1 - c.df_lookahead);
+                       (const unsigned char *)bands->d_bin2band, B, T, E, Fd, run_df ? O : 0, O - 1 - c.df_lookahead);
             DFX_LAUNCH_CHECK();
         }
         // the real-time runtime filters with libDF's own post_filter (lib.rs:446-471 via tract.rs:603-610): Rust arithmetic and its

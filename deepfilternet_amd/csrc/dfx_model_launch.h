@@ -720,27 +720,34 @@ static int run_gru_stack(const dfx_model *m, const std::vector<GruW> &layers, co
                          float *gi, int64_t B, int64_t T, const float **y, hipStream_t s, float *hstate = nullptr, int64_t t0 = 0,
                          DfxRowMap rm = DfxRowMap{0, 0, 0}, float *hnext = nullptr, bool twin = false) {
     const int64_t R = B * (T - t0);
-    if (hstate && m->exact_fp32) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fp16-split GRU kernels (unset DFX_EXACT_FP32)");
     const float *in = x;
     float *outb = (x == bufa) ? bufb : bufa;
     for (size_t l = 0; l < layers.size(); ++l) {
         const GruW &g = layers[l];
-        if (hstate && hnext && T - t0 == 1 && !m->exact_fp32) {   // one time step of many streams: projection + recurrence + gates in one launch
+        if (hstate && hnext && T - t0 == 1) {   // one time step of many streams: projection + recurrence + gates in one launch
+            const bool x32 = m->exact_fp32;   // exact fp32 matrix ops over fp32 fragments (dfx_k_gru_step_x32)
+            if (x32 && !g.has_wih_x32) DFX_FAIL(DFX_ERR_UNSUPPORTED, "the exact model carries no fp32 W_ih fragments");
             DfxGstArgs A;
             A.x = in, A.xrm = rm;
             A.h_in = hstate + l * B * 256, A.h_out = hnext + l * B * 256;
             A.y = outb, A.yrm = rm;
-            A.wif = reinterpret_cast<const dfx_h8 *>(m->p(g.wih_h3));
-            A.whf = reinterpret_cast<const dfx_h8 *>(m->p(g.whh_pj));
+            A.wif = reinterpret_cast<const dfx_h8 *>(m->p(x32 ? g.wih_x32 : g.wih_h3));
+            A.whf = reinterpret_cast<const dfx_h8 *>(m->p(x32 ? g.whh_x32 : g.whh_pj));
             A.bias_i = m->p(g.bias_i), A.bhn = m->p(g.bhn);
-            A.unscale_i = g.wih_unscale, A.unscale_h = g.whh_unscale;
+            A.unscale_i = x32 ? 1.f : g.wih_unscale, A.unscale_h = x32 ? 1.f : g.whh_unscale;
             A.B = B;
             // 32 hidden units per workgroup (twice the workgroups, half the chunk) unless 64-unit workgroups already fill the chip — by
             // themselves, or together with the other decoder's stack that runs at the same time (twin: at 4096 streams 0.456 vs 0.470 ms per hop)
             const bool wide = dfx_ceil_div(B, DFX_PH_BM) * 4 * (twin ? 2 : 1) >= dfx_env_num_cus();
             DfxKScope ks(DFX_K_GRU_REC, s);
             const unsigned rb8 = (unsigned)(dfx_ceil_div(dfx_ceil_div(B, DFX_PH_BM), 8) * 8);   // row blocks, padded: the kernel deals them to the XCDs
-            if (wide) {
+            if (x32 && wide) {
+                DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_gru_step_x32<4>, DFX_PH_SMEM));
+                dfx_launch(dfx_k_gru_step_x32<4>, dim3(rb8 * 4), dim3(DFX_PH_THREADS), DFX_PH_SMEM, s, A);
+            } else if (x32) {
+                DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_gru_step_x32<2>, DFX_PH_SMEM / 2));
+                dfx_launch(dfx_k_gru_step_x32<2>, dim3(rb8 * 8), dim3(DFX_PH_THREADS), DFX_PH_SMEM / 2, s, A);
+            } else if (wide) {
                 DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_gru_step_h3<4>, DFX_PH_SMEM));
                 dfx_launch(dfx_k_gru_step_h3<4>, dim3(rb8 * 4), dim3(DFX_PH_THREADS), DFX_PH_SMEM, s, A);
             } else {
@@ -753,18 +760,18 @@ static int run_gru_stack(const dfx_model *m, const std::vector<GruW> &layers, co
             continue;
         }
         if (m->exact_fp32) {
-            if (int rc = launch_proj(in, m->p(g.wih_t), m->p(g.bias_i), gi, R, 768, s)) return rc;
+            if (int rc = launch_proj(in, m->p(g.wih_t), m->p(g.bias_i), gi, R, 768, s, rm)) return rc;
         } else {
             if (int rc = launch_proj_h3(m, g, in, gi, R, 768, s, rm)) return rc;
         }
-        if (m->exact_fp32) {
+        if (m->exact_fp32 && !hstate) {   // (the VALU recurrence starts every clip from a zero state: whole sequences only)
             DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_gru_rec, DFX_GRU_SMEM));
             DfxKScope ks(DFX_K_GRU_REC, s);
             dfx_launch(dfx_k_gru_rec, dim3((unsigned)dfx_ceil_div(B, DFX_GRU_ROWS)), dim3(DFX_GRU_THREADS), DFX_GRU_SMEM, s,
                        (const float *)gi, reinterpret_cast<const float4 *>(m->p(g.whh4)), m->p(g.bhn), (const float *)nullptr,
                        (float *)nullptr, outb, B, T);
             DFX_LAUNCH_CHECK();
-        } else {
+        } else {   // fp16-split, or the frames [t0, T) of a stream handle in either arithmetic (exact: dfx_k_gru_rec_x32)
             float *hl = hstate ? hstate + l * B * 256 : nullptr;
             if (int rc = launch_gru_h3(m, g, gi, outb, hl, hl, B, T, t0, T, s)) return rc;
         }

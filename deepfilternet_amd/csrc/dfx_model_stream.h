@@ -187,8 +187,10 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: the DF state does not match the model (fft/hop/nb_erb)");
     if (c.conv_lookahead != c.df_lookahead)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: conv_lookahead != df_lookahead is not supported by the streaming path");
-    if (!m->fuse_c0 || m->exact_fp32 || !m->run_df)
-        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the default (fused, fp16-split, DF stage on) engine configuration");
+    // (either arithmetic, DF stage on or off: an exact handle keeps its feature windows in ring form and a gated one its c0 window — the forms of
+    // every model without fp16-split fragments — and its GRU layers step on dfx_k_gru_step_x32 / dfx_k_gru_rec_x32)
+    if (!m->fuse_c0)
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
     if (int rc = dfx_require_device()) return rc;
     dfx_stream_state *s = new dfx_stream_state();
     s->m = m;
@@ -248,7 +250,7 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         const int kt = c.df_pathway_kernel_size_t;
         const size_t rb = kt >= 2 && c.conv_ch % 32 == 0 ? (size_t)B * (kt - 1) * ((Fd + 15) / 16) * 64 * 16 : 0;
         constexpr bool ring_env = true;
-        if (rb > 0 && rb <= ((size_t)1 << 30) && ring_env) {
+        if (rb > 0 && rb <= ((size_t)1 << 30) && ring_env && !m->exact_fp32) {   // (only the fp16-split step kernel keeps pending sums)
             s->c0ring_bytes = rb;
             s->c0ring = take(rb);
         }

@@ -3412,6 +3412,122 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_h3(DfxGstArg
     }
 }
 
+// The exact form of the step (DFX_EXACT_FP32=1): the same workgroup shape, chunk pipeline, XCD dealing and state contract on
+// v_mfma_f32_16x16x4_f32.  A.wif / A.whf are fp32 fragments in dfx_k_gru_rec_x32's order, [16 unit tiles][8 k-chunks][3 gates][2 halves][64 lanes]
+// float4 (GruW::wih_x32 / whh_x32): half h of lane (jl, q) holds W[gate][16 tile + jl][32 kc + 8 q + 4 h + 0..3], and matrix op j of a half
+// contracts the k-set {32 kc + 8 q + 4 h + j, q = 0..3} against the j-th of the four consecutive row values the lane holds — the rows
+// need no scaling, no split and no range guard, and stay in the registers they were loaded into.  A chunk (one gate of one matrix, CT
+// tiles) is 8 x CT x 2 KB: 64 KB at CT = 4 like the split kernel's hi + lo chunk, in runs of 2 KB of the fragment array.  Per wave
+// 6 x 64 CT matrix ops of 32 cycles (CT = 4: 20 us of pipe time per wave, two waves per SIMD) against 2 LDS reads of 16 bytes per 8 ops:
+// the matrix pipe sets the pace.  Gate math: dfx_gru_h3_run's (dfx_k_gru_rec_x32 takes the calls of several hops).  A.unscale_* are not read.
+// (DFX_GST_ABLATE: bits 2, 4 and 8 as in the split kernel; there is no form without the matrix ops.)
+template <int CT>
+__global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_x32(DfxGstArgs A) {
+    static_assert(CT == 2 || CT == 4, "32 or 64 hidden units per workgroup");
+    constexpr int CHUNK = 8 * CT * 2 * 64;   // 16-byte pieces per chunk of this workgroup: [kc][ct][half][lane]
+    constexpr int PER_T = CHUNK / DFX_PH_THREADS;
+    constexpr int NU = 16 / CT;              // unit blocks per layer
+    static_assert((size_t)2 * CHUNK * 16 <= DFX_PH_SMEM, "two chunks fit the projection kernel's LDS");
+    DFX_DYN_SMEM(dfx_h8, ws);  // [2][CHUNK]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
+    // (row blocks dealt to the XCDs as in dfx_k_gru_step_h3: grid = row blocks padded to a multiple of 8, times NU)
+    const int xcd = (int)(blockIdx.x & 7), kk = (int)(blockIdx.x >> 3);
+    const int u = kk % NU;   // block of 16 * CT hidden units = the unit tiles CT u .. CT u + CT - 1
+    const int64_t rb = xcd + 8 * (int64_t)(kk / NU);
+    if (rb * DFX_PH_BM >= A.B) return;
+    const int64_t b = rb * DFX_PH_BM + 16 * wave + jl;
+    const bool ok = b < A.B;
+    // piece e = ((kc * CT + ct) * 2 + half) * 64 + lane of chunk i (i < 3: W_ih, gate i; else W_hh, gate i - 3) inside the fragment array
+    auto src_of = [&](int i, int e) -> const dfx_h8 * {
+        const int kc = e / (CT * 128), rem = e - kc * (CT * 128), ct = rem >> 7;
+        return (i < 3 ? A.wif : A.whf) + ((((size_t)(CT * u + ct) * 8 + kc) * 3 + (i % 3)) * 128 + (rem & 127));
+    };
+    // both operand rows are requested before anything waits for data, the first chunk goes to LDS meanwhile (rows past the end read the last row)
+    f32x4 xv[16], hv[16];   // [2 kc + half]: the row's values 32 kc + 8 q + 4 half + 0..3
+    const int64_t bl = ok ? b : A.B - 1;
+    const int64_t xr = dfx_row(A.xrm, bl);
+    auto fetch_row = [&](const float *row, f32x4 (&v)[16]) {
+        const float4 *p = reinterpret_cast<const float4 *>(row + 8 * q);
+#pragma unroll
+        for (int i = 0; i < 16; ++i) {
+            const float4 t = !(DFX_GST_ABLATE & 4) ? p[8 * (i >> 1) + (i & 1)] : make_float4(0.f, 0.f, 0.f, 0.f);
+            v[i] = f32x4{t.x, t.y, t.z, t.w};
+        }
+    };
+    fetch_row(A.x + xr * 256, xv);
+    fetch_row(A.h_in + bl * 256, hv);
+#pragma unroll
+    for (int i = 0; i < PER_T; ++i) ws[i * DFX_PH_THREADS + tid] = *src_of(0, i * DFX_PH_THREADS + tid);
+    f32x4 g[6][CT];   // gi (r, z, n) then gh (r, z, n)
+    __syncthreads();
+    dfx_static_for<0, 6>([&](auto cc) {
+        constexpr int c = decltype(cc)::value;
+        const dfx_h8 *wc = ws + (size_t)(c & 1) * CHUNK;
+        dfx_h8 pre[PER_T];
+        if constexpr (c + 1 < 6 && !(DFX_GST_ABLATE & 2)) {
+#pragma unroll
+            for (int i = 0; i < PER_T; ++i) pre[i] = *src_of(c + 1, i * DFX_PH_THREADS + tid);
+            DFX_SCHED_BARRIER();   // the loads are issued here, above the matrix ops (see dfx_k_gru_step_h3)
+        }
+        f32x4 acc[CT];
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int kc = 0; kc < 8; ++kc) {
+#pragma unroll
+            for (int hf = 0; hf < 2; ++hf) {
+                f32x4 w[CT];
+#pragma unroll
+                for (int ct = 0; ct < CT; ++ct) w[ct] = __builtin_bit_cast(f32x4, wc[((kc * CT + ct) * 2 + hf) * 64 + lane]);
+                const f32x4 v = c < 3 ? xv[2 * kc + hf] : hv[2 * kc + hf];
+                // k ascending inside the chunk; consecutive ops go to different accumulators (a dependent op waits 40 cycles, an independent one 32)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int ct = 0; ct < CT; ++ct) acc[ct] = __builtin_amdgcn_mfma_f32_16x16x4f32(w[ct][j], v[j], acc[ct], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) g[c][ct] = acc[ct];
+        if constexpr (c + 1 < 6) {
+            dfx_h8 *dst = ws + (size_t)((c + 1) & 1) * CHUNK;
+            if constexpr (!(DFX_GST_ABLATE & 2)) {
+#pragma unroll
+                for (int i = 0; i < PER_T; ++i) dst[i * DFX_PH_THREADS + tid] = pre[i];
+            }
+            __syncthreads();
+        }
+    });
+    if (ok) {
+        const int64_t yr = A.y ? dfx_row(A.yrm, b) : 0;
+#pragma unroll
+        for (int ct = 0; ct < CT; ++ct) {
+            const int n0 = 16 * CT * u + 16 * ct + 4 * q;   // D leaves lane (row jl, q) with the units n0 .. n0 + 3
+            const float4 br = *reinterpret_cast<const float4 *>(A.bias_i + n0), bz = *reinterpret_cast<const float4 *>(A.bias_i + 256 + n0),
+                         bn = *reinterpret_cast<const float4 *>(A.bias_i + 512 + n0), bh = *reinterpret_cast<const float4 *>(A.bhn + n0),
+                         hp = *reinterpret_cast<const float4 *>(A.h_in + b * 256 + n0);
+            const float brr[4] = {br.x, br.y, br.z, br.w}, bzz[4] = {bz.x, bz.y, bz.z, bz.w}, bnn[4] = {bn.x, bn.y, bn.z, bn.w},
+                        bhh[4] = {bh.x, bh.y, bh.z, bh.w}, hpp[4] = {hp.x, hp.y, hp.z, hp.w};
+            float o[4];
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                if (DFX_GST_ABLATE & 8) {
+                    o[r] = g[0][ct][r] + g[1][ct][r] + g[2][ct][r] + g[3][ct][r] + g[4][ct][r] + g[5][ct][r] + brr[r] + bzz[r] + bnn[r] + bhh[r] + hpp[r];
+                    continue;
+                }
+                const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[0][ct][r] + brr[r]) + g[3][ct][r])));
+                const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[1][ct][r] + bzz[r]) + g[4][ct][r])));
+                const float pre = (g[2][ct][r] + bnn[r]) + rg * (g[5][ct][r] + bhh[r]);
+                const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
+                o[r] = (1.f - zg) * ng + zg * hpp[r];
+            }
+            const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+            *reinterpret_cast<float4 *>(A.h_out + b * 256 + n0) = ov;
+            if (A.y) *reinterpret_cast<float4 *>(A.y + yr * 256 + n0) = ov;
+        }
+    }
+}
+
 // The same projection with TWO row tiles per wave: every W fragment read from LDS feeds 6 matrix ops instead of 3.  dfx_k_proj256_h3 is
 // bound by its LDS fragment reads (per 64-column chunk and CU: 8 waves x 64 ds_read_b128 = 512 KB against 3072 matrix-pipe cycles per
 // SIMD, and ds_read_b128 runs at half the LDS rate); here a workgroup is NW waves x 32 rows: NW = 8 (256 rows, two waves per SIMD, ~220

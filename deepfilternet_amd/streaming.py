@@ -19,6 +19,10 @@ zeros without being processed.
 one ERB mask per stream (``reduce_mask`` = "mean" (reference default) | "max" | "none", tract.rs:96-118,868-902), one stage decision
 per stream (taken from its first channel's local SNR).
 
+The handle takes the model's engine configuration: a model created under ``DFX_EXACT_FP32=1`` streams in exact fp32 arithmetic (equal to
+its own ``enhance(pad=False)`` delayed; one launch per GRU layer on a one-hop call, like the fp16-split default), and a mask-only model
+(``init_df(mask_only=True)``) streams without the DF stage: gated, it never takes stage 2, and ``process_raw`` reports gains only.
+
 ``rt.reset([3, 17])`` makes single streams start over (a new caller in a used slot) while all others run on; ``rt.frames`` are the per-stream ages in hops.
 """
 from __future__ import annotations

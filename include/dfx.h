@@ -187,7 +187,8 @@ int dfx_model_cfg_get(const dfx_model *m, dfx_model_cfg *out);
  * stream (useful for per-kernel timing).  Default: enabled (environment DFX_STREAMS=0 disables at creation). */
 int dfx_model_set_streams(dfx_model *m, int enable);
 /* DfNet(run_df=False) (deepfilternet3.py:383,433-443; init_df(mask_only=True), enhance.py:109,172-175): the DF decoder does not run,
- * the enhanced spectrum is the masked spectrum on every bin, df_coefs is not produced (a caller's buffer is zero-filled). */
+ * the enhanced spectrum is the masked spectrum on every bin, df_coefs is not produced (a caller's buffer is zero-filled).  Read by
+ * every pass: set it before the first call of a stream handle made on the model, not while one is running. */
 int dfx_model_set_run_df(dfx_model *m, int enable);
 /* Pipelining knobs (defaults 12, 32, 1; time_chunks <= 16; environment DFX_TCHUNKS / DFX_CHUNKS at creation):
  *   time_chunks      the GRU phase is cut into this many time chunks and every GRU layer runs on its own stream, chunk k of
@@ -307,6 +308,15 @@ int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int1
  *   window of history + lookahead hops.  A refused call does not advance the handle, so on a handle that is driven through the raw
  *   entry point alone the refusal lasts until dfx_stream_process has carried the handle past that window or dfx_stream_reset has
  *   reset all of it: do not reset single streams of such a handle.
+ *   Engine configurations: every model the batch path serves with a fused DF encoder streams, in either arithmetic and with the DF stage on
+ *   or off; refused (DFX_ERR_UNSUPPORTED) are conv_lookahead != df_lookahead and df_pathway_kernel_size_t > 5 or df_order > 8.  A handle
+ *   on a DFX_EXACT_FP32=1 model runs every contraction in fp32, like that model's batch path, and equals it delayed: a one-hop call steps
+ *   each GRU layer in one launch (dfx_k_gru_step_x32), a call of several hops takes the projection + recurrence kernels with the handle's
+ *   state.  Exact handles keep the encoder's feature windows in ring form and a gated one the per-stream window of c0 frames in front of
+ *   df_convp (the forms of every model without fp16-split fragments; the fp16-split default keeps linear windows and pending sums).
+ *   A mask-only model (dfx_model_set_run_df(m, 0), to be set before the handle's first call) never runs stage 2: its DF decoder's state
+ *   never moves, gating decides between zeros / pass / mask only, and dfx_stream_process_raw reports gains (stage bit 2) with zero-filled
+ *   coefficients and never bit 8.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dfx_stream_state dfx_stream_state;
 int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out);

@@ -1,10 +1,11 @@
 #!/usr/bin/env python3
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
-    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K]
+    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
+--exact: the model is created under DFX_EXACT_FP32=1 (every contraction in fp32: the one-hop GRU layers on dfx_k_gru_step_x32).
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
 one GPU sustains at that call size (a stream needs 100 hops/s)."""
@@ -29,7 +30,10 @@ def main() -> None:
                     help="df3_ll: DeepFilterNet3 without lookahead (the reference's low-latency LADSPA model, ladspa/README.md:3)")
     ap.add_argument("--gating", action="store_true", help="per-stream stage gating + silent-input shortcut (tract.rs:513-525,658-672)")
     ap.add_argument("--churn", type=int, default=0, help="reset this many streams before every call, rotating through the pool")
+    ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
+    if args.exact:
+        os.environ["DFX_EXACT_FP32"] = "1"   # read when the model is created
     from deepfilternet_amd import _lib
     from deepfilternet_amd.config import ModelParams
     from deepfilternet_amd.enhance import init_df
@@ -40,6 +44,7 @@ def main() -> None:
     if args.model == "df3_ll":
         p.conv_lookahead = p.df_lookahead = 0
     model, df_state, _, _ = init_df(params=p, state_dict=random_state_dict(p, 0), epoch="none")
+    exact = bool(model.query(model.Q_EXACT_FP32))
     dev = _lib.device()
     for n in args.frames_per_call:
         rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating)
@@ -77,7 +82,7 @@ def main() -> None:
         ms_call = dt / args.calls * 1e3
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
-                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn,
+                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "exact_fp32": exact,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         del rt
 
