@@ -497,6 +497,7 @@ struct dfx_model {
         int dftail_every = 0;           // DFX_SEQ_DFTAIL_EVERY (0: the rule in forward_impl)
         bool tail_split = true;         // the ERB decoder's linear_out on a stream of its own beside the decoder tail (round 6; DFX_TAIL_SPLIT=0 in -DDFX_DEV builds)
         int64_t convp_elems = (int64_t)1 << 29;   // DFX_CONVP_ELEMS (test hook)
+        bool erb_enc_split = false;     // DFX_ERB_ENC_SPLIT=1 (test hook): batch passes run the ERB encoder as three launches (dfx_k_erb_enc, dfx_k_pwconv_f x 2) instead of dfx_k_erb_enc4
     } sw;
     // Error words, written by kernels, read by the host (page-locked host memory the device can store to: dfx_env_err_words_alloc):
     // [0] unused, [1] fp16-split range, [2] a flag wait of the persistent GRU phase timed out.
@@ -1209,6 +1210,8 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
         {
             const char *cel = getenv("DFX_CONVP_ELEMS");   // test hook: the 32-bit-offset split of df_convp at small sizes
             if (cel && atoll(cel) > 0) m->sw.convp_elems = atoll(cel);
+            const char *ees = getenv("DFX_ERB_ENC_SPLIT");   // test hook: the three-launch form of the ERB encoder in batch passes
+            m->sw.erb_enc_split = ees && ees[0] == '1';
         }
 #ifdef DFX_DEV
         {   // dev A/Bs of the phase's side work (product builds have no such switches)

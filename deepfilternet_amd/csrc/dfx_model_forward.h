@@ -146,6 +146,9 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     const bool fuse_tail = fuse_dec && erb_tail_ok<C>(m, E);
     const bool fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
     const bool no_e0 = fuse_tail && fuse_enc;   // e0 never exists in HBM
+    // batch passes on the fp16-split path: the four ERB convolutions as one launch (dfx_k_erb_enc4); streaming passes (frame ranges, gating,
+    // row maps), exact mode and other shapes keep dfx_k_erb_enc + dfx_k_pwconv_f x 2 (DFX_ERB_ENC_SPLIT=1: batch passes too — test hook)
+    const bool fuse_enc4 = fuse_enc && !sc && !m->sw.erb_enc_split && erb_enc4_ok<C>(m, E);
     const float *e0r = no_e0 ? nullptr : e0;   // what the decoder tail is handed
     if (sc && !fuse_enc) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
     const DfxGate *gate = sc ? sc->gate : nullptr;
@@ -297,6 +300,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     // Encoder, ERB branch (:168-171) for frames [t0, t1) = Rk rows reached through rm
     auto erb_range = [&](int64_t t0, int64_t t1, int64_t Rk, DfxRowMap rm, hipStream_t st) -> int {
         int r;
+        if (fuse_enc4) return launch_erb_enc4<C>(m, feat_erb, no_e0 ? nullptr : e0, e1, e2, e3, B, T, st, t0, Lk, t1, featT);
         if (fuse_enc) {
             if ((r = launch_erb_enc<C>(m, feat_erb, no_e0 ? nullptr : e0, e1, B, T, st, t0, Lk, t1, featT))) return r;
         } else {

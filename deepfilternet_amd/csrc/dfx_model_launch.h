@@ -401,6 +401,55 @@ static int launch_erb_enc(const dfx_model *m, const float *feat_erb, float *e0, 
     return DFX_OK;
 }
 
+// erb_conv0 -> erb_conv1 -> erb_conv2 -> erb_conv3 in one kernel (dfx_k_erb_enc4): e1 / e2 are written once and not read back by the encoder
+template <int C>
+static bool erb_enc4_ok(const dfx_model *m, int E) {
+    if constexpr (C % 32 != 0) return false;
+    const dfx_model_cfg &c = m->cfg;
+    // (the strips assume what DeepFilterNet3's encoder is: erb_conv1..3 of kernel 1 x 3 over frequency, strides 2 / 2 / 1 — the only form
+    // prep_sep packs for these layers — on E = nb_erb bins)
+    return !m->exact_fp32 && m->erb1.wt_h3 && m->erb2.wt_h3 && m->erb3.wt_h3 && E == c.nb_erb && dfx_enc4_ok(C, E);
+}
+template <int C>
+static int launch_erb_enc4(const dfx_model *m, const float *feat_erb, float *e0, float *e1, float *e2, float *e3, int64_t B, int64_t T,
+                           hipStream_t s, int64_t t_begin = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0) {
+    if constexpr (C % 32 != 0) {
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "erb enc4: conv_ch");
+    } else {
+        const dfx_model_cfg &c = m->cfg;
+        if (t_end < 0) t_end = T;
+        const int64_t R = B * (t_end - t_begin);
+        if (R <= 0) return DFX_OK;
+        DfxEnc4Args A;
+        A.feat = feat_erb;
+        A.feat_T = feat_T;
+        A.w0 = m->p(m->erb0_w);
+        A.b0 = m->p(m->erb0_b);
+        const PwW *L3[3] = {&m->erb1, &m->erb2, &m->erb3};
+        for (int l = 0; l < 3; ++l) {
+            A.dw[l] = m->p(L3[l]->dw);
+            A.bias[l] = m->p(L3[l]->bias);
+            A.wh3[l] = reinterpret_cast<const dfx_h8 *>(m->p(L3[l]->wt_h3));
+            A.unscale[l] = L3[l]->unscale;
+        }
+        A.e0 = e0, A.e1 = e1, A.e2 = e2, A.e3 = e3;
+        A.B = B;
+        A.T = T;
+        A.E = c.nb_erb;
+        A.L = L < 0 ? c.conv_lookahead : L;
+        A.t_begin = t_begin;
+        A.t_end = t_end;
+        A.err = m->d_err;
+        const size_t smem = DFX_ENC4_SMEM(C, c.nb_erb);
+        DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_erb_enc4<C>, smem));
+        DfxKScope ks(DFX_K_ERB_ENC, s);
+        const dim3 grid((unsigned)nn_grid(dfx_ceil_div(R, DFX_ENC4_WAVES), 1));
+        dfx_launch(dfx_k_erb_enc4<C>, grid, dim3(64 * DFX_ENC4_WAVES), smem, s, A);
+        DFX_LAUNCH_CHECK();
+        return DFX_OK;
+    }
+}
+
 // enc.df_conv0 -> enc.df_conv1 without the c0 round trip (dfx_k_df_conv01)
 template <int C>
 static int launch_conv01(const dfx_model *m, const PwW &w, const float *feat_spec, float *out, int64_t B, int64_t T, int Fin,

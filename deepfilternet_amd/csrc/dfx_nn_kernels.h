@@ -1529,8 +1529,9 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, (SKIP && NVI == DFX_PWF_MAXV) 
 // ERB encoder head, fused: erb_conv0 (3x3 from one channel, VALU, same arithmetic as dfx_k_conv_in_erb) -> erb_conv1 (stride 2)
 // (deepfilternet3.py:106-109,168-169).  A wave owns one frame: its E positions of e0 are one LDS strip and its E/2 positions of e1
 // one or two MFMA tiles.  e0 (the largest ERB activation) is written once and never read back by the encoder; the three feat_erb
-// rows of the NEXT frame are fetched while the current one is computed.  (Fusing erb_conv2/3 as well was measured slower: their
-// weights push the kernel to one wave per SIMD, where its dependent LDS -> VALU -> MFMA phases cannot overlap.)
+// rows of the NEXT frame are fetched while the current one is computed.  (Fusing erb_conv2/3 as well was measured slower in round 1: their
+// fp32 weights pushed the kernel to one wave per SIMD.  With fp16-split fragments in LDS it is dfx_k_erb_enc4, which batch passes run;
+// this kernel serves streaming passes, exact fp32 and the shapes dfx_enc4_ok() refuses.)
 struct DfxEncArgs {
     const float *feat;  // [B, T, E]
     const float *w0, *b0;            // erb_conv0 [3][3][C], [C]
@@ -2304,6 +2305,174 @@ __global__ void __launch_bounds__(64 * DFX_TAIL_WAVES, 1) dfx_k_erb_tail(DfxTail
         DFX_WAVE_SYNC();  // the strips are rewritten by the next frame
     }
     if (amax >= DFX_H3_LIMIT && A.err) dfx_raise(A.err + 1);
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// dfx_k_erb_enc4: the whole ERB branch of the encoder for one frame in one kernel (deepfilternet3.py:106-109,168-171):
+//     e0 = erb_conv0(feat_erb)  [E]        e1 = erb_conv1(e0)  [E] -> [E/2]        e2 = erb_conv2(e1)  [E/2] -> [E/4]        e3 = erb_conv3(e2)  [E/4]
+// As three launches (dfx_k_erb_enc, dfx_k_pwconv_f x 2) e1 and e2 were written and streamed back from HBM (6 KB of the 14.7 KB per frame), each
+// launch with its own fill and drain of the chip, in the serial front of the step.  Here a wave owns a frame and ONE strip [E][C + 4]:
+// erb_conv0 (the arithmetic of dfx_k_erb_enc) fills its E rows with e0; erb_conv1 takes its taps from them and, once every lane has its taps,
+// writes e1 over rows [0, E/2) — e0 is dead by then; erb_conv2 goes from there into rows [E/2, 3E/4), erb_conv3 from those into rows
+// [3E/4, E).  e1 / e2 / e3 leave from the strip as contiguous 16-byte runs, each requested before the next stage's matrix work; the next
+// frame's feature rows are requested before the current frame's stages.  The stage bodies are dfx_chain_tile_h3_lds (dfx_chain_stage_h3's
+// tile body, fragments of the three layers resident in LDS as in dfx_k_erb_tail): the k order, fragments, unscale factors, bias / ReLU
+// epilogue and range guard of the three-launch form — same bits.  erb_conv2 / erb_conv3 have E/4 = 8 positions per frame: half of their
+// tile's columns are idle.
+// What bounds the kernel is waves per SIMD, as in dfx_k_erb_tail (per frame ~1000 vector instructions, ~1000 cycles of the LDS pipe and 72
+// matrix ops in four dependent phases).  With a second strip for e1 (13.2 KB per wave, 8 waves per CU) it ran at 0.76 ms; with the one strip
+// (8.9 KB per wave; LDS at C = 64: tables 3 KB + fragments 48 KB + 12 x 8.9 KB = 157.9 KB, 166 registers) a workgroup of 12 waves = 3 per
+// SIMD fits a CU: 0.67 ms; erb_conv0's taps read once per four positions instead of nine times per position: 0.64 ms — for the 0.955 ms of
+// the three launches (docs/measurements.md, "The ERB encoder's four convolutions as one frame-resident kernel").
+// ---------------------------------------------------------------------------------------------------------------------
+#define DFX_ENC4_WAVES 12
+#define DFX_ENC4_TAB4(C) (3 * 3 * (C) / 4 + 3 * (C) / 4)   /* float4s: dw x3, bias x3 */
+#define DFX_ENC4_WAVE_FLOATS(C, E) ((E) * ((C) + 4) + (DFX_ENC_FS(E) + 3) / 4 * 4)
+#define DFX_ENC4_SMEM(C, E) ((size_t)DFX_ENC4_TAB4(C) * 16 + 3 * DFX_TAIL_WFRAG(C) * 16 + (size_t)DFX_ENC4_WAVES * DFX_ENC4_WAVE_FLOATS(C, E) * 4)
+static __host__ __device__ __forceinline__ bool dfx_enc4_ok(int C, int E) {
+    // E = 32 (compiled in, as in dfx_k_erb_tail): erb_conv1's E/2 positions are one 16-position tile, e1, e2 and e3 lie one behind the other
+    // in the strip of e0, the three bordered feature rows are within three loads per lane
+    return (C == 32 || C == 64) && E == 32 && DFX_ENC4_SMEM(C, E) <= (size_t)160 * 1024;
+}
+struct DfxEnc4Args {
+    const float *feat;                 // [B, feat_T or T, E]
+    const float *w0, *b0;              // erb_conv0 folded [3][3][C], [C]
+    const float *dw[3], *bias[3];      // erb_conv1..3: depthwise [3][C], BN shift [C]
+    const dfx_h8 *wh3[3];              // their pointwise fragments (pack_pw_h3)
+    float unscale[3];
+    float *e0, *e1, *e2, *e3;          // [B*T, E, C] (null: not stored), [B*T, E/2, C], [B*T, E/4, C] x2
+    int64_t B, T;
+    int E, L;
+    int64_t t_begin, t_end;            // frames [t_begin, t_end) of every clip are produced
+    int64_t feat_T;                    // > 0: frames per clip of feat
+    unsigned int *err;
+};
+// N4 float4s of a strip (rows of C floats, C + 4 apart) to one contiguous run of HBM
+template <int C, int N4>
+static __device__ __forceinline__ void dfx_enc4_store_rows(const float *strip, float4 *dst, int lane) {
+    constexpr int NV = N4 / 64, C4 = C / 4, LD = C + 4;
+    static_assert(N4 % 64 == 0, "whole 16-byte pieces per lane");
+    int ln = lane;
+    DFX_OPAQUE(ln);   // (the lane's share of the addresses per use, not held across the frame loop)
+    float4 v[NV];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+        const int idx = ln + 64 * i, row = idx / C4, k4 = idx - row * C4;
+        v[i] = *reinterpret_cast<const float4 *>(strip + row * LD + 4 * k4);
+    }
+#pragma unroll
+    for (int i = 0; i < NV; ++i) dst[ln + 64 * i] = v[i];
+}
+template <int C>
+__global__ void __launch_bounds__(64 * DFX_ENC4_WAVES, 1) dfx_k_erb_enc4(DfxEnc4Args A) {
+    constexpr int LD = C + 4, C4 = C / 4, NTH = 64 * DFX_ENC4_WAVES;
+    DFX_DYN_SMEM(float4, sm4);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4;
+    constexpr int E = 32, E1 = E / 2, E2 = E / 4, EP = E + 2;
+    float4 *dws = sm4;                  // [3 layers][3][C4]
+    float4 *bis = dws + 9 * C4;         // [3 layers][C4]
+    dfx_h8 *wfr = reinterpret_cast<dfx_h8 *>(bis + 3 * C4);   // [3 layers][NT * KC * 2 * 64]
+    float *S0 = reinterpret_cast<float *>(wfr + 3 * DFX_TAIL_WFRAG(C)) + (size_t)wave * DFX_ENC4_WAVE_FLOATS(C, E);   // e0 [E][LD]
+    float *S1 = S0, *S2 = S0 + E1 * LD, *S3 = S2 + E2 * LD;   // e1 [E1][LD] over the e0 rows erb_conv1 has read, e2 and e3 [E2][LD] behind it
+    float *fs = S0 + E * LD;            // [3][E + 2]
+#pragma unroll
+    for (int l = 0; l < 3; ++l) {   // (constant indices into the argument arrays: a run-time index would move the struct to scratch)
+        for (int i = tid; i < 3 * C4; i += NTH) dws[l * 3 * C4 + i] = reinterpret_cast<const float4 *>(A.dw[l])[i];
+        for (int i = tid; i < C4; i += NTH) bis[l * C4 + i] = reinterpret_cast<const float4 *>(A.bias[l])[i];
+        for (int i = tid; i < (int)DFX_TAIL_WFRAG(C); i += NTH) wfr[l * DFX_TAIL_WFRAG(C) + i] = A.wh3[l][i];
+    }
+    // erb_conv0: lane -> (position block lane / C4, channel quad lane % C4); C4 <= 16 divides 64.  A lane's PP positions are consecutive and
+    // taken four at a time: 3 x 6 taps read per four positions (dfx_k_erb_enc's interleaved positions read 9 per position)
+    static_assert(64 % C4 == 0, "channel quad of a lane must not depend on the load index");
+    constexpr int PP = E / (64 / C4);
+    const int c4 = lane % C4, pbase = (lane / C4) * PP;
+    float4 wv[9];
+#pragma unroll
+    for (int k = 0; k < 9; ++k) wv[k] = reinterpret_cast<const float4 *>(A.w0)[k * C4 + c4];
+    const float4 bv = reinterpret_cast<const float4 *>(A.b0)[c4];
+    __syncthreads();
+    // logical rows: (clip, produced frame), B * T < 2^31 (forward_impl refuses more): 32-bit divisions, on the scalar unit (the row is wave-uniform)
+    const uint32_t Tn = (uint32_t)(A.t_end - A.t_begin);
+    const int64_t R = A.B * (int64_t)Tn, fT = A.feat_T > 0 ? A.feat_T : A.T;
+    const int64_t rstep = (int64_t)gridDim.x * DFX_ENC4_WAVES;
+    // element i of the zero-bordered tap rows [3][E+2] of a frame (zero: border, causal pad after the lookahead shift, beyond T)
+    float fx[3];
+    auto fetch = [&](int64_t rl) {
+        const uint32_t b = (uint32_t)rl / Tn;
+        const int64_t t = A.t_begin + ((uint32_t)rl - b * Tn);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            const int i = lane + 64 * k, kt = i / EP, fp = i - kt * EP;
+            const int64_t tau = t - 2 + kt, tin = tau + A.L;
+            float v = 0.f;
+            if (rl < R && i < 3 * EP && fp >= 1 && fp <= E && tau >= 0 && tin < A.T) v = A.feat[((int64_t)b * fT + tin) * E + fp - 1];
+            fx[k] = v;
+        }
+    };
+    auto into = [&](float *strip) {
+        return [=](int p, bool valid, int nt, float4 o) {
+            if (valid) *reinterpret_cast<float4 *>(strip + p * LD + 16 * nt + 4 * q) = o;
+        };
+    };
+    float amax = 0.f;
+    int64_t rl = (int64_t)blockIdx.x * DFX_ENC4_WAVES + dfx_wave_uniform(wave);
+    fetch(rl);
+    for (; rl < R; rl += rstep) {
+        const uint32_t cb = (uint32_t)rl / Tn;
+        const int64_t r = (int64_t)cb * A.T + A.t_begin + ((uint32_t)rl - cb * Tn);   // physical row
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (lane + 64 * k < 3 * EP) fs[lane + 64 * k] = fx[k];
+        fetch(rl + rstep);   // in flight during this frame's four stages
+        DFX_WAVE_SYNC();
+        // ---- erb_conv0 (VALU, the arithmetic of dfx_k_erb_enc in the same order): fs -> S0
+        static_assert(PP % 4 == 0, "whole groups of four positions per lane");
+#pragma unroll 1   // (all PP positions unrolled: 30 taps and the scheduler's interleaved accumulators were 52 bytes of scratch per lane at C = 64)
+        for (int p4 = pbase; p4 < pbase + PP; p4 += 4) {
+            float xw[3][6];
+#pragma unroll
+            for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+                for (int i = 0; i < 6; ++i) xw[kt][i] = fs[kt * EP + p4 + i];
+#pragma unroll
+            for (int it = 0; it < 4; ++it) {
+                const int p = p4 + it;
+                float4 acc = bv;
+#pragma unroll
+                for (int kt = 0; kt < 3; ++kt)
+#pragma unroll
+                    for (int kf = 0; kf < 3; ++kf) {
+                        const float x = xw[kt][it + kf];  // bin p - 1 + kf, border included
+                        const float4 ww = wv[kt * 3 + kf];
+                        acc.x += ww.x * x;
+                        acc.y += ww.y * x;
+                        acc.z += ww.z * x;
+                        acc.w += ww.w * x;
+                    }
+                const float4 o = make_float4(fmaxf(acc.x, 0.f), fmaxf(acc.y, 0.f), fmaxf(acc.z, 0.f), fmaxf(acc.w, 0.f));
+                if (A.e0) reinterpret_cast<float4 *>(A.e0 + (r * E + p) * C)[c4] = o;   // (null: the decoder tail recomputes e0 from the features)
+                *reinterpret_cast<float4 *>(S0 + p * LD + 4 * c4) = o;
+            }
+        }
+        DFX_WAVE_SYNC();
+        // ---- erb_conv1: S0 [E] -> S1 [E/2] = the first rows of S0 (every lane has taken its taps of e0 before the first of them is overwritten)
+        dfx_chain_tile_h3_lds<C, DFX_PW_MODE_DW3>(S0, E, 2, 0, E1, dws, wfr, bis, A.unscale[0], amax, lane, [=](int p, bool valid, int nt, float4 o) {
+            if (nt == 0) DFX_WAVE_SYNC();
+            if (valid) *reinterpret_cast<float4 *>(S1 + p * LD + 16 * nt + 4 * q) = o;
+        });
+        DFX_WAVE_SYNC();
+        // ---- e1 out (under erb_conv2's matrix work); erb_conv2: S1 [E/2] -> S2 [E/4]
+        dfx_enc4_store_rows<C, E1 * C4>(S1, reinterpret_cast<float4 *>(A.e1) + r * (E1 * C4), lane);
+        dfx_chain_tile_h3_lds<C, DFX_PW_MODE_DW3>(S1, E1, 2, 0, E2, dws + 3 * C4, wfr + DFX_TAIL_WFRAG(C), bis + C4, A.unscale[1], amax, lane, into(S2));
+        DFX_WAVE_SYNC();
+        // ---- e2 out; erb_conv3: S2 [E/4] -> S3 [E/4]
+        dfx_enc4_store_rows<C, E2 * C4>(S2, reinterpret_cast<float4 *>(A.e2) + r * (E2 * C4), lane);
+        dfx_chain_tile_h3_lds<C, DFX_PW_MODE_DW3>(S2, E2, 1, 0, E2, dws + 6 * C4, wfr + 2 * DFX_TAIL_WFRAG(C), bis + 2 * C4, A.unscale[2], amax, lane, into(S3));
+        DFX_WAVE_SYNC();
+        dfx_enc4_store_rows<C, E2 * C4>(S3, reinterpret_cast<float4 *>(A.e3) + r * (E2 * C4), lane);
+        DFX_WAVE_SYNC();  // the strips are rewritten by the next frame
+    }
+    if (amax >= DFX_H3_LIMIT && A.err) dfx_raise(A.err + 1);   // a value left the f16 range of the split: reported, not hidden
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
