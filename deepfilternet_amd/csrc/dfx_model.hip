@@ -167,7 +167,10 @@ struct DfxStreamCtx {
 // stream that has been silent for more than 5 hops is not processed at all.  Lockstep streams take those decisions independently:
 // every kernel still runs for every stream (a skipped stream costs the same as a busy one on a GPU), and the decisions are applied
 // as data: flags[b] selects whose state is kept (dfx_k_gate_commit) and what the deep-filter kernel is fed (dfx_k_gate_edit).
-enum { DFX_GATE_FROZEN = 1, DFX_GATE_GAINS = 2, DFX_GATE_ZEROS = 4, DFX_GATE_DF = 8 };
+// DFX_GATE_PAUSED (pausable handles, dfx_stream_process_active): the stream sits this pass out.  It is always set together with
+// DFX_GATE_FROZEN (dfx_k_stream_pause), so every kernel that gives a frozen stream its state back does the same for a paused one; the bit
+// itself only tells dfx_k_gate_finish and the warm-up of a reset stream that no hop was consumed at all.
+enum { DFX_GATE_FROZEN = 1, DFX_GATE_GAINS = 2, DFX_GATE_ZEROS = 4, DFX_GATE_DF = 8, DFX_GATE_PAUSED = 16 };
 struct DfxGate {
     unsigned char *flags;  // [B]
     float thr[3];          // min_db_thresh, max_db_erb_thresh, max_db_df_thresh
@@ -388,6 +391,7 @@ __global__ void dfx_k_gate_pend_commit(const unsigned char *flags, unsigned char
 
 // End of a gated hop: frozen streams answer zeros and lsnr = -15 (tract.rs:522-525); the others update the skip counter from the
 // stage decision (:562-567: gains present -> 0, absent -> += 1).  warm: the hop produced no net position yet (no decision taken).
+// A paused stream (DFX_GATE_PAUSED, set with DFX_GATE_FROZEN) answers zeros too, but no estimate was made for it: its lsnr is NaN.
 __global__ void dfx_k_gate_finish(const unsigned char *flags, int *skip_counter, float *y, int64_t y_stride, int hop, float *lsnr_out,
                                   int64_t lsnr_stride, int64_t B, int warm) {
     const int64_t b = blockIdx.x;
@@ -395,7 +399,7 @@ __global__ void dfx_k_gate_finish(const unsigned char *flags, int *skip_counter,
     const unsigned char f = flags[b];
     if (f & DFX_GATE_FROZEN) {
         for (int i = threadIdx.x; i < hop; i += blockDim.x) y[b * y_stride + i] = 0.f;
-        if (threadIdx.x == 0 && lsnr_out) lsnr_out[b * lsnr_stride] = -15.f;
+        if (threadIdx.x == 0 && lsnr_out) lsnr_out[b * lsnr_stride] = (f & DFX_GATE_PAUSED) ? __int_as_float(0x7fc00000) : -15.f;
     } else if (threadIdx.x == 0 && !warm) {
         skip_counter[b] = (f & (DFX_GATE_GAINS | DFX_GATE_ZEROS)) ? 0 : skip_counter[b] + 1;
     }

@@ -99,7 +99,8 @@ __global__ void __launch_bounds__(256) dfx_k_stream_reset_rows(DfxRowClear R, Df
 __global__ void dfx_k_stream_tzero(const int64_t *birth, int64_t now, int64_t Hs, int *tz, int64_t B) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
-    const int64_t age = now - birth[b];
+    // (a stream that sits this pass out — dfx_k_stream_pause has moved its birth already — may read one hop younger than 0: its pass is discarded)
+    const int64_t age = now > birth[b] ? now - birth[b] : 0;
     tz[b] = age < Hs ? (int)(Hs - age) : 0;
 }
 
@@ -113,6 +114,42 @@ __global__ void __launch_bounds__(256) dfx_k_stream_warm(DfxRowClear R, const in
     if (b >= B || tz[b] <= H) return;
     dfx_clear_row(R, b, (int)blockIdx.y, (int)gridDim.y);
     if (gate_counter && blockIdx.y == 0 && threadIdx.x == 0) gate_counter[b] -= 1;
+}
+
+// The same on a pausable handle: a stream that sits the pass out (DFX_GATE_PAUSED) did not consume the hop — nothing of it is cleared and its
+// silent-input counter stays.
+__global__ void __launch_bounds__(256) dfx_k_stream_warm_active(DfxRowClear R, const int *tz, int H, int *gate_counter, const unsigned char *flags, int64_t B) {
+    const int64_t b = blockIdx.x;
+    if (b >= B || tz[b] <= H || (flags[b] & DFX_GATE_PAUSED)) return;
+    dfx_clear_row(R, b, (int)blockIdx.y, (int)gridDim.y);
+    if (gate_counter && blockIdx.y == 0 && threadIdx.x == 0) gate_counter[b] -= 1;
+}
+
+// ---- streams that sit a call out (dfx_stream_process_active) ------------------------------------------------------------------------------
+// The call's mask travels as a bit field in the kernel arguments (no upload, no wait): bit k of DfxPauseMask = stream first + k is paused.
+// One thread per row of the streams [first, first + n): a paused row is flagged DFX_GATE_FROZEN | DFX_GATE_PAUSED for this pass — the hold /
+// commit kernels of the gated runtime then hand it every state array back — its silent-input counter takes the value it had before
+// dfx_k_gate_pre looked at the hop (counter_before; null: no silent-input test ran), and birth[row] moves forward by `bump` hops, so that
+// the stream's age (handle hop count - birth) stands still.  set_all: the rows that take part get flags 0 (a handle without the silent-input
+// test, where no other kernel initialises the flags of the pass).
+#define DFX_PAUSE_STREAMS 4096   /* streams per launch: 512 bytes of kernel arguments */
+struct DfxPauseMask {
+    int first, n;
+    unsigned bits[DFX_PAUSE_STREAMS / 32];
+};
+__global__ void __launch_bounds__(256) dfx_k_stream_pause(DfxPauseMask P, int ch, unsigned char *flags, int set_all, int *counter, const int *counter_before,
+                                                          int64_t *birth, int bump) {
+    const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (k >= (int64_t)P.n * ch) return;
+    const int st = (int)(k / ch);
+    const int64_t row = (int64_t)P.first * ch + k;
+    if ((P.bits[st >> 5] >> (st & 31)) & 1u) {
+        flags[row] = DFX_GATE_FROZEN | DFX_GATE_PAUSED;
+        if (counter_before) counter[row] = counter_before[row];
+        birth[row] += bump;
+    } else if (set_all) {
+        flags[row] = 0;
+    }
 }
 
 // ------------------------------------------------------------------------------------------------ streaming (dfx_stream_*)
@@ -166,6 +203,17 @@ struct dfx_stream_state {
     size_t g_flags = 0, g_counter = 0, g_sh_erb = 0, g_sh_unit = 0, g_sh_h = 0, g_c0_win = 0, g_mask = 0, g_coefs = 0, gate_bytes = 0;
     size_t g_pend2 = 0, g_par = 0, g_cnt = 0;   // pending-sum form of the gated df_convp (g_pend2_ok; then g_c0_win is not allocated)
     bool g_pend2_ok = false;
+    size_t g_sh_counter = 0;  // the silent-input counters as they were before dfx_k_gate_pre (a paused stream gets its own back)
+    // Pausable handles (dfx_stream_set_pausable): a call may carry a mask of the streams that take part (dfx_stream_process_active).  Such a
+    // handle keeps its state in the per-stream forms of the gated runtime from its first hop (one hop per pass; without gating every stage
+    // is forced on and the silent-input test is off), and a paused stream is one more kind of frozen row (DFX_GATE_PAUSED).  The handle's hop
+    // count still advances with every pass; a paused stream's birth moves with it — here and, by dfx_k_stream_pause, on the device — so its
+    // age stands still.  Which passes take the per-row t_zero / the warm-up is decided per pass from the ages of the streams that take part.
+    bool pausable = false;
+    bool fresh = true;        // no hop consumed since create / dfx_stream_reset
+    std::vector<unsigned char> paused;   // [B / channels], this call: 1 = sits out
+    bool any_paused = false;
+    bool p_mixed = false, p_warm = false;   // this pass (stream_process_impl)
     // (Replaying a steady-state call from a hipGraph was built in round 1 and removed in round 4: on ROCm 7.2 the replay of the hop's kernel nodes
     // took 2.0-2.2 ms per call where plain launches take 0.4.)
 };
@@ -315,6 +363,7 @@ extern "C" int dfx_stream_reset(dfx_stream_state *s, void *stream) {
     s->feat_owns = false;
     s->hflip = 0;
     s->c0ring_ok = true;   // (zeros = the causal padding in front of the stream)
+    s->fresh = true;
     return DFX_OK;
 }
 
@@ -421,15 +470,11 @@ extern "C" int dfx_stream_set_channels(dfx_stream_state *s, int channels, int re
     return DFX_OK;
 }
 
-extern "C" int dfx_stream_set_gating(dfx_stream_state *s, int enable) {
-    if (!s) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_gating: null handle");
-    if (!enable) {
-        s->gated = false;
-        return DFX_OK;
-    }
+// the per-stream state forms (flags, counters, shadow copies, df_convp's per-stream delay line) of gated and of pausable handles
+static int stream_gate_alloc(dfx_stream_state *s, const char *who) {
     const dfx_model_cfg &c = s->m->cfg;
-    if (c.df_lookahead > 5) DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_set_gating: lookahead > 5 hops is not supported");
-    if (c.df_pathway_kernel_size_t > 5) DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_set_gating: df_pathway_kernel_size_t > 5 is not supported");
+    if (c.df_lookahead > 5) DFX_FAIL(DFX_ERR_UNSUPPORTED, "%s: lookahead > 5 hops is not supported", who);
+    if (c.df_pathway_kernel_size_t > 5) DFX_FAIL(DFX_ERR_UNSUPPORTED, "%s: df_pathway_kernel_size_t > 5 is not supported", who);
     if (!s->gate_buf) {
         const int64_t B = s->B, T = s->H + 1;
         size_t off = 0;
@@ -455,14 +500,34 @@ extern "C" int dfx_stream_set_gating(dfx_stream_state *s, int enable) {
         }
         s->g_mask = take((size_t)B * T * c.nb_erb * 4);                       // dfx_stream_process_raw: the pass's mask / coefficients
         s->g_coefs = take((size_t)B * c.df_order * T * c.nb_df * 8);
+        s->g_sh_counter = take((size_t)B * 4);
         s->gate_bytes = off;
         if (hipMalloc(reinterpret_cast<void **>(&s->gate_buf), off) != hipSuccess) {
             s->gate_buf = nullptr;
-            DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream_set_gating: device allocation of %zu bytes failed", off);
+            DFX_FAIL(DFX_ERR_ALLOC, "%s: device allocation of %zu bytes failed", who, off);
         }
         DFX_HIP(hipMemset(s->gate_buf, 0, off));
     }
+    return DFX_OK;
+}
+
+extern "C" int dfx_stream_set_gating(dfx_stream_state *s, int enable) {
+    if (!s) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_gating: null handle");
+    if (!enable) {
+        s->gated = false;
+        return DFX_OK;
+    }
+    if (int rc = stream_gate_alloc(s, "dfx_stream_set_gating")) return rc;
     s->gated = true;
+    return DFX_OK;
+}
+
+extern "C" int dfx_stream_set_pausable(dfx_stream_state *s, int enable) {
+    if (!s) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_pausable: null handle");
+    if (!s->fresh) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_pausable: only at a reset point (no hop consumed since create / dfx_stream_reset)");
+    if (enable)
+        if (int rc = stream_gate_alloc(s, "dfx_stream_set_pausable")) return rc;
+    s->pausable = enable != 0;
     return DFX_OK;
 }
 
@@ -498,7 +563,38 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
     if (ys < 0) ys = n * hop;
     if (ls < 0) ls = n;
     int rc;
-    const bool gated = S->gated && S->gate_buf;
+    // per-stream state forms: gated handles, and pausable ones (there `silence` — the silent-input test and the stage decisions — may be off)
+    const bool silence = S->gated && S->gate_buf, gated = (S->gated || S->pausable) && S->gate_buf;
+    // pausable handles: this pass's paused rows are flagged behind dfx_k_gate_pre (bump: the hops by which the handle's count will advance)
+    auto pause_rows = [&](hipStream_t on, int bump) -> int {
+        if (!S->pausable || (silence && !S->any_paused)) return DFX_OK;
+        const int ch = S->channels;
+        const int64_t ns = B / ch;
+        for (int64_t k0 = 0; k0 < ns; k0 += DFX_PAUSE_STREAMS) {
+            DfxPauseMask P;
+            P.first = (int)k0, P.n = (int)(ns - k0 < DFX_PAUSE_STREAMS ? ns - k0 : DFX_PAUSE_STREAMS);
+            memset(P.bits, 0, sizeof(P.bits));
+            bool any = false;
+            if (S->any_paused)
+                for (int k = 0; k < P.n; ++k)
+                    if (S->paused[(size_t)(k0 + k)]) P.bits[k >> 5] |= 1u << (k & 31), any = true;
+            if (!any && silence) continue;
+            dfx_launch(dfx_k_stream_pause, dim3((unsigned)dfx_ceil_div((int64_t)P.n * ch, 256)), dim3(256), 0, on, P, ch, S->gate_buf + S->g_flags, (int)!silence,
+                       reinterpret_cast<int *>(S->gate_buf + S->g_counter),
+                       silence ? (const int *)reinterpret_cast<int *>(S->gate_buf + S->g_sh_counter) : (const int *)nullptr,
+                       reinterpret_cast<int64_t *>(S->buf + S->birth_dev), bump);
+            DFX_LAUNCH_CHECK();
+        }
+        return DFX_OK;
+    };
+    auto gate_pre = [&](hipStream_t on) -> int {   // the silent-input test of the pass (gated handles), then the rows that sit it out
+        if (silence) {
+            if (S->pausable && S->any_paused)
+                DFX_HIP(hipMemcpyAsync(S->gate_buf + S->g_sh_counter, S->gate_buf + S->g_counter, (size_t)B * 4, hipMemcpyDeviceToDevice, on));
+            if (int r = launch_gate_pre(x, xs, (int)hop, B, reinterpret_cast<int *>(S->gate_buf + S->g_counter), S->gate_buf + S->g_flags, S->channels, on)) return r;
+        }
+        return pause_rows(on, S->lim != 1.f ? 1 : 0);
+    };
     if (gated && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "gated streaming passes carry one hop");
     // ---- rolling spectra: linear (sliding window, see dfx_stream_state::spec_lin) or ring.  spec_window() brings the form this call uses
     // up to date with the other one if that one holds the state, appends the call's new frames and returns the window [Hs + n frames]
@@ -586,9 +682,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         // that switching the limit back mid-stream continues from the right history); features, network and synthesis do not run, the
         // hop is passed through undelayed with lsnr = 35 — unless the stream has been silent for more than 5 hops (zeros, -15).
         unsigned char *gflags = gated ? S->gate_buf + S->g_flags : nullptr;
-        if (gated) {
-            if ((rc = launch_gate_pre(x, xs, (int)hop, B, reinterpret_cast<int *>(S->gate_buf + S->g_counter), gflags, S->channels, s))) return rc;
-        }
+        if (gated && (rc = gate_pre(s))) return rc;
         float *am_in = fp(S->ana_mem[S->flip]), *am_out = fp(S->ana_mem[S->flip ^ 1]);
         float *new_spec = fp(S->new_spec);
         if ((rc = dfx_launch_analysis(st, x, B, n * hop, xs, am_in, am_out, new_spec, nullptr, s, -1, Fp))) return rc;
@@ -633,7 +727,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
     if (gated) {
         // silent-input shortcut (tract.rs:513-525) + a copy of the in-place state, so that the streams that turn out not to advance
         // (frozen, or a decoder stage skipped) can be given their state back after the pass
-        if ((rc = launch_gate_pre(x, xs, (int)hop, B, gcount, gflags, S->channels, s))) return rc;
+        if ((rc = gate_pre(s))) return rc;
         DFX_HIP(hipMemcpyAsync(gp(S->g_sh_erb), fp(S->erb_state), (size_t)B * E * 4, hipMemcpyDeviceToDevice, s));
         DFX_HIP(hipMemcpyAsync(gp(S->g_sh_unit), fp(S->unit_state), (size_t)B * Fd * 4, hipMemcpyDeviceToDevice, s));
         // (the GRU states: only when the layers run in place — the one-step kernel leaves the old states in the other buffer)
@@ -656,7 +750,8 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
     const int64_t skip = a0 < L ? ((L - a0) < n ? (L - a0) : n) : 0;
     // streams that started over on their own (dfx_stream_reset_streams): mixed — one of them is still younger than the window, the pass takes
     // t_zero per stream; warm — one of them is younger than the lookahead (the caller passes one hop at a time then): dfx_k_stream_warm
-    const bool mixed = skip < n && a0 < S->mixed_until, warm = mixed && a0 < S->warm_until;
+    // (pausable handles: decided per pass from the ages of the streams that take part — stream_process_impl)
+    const bool mixed = skip < n && (S->pausable ? S->p_mixed : a0 < S->mixed_until), warm = mixed && (S->pausable ? S->p_warm : a0 < S->warm_until);
     if (warm && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "warm-up hops of a reset stream are passed one at a time");
     float *work_fe = fp(S->work_fe), *work_fs = fp(S->work_fs), *work_spec = fp(S->work_spec);
     struct Ring { size_t *hist; float *nw, *work; int64_t h, row; bool zero_skipped; } rings[2] = {
@@ -765,6 +860,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
             gate.channels = S->channels;
             gate.flags = gflags;
             gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
+            if (!silence) gate.thr[0] = -INFINITY, gate.thr[1] = gate.thr[2] = INFINITY;   // pausable, not gated: every stage runs on every hop
             gate.c0_win = gp(S->g_c0_win);
             if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
             sc.gate = &gate;
@@ -819,7 +915,11 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
                 }
             }
             if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream warm-up: more state arrays than DFX_ROWS_MAX_ENTRIES");
-            dfx_launch(dfx_k_stream_warm, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount, B);
+            if (S->pausable)
+                dfx_launch(dfx_k_stream_warm_active, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount,
+                           (const unsigned char *)gflags, B);
+            else
+                dfx_launch(dfx_k_stream_warm, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount, B);
             DFX_LAUNCH_CHECK();
         }
     }
@@ -873,20 +973,59 @@ static int stream_call_end(const dfx_model *m, hipStream_t s) {
     return model_poll(m);
 }
 static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s);
-extern "C" int dfx_stream_process(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, void *stream) {
+extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, const unsigned char *active,
+                                         void *stream) {
     if (!S || n <= 0 || n > S->nmax || !x || !y) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process: bad arguments (1 <= n_frames <= max_frames)");
+    if (active && !S->pausable) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_active: a mask needs a pausable handle (dfx_stream_set_pausable)");
     if (int rc = dfx_require_device()) return rc;
     if (int rc = model_poll(S->m)) return rc;
     hipStream_t s = dfx_stream(stream);
+    S->any_paused = false;
+    if (S->pausable) {   // the mask of this call, on the host: it reaches the kernels as arguments (dfx_k_stream_pause)
+        const size_t ns = (size_t)(S->B / S->channels);
+        S->paused.assign(ns, 0);
+        for (size_t k = 0; active && k < ns; ++k)
+            if (!active[k]) S->paused[k] = 1, S->any_paused = true;
+    }
     {
         DfxTurn turn(S->m, s, false);   // (the enqueue lock only: a hop starts no persistent phase)
+        S->fresh = false;
         if (int rc = stream_process_impl(S, x, n, y, lsnr_out, s)) return rc;
     }
     return stream_call_end(S->m, s);
 }
+extern "C" int dfx_stream_process(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, void *stream) {
+    return dfx_stream_process_active(S, x, n, y, lsnr_out, nullptr, stream);
+}
 static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s) {
     const bool advances = S->lim != 1.f;  // the pass-through case (tract.rs:540-543) moves the STFT memory and the rolling spectra only
     const int64_t hop = S->st->hop;
+    if (S->pausable && S->gate_buf) {
+        // one hop per pass, like a gated handle.  Whether a pass takes the per-row t_zero (a stream younger than the window and than the
+        // handle) and the warm-up (younger than the lookahead) follows the ages of the streams that take part: a young stream that sits out
+        // keeps nobody in those forms.  After the pass the paused streams' births follow the handle's count (dfx_k_stream_pause did the same).
+        const int ch = S->channels;
+        const int64_t ns = S->B / ch, Hs = S->H + S->L;
+        for (int64_t i = 0; i < n; ++i) {
+            S->p_mixed = S->p_warm = false;
+            for (int64_t k = 0; k < ns; ++k) {
+                const int64_t born = S->birth[(size_t)(k * ch)], age = S->frames - born;
+                if (S->paused[(size_t)k] || born == 0 || age >= Hs) continue;
+                S->p_mixed = true;
+                if (age < S->L) S->p_warm = true;
+            }
+            if (int rc = stream_body(S, x + i * hop, 1, y + i * hop, lsnr_out ? lsnr_out + i : nullptr, s, n * hop, n * hop, n)) return rc;
+            if (advances) {
+                S->frames += 1;
+                if (S->any_paused)
+                    for (int64_t k = 0; k < ns; ++k)
+                        if (S->paused[(size_t)k])
+                            for (int c = 0; c < ch; ++c) S->birth[(size_t)(k * ch + c)] += 1;
+            }
+            S->flip ^= 1;
+        }
+        return DFX_OK;
+    }
     if (S->gated && S->gate_buf) {  // one hop per pass: the stage decisions of hop i shape the state hop i+1 starts from
         for (int64_t i = 0; i < n; ++i) {
             if (int rc = stream_body(S, x + i * hop, 1, y + i * hop, lsnr_out ? lsnr_out + i : nullptr, s, n * hop, n * hop, n)) return rc;
@@ -926,10 +1065,15 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
     if (!S->gated || !S->gate_buf) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_raw: switch gating on first (dfx_stream_set_gating)");
     if (S->frames < S->mixed_until)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_process_raw: a stream reset by dfx_stream_reset_streams is younger than the window (the raw path has one start for all streams)");
+    if (S->pausable)   // (a stream that sat calls out is younger than the handle in the same way)
+        for (int64_t k = 0; k < S->B; ++k)
+            if (S->birth[(size_t)k] != 0 && S->frames - S->birth[(size_t)k] < S->H + S->L)
+                DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_process_raw: a stream that was reset or paused is younger than the window (the raw path has one start for all streams)");
     if (int rc = dfx_require_device()) return rc;
     if (int rc = model_poll(S->m)) return rc;
     hipStream_t s = dfx_stream(stream);
     DfxTurn turn(S->m, s, false);   // (the enqueue lock)
+    S->fresh = false;
     const dfx_model *m = S->m;
     const dfx_state *st = S->st;
     const dfx_model_cfg &c = m->cfg;

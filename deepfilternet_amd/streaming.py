@@ -24,6 +24,14 @@ its own ``enhance(pad=False)`` delayed; one launch per GRU layer on a one-hop ca
 (``init_df(mask_only=True)``) streams without the DF stage: gated, it never takes stage 2, and ``process_raw`` reports gains only.
 
 ``rt.reset([3, 17])`` makes single streams start over (a new caller in a used slot) while all others run on; ``rt.frames`` are the per-stream ages in hops.
+
+``pausable=True`` lets single streams sit calls out: ``rt.process(hop, active=mask)`` with one bool per stream.  A stream whose entry is
+false is paused for that call — none of its state moves and its age stands still, its rows of the output are exact zeros and its lsnr
+NaN, and its next active hop is processed as if the paused calls had not happened (every caller keeps its own clock, as with one
+reference handle each).  Its input rows are still read and computed, then discarded: fill them with finite samples (zeros are fine).
+A pause is not silence: on a gated handle the stream's silent-input counter neither rises nor clears.  ``reset([i])`` followed by
+paused calls reserves a slot.  A paused row still costs its lane; a pausable handle runs one hop per pass in the per-stream state forms
+of a gated handle, so declare it only where it is needed.
 """
 from __future__ import annotations
 
@@ -40,7 +48,7 @@ from .model import DfNet
 class DfStream:
     def __init__(self, model: DfNet, df_state: DF, streams: int = 1, max_frames: int = 1, atten_lim_db: Optional[float] = None,
                  gating: bool = False, thresholds: Optional[Tuple[float, float, float]] = None, channels: int = 1,
-                 reduce_mask: str = "mean"):
+                 reduce_mask: str = "mean", pausable: bool = False):
         if not isinstance(model, DfNet):
             raise TypeError("DfStream needs a deepfilternet_amd.DfNet (see init_df)")
         h = C.c_void_p()
@@ -57,6 +65,8 @@ class DfStream:
             self.set_thresholds(*thresholds)
         if gating:
             self.set_gating(True)
+        if pausable:
+            _lib.check(_lib.lib().dfx_stream_set_pausable(self._h, 1))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -108,14 +118,26 @@ class DfStream:
 
     @property
     def frames(self) -> torch.Tensor:
-        """Hops of network time every stream has consumed since its own last reset: CPU int64 [streams / channels]."""
+        """Hops of network time every stream has consumed since its own last reset (calls it sat out do not count): CPU int64 [streams / channels]."""
         out = torch.zeros(self.streams // self.channels, dtype=torch.int64)
         _lib.check(_lib.lib().dfx_stream_frames(self._h, C.cast(out.data_ptr(), C.POINTER(C.c_int64))))
         return out
 
-    def process(self, frames: torch.Tensor, return_lsnr: bool = False):
+    def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None):
         """df_process_frame (capi.rs:161) for every stream: ``frames`` [streams, n*hop] float32 -> enhanced [streams, n*hop]
-        (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB."""
+        (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB.
+
+        ``active`` (pausable handles): a sequence or tensor of bools or integers, one per stream (``streams // channels``); a stream whose
+        entry is false is paused for all hops of this call (zeros out, lsnr NaN, no state moves; its input rows must still be finite).
+        ``None`` = all streams take part.  The mask is read on the host: a device tensor is copied there first, which waits for the device."""
+        mask = None
+        if active is not None:
+            mask = torch.as_tensor(active).reshape(-1)
+            if mask.is_floating_point() or mask.is_complex():
+                raise TypeError("active must hold bools or integers")
+            if mask.numel() != self.streams // self.channels:
+                raise ValueError(f"active must have one entry per stream ({self.streams // self.channels})")
+            mask = (mask.to("cpu") != 0).to(torch.uint8).contiguous()
         src_dev = frames.device
         x = frames.to(_lib.device(), torch.float32).contiguous()
         hop = self.frame_length
@@ -126,7 +148,11 @@ class DfStream:
             raise ValueError(f"at most max_frames={self.max_frames} hops per call")
         y = torch.empty_like(x)
         lsnr = torch.empty((self.streams, n), dtype=torch.float32, device=x.device) if return_lsnr else None
-        _lib.check(_lib.lib().dfx_stream_process(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr), _lib.stream()))
+        if mask is None:
+            _lib.check(_lib.lib().dfx_stream_process(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr), _lib.stream()))
+        else:
+            _lib.check(_lib.lib().dfx_stream_process_active(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr), C.c_void_p(mask.data_ptr()),
+                                                            _lib.stream()))
         y = y.to(src_dev)
         self._model.poll()   # faults raised by kernels (invalid results) are never silent: see DfNet.poll
         return (y, lsnr.to(src_dev)) if return_lsnr else y

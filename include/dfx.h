@@ -308,6 +308,18 @@ int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int1
  *   window of history + lookahead hops.  A refused call does not advance the handle, so on a handle that is driven through the raw
  *   entry point alone the refusal lasts until dfx_stream_process has carried the handle past that window or dfx_stream_reset has
  *   reset all of it: do not reset single streams of such a handle.
+ *   Paused streams (dfx_stream_set_pausable, dfx_stream_process_active): a call on a pausable handle may carry a mask of the streams that
+ *   take part; a stream that does not is paused for the n hops of the call.  Nothing of a paused stream moves — STFT memories, running
+ *   means, feature and spectrum windows, GRU states, df_convp's delay line, the silent-input counter and stage flags of a gated handle, its
+ *   age (dfx_stream_frames) — so its next active hop is processed as if the paused calls had not happened: every caller keeps its own
+ *   clock, as with one df_process_frame handle each.  Its rows of x are still read and computed like any row and the results discarded:
+ *   they must hold finite, ordinary samples (zeros are fine).  Its rows of y are exact zeros, its lsnr entries NaN (no estimate was made).
+ *   With `channels` rows per stream the mask has one entry per stream.  A pause is not silence: a gated handle takes no stage decision for
+ *   the stream and its silent-input counter neither rises nor clears.  dfx_stream_reset_streams followed by paused calls is a reserved
+ *   slot: the stream starts, `lookahead` silent hops included, with its first active hop.  A paused row still costs its lane in every
+ *   kernel.  A pausable handle keeps its state in the per-stream forms of a gated handle from its first hop and runs one hop per pass
+ *   (without gating every stage runs on every hop); a handle that is not pausable enqueues exactly what it did before.  The mask is a host
+ *   array and travels to the device as kernel arguments (4096 streams per launch): no upload, and the call never waits for the device.
  *   Engine configurations: every model the batch path serves with a fused DF encoder streams, in either arithmetic and with the DF stage on
  *   or off; refused (DFX_ERR_UNSUPPORTED) are conv_lookahead != df_lookahead and df_pathway_kernel_size_t > 5 or df_order > 8.  A handle
  *   on a DFX_EXACT_FP32=1 model runs every contraction in fp32, like that model's batch path, and equals it delayed: a one-hop call steps
@@ -338,6 +350,12 @@ int dfx_stream_set_gating(dfx_stream_state *s, int enable);              /* DfTr
 int dfx_stream_set_thresholds(dfx_stream_state *s, float min_db_thresh, float max_db_erb_thresh,
                               float max_db_df_thresh);                   /* RuntimeParams::with_thresholds (tract.rs:160-170) */
 int dfx_stream_process(dfx_stream_state *s, const float *x, int64_t n_frames, float *y, float *lsnr, void *stream);
+/* Accepted only at a reset point (no hop consumed since create / dfx_stream_reset); else DFX_ERR_INVALID_ARG. */
+int dfx_stream_set_pausable(dfx_stream_state *s, int enable);
+/* dfx_stream_process with a mask: active = HOST array [streams / channels], nonzero = the stream takes part; NULL = all.
+ * A mask (non-NULL) on a handle that is not pausable: DFX_ERR_INVALID_ARG. */
+int dfx_stream_process_active(dfx_stream_state *s, const float *x, int64_t n_frames, float *y, float *lsnr,
+                              const unsigned char *active, void *stream);
 /* DfTract::process_raw (tract.rs:441-507) == df_process_frame_raw (capi.rs:172-210) for every stream: one spectral frame
  * spec [streams, F][2] in, the pass's raw ERB gains [streams, nb_erb] and deep-filter coefficients [streams, df_order, nb_df][2] out,
  * stages [streams] saying which of them exist (bit value 2: gains — the network's mask, or zeros below min_db_thresh; 8: coefficients;

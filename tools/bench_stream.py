@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
-    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact]
+    python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact] [--paused FRACTION]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
+--paused FRACTION: a pausable handle (DfStream(pausable=True)); every call pauses that share of the streams, a block that rotates through
+the pool (0: a pausable handle on which nobody pauses).
 --exact: the model is created under DFX_EXACT_FP32=1 (every contraction in fp32: the one-hop GRU layers on dfx_k_gru_step_x32).
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
@@ -30,6 +32,8 @@ def main() -> None:
                     help="df3_ll: DeepFilterNet3 without lookahead (the reference's low-latency LADSPA model, ladspa/README.md:3)")
     ap.add_argument("--gating", action="store_true", help="per-stream stage gating + silent-input shortcut (tract.rs:513-525,658-672)")
     ap.add_argument("--churn", type=int, default=0, help="reset this many streams before every call, rotating through the pool")
+    ap.add_argument("--paused", type=float, default=None, metavar="FRACTION",
+                    help="pausable handle; this share of the streams (a rotating block) sits every call out")
     ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
     if args.exact:
@@ -47,7 +51,7 @@ def main() -> None:
     exact = bool(model.query(model.Q_EXACT_FP32))
     dev = _lib.device()
     for n in args.frames_per_call:
-        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating)
+        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None)
         hop = rt.frame_length
         x = 0.1 * torch.randn((args.streams, n * hop), device=dev)
         nslots, churn_pos = args.streams, 0
@@ -58,15 +62,27 @@ def main() -> None:
                 rt.reset([(churn_pos + k) % nslots for k in range(args.churn)])
                 churn_pos = (churn_pos + args.churn) % nslots
 
+        n_paused, pause_pos = int(round((args.paused or 0.0) * args.streams)), 0
+
+        def mask():   # the next block of the pool sits this call out (a host array: the mask travels as kernel arguments)
+            nonlocal pause_pos
+            if args.paused is None:
+                return None
+            m = torch.ones(args.streams, dtype=torch.bool)
+            idx = (pause_pos + torch.arange(n_paused)) % nslots
+            m[idx] = False
+            pause_pos = (pause_pos + n_paused) % nslots
+            return m
+
         for _ in range(10):
             churn()
-            rt.process(x)
+            rt.process(x, active=mask())
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         dev_sync = int(os.environ.get("DFX_BENCH_DEV_SYNC", "0"))   # dev: the host waits after every n-th call (enqueue depth experiment)
         for i in range(args.calls):
             churn()
-            y = rt.process(x)
+            y = rt.process(x, active=mask())
             if dev_sync and (i + 1) % dev_sync == 0:
                 torch.cuda.synchronize()
         torch.cuda.synchronize()
@@ -75,14 +91,14 @@ def main() -> None:
         # host cost of a call: 32 calls enqueued into empty queues, no wait in between (what bounds the rate on a box with a slow host)
         t1 = time.perf_counter()
         for i in range(32):
-            y = rt.process(x)
+            y = rt.process(x, active=mask())
         host_ms = (time.perf_counter() - t1) / 32 * 1e3
         torch.cuda.synchronize()
         hops = args.streams * n * args.calls
         ms_call = dt / args.calls * 1e3
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
-                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "exact_fp32": exact,
+                          "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "paused": args.paused, "exact_fp32": exact,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         del rt
 
