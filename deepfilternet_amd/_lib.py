@@ -117,6 +117,10 @@ SIGNATURES = {
     "dfx_stream_set_channels": (_i, [_vp, _i, _i]),
     "dfx_stream_set_gating": (_i, [_vp, _i]),
     "dfx_stream_set_thresholds": (_i, [_vp, _f, _f, _f]),
+    "dfx_stream_set_atten_lim_streams": (_i, [_vp, C.POINTER(_i64), _i64, C.POINTER(_f), _vp]),
+    "dfx_stream_set_post_filter_beta_streams": (_i, [_vp, C.POINTER(_i64), _i64, C.POINTER(_f), _vp]),
+    "dfx_stream_set_thresholds_streams": (_i, [_vp, C.POINTER(_i64), _i64, C.POINTER(_f), _vp]),
+    "dfx_stream_get_settings": (_i, [_vp, C.POINTER(_f)]),
     "dfx_stream_process": (_i, [_vp, _fp, _i64, _fp, _fp, _vp]),
     "dfx_stream_set_pausable": (_i, [_vp, _i]),
     "dfx_stream_process_active": (_i, [_vp, _fp, _i64, _fp, _fp, _vp, _vp]),

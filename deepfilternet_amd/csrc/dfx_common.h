@@ -139,4 +139,6 @@ int dfx_launch_df_apply(const float *spec, const float *coefs, int coef_layout, 
                         int64_t T, int F, int nb_df, int order, int lookahead, float pf_beta, float atten_lim, float *out, hipStream_t s,
                         int64_t t_begin = 0, int64_t t_end = -1, int64_t coef_T = -1, int64_t out_T = -1, int64_t out_toff = 0,
                         int64_t spec_stride = 0, int64_t out_stride = 0,
-                        int pf_rs_channels = 0);  // > 0: the real-time runtime's post filter (lib.rs:446-471) over frames of that many rows
+                        int pf_rs_channels = 0,   // > 0: the real-time runtime's post filter (lib.rs:446-471) over frames of that many rows
+                        const float *lim_rows = nullptr,    // non-null: device [B], clip b's own atten_lim / pf_beta in place of the scalars
+                        const float *beta_rows = nullptr);  //   (the streaming runtime's per-stream settings, dfx_stream_set_*_streams)

@@ -730,10 +730,10 @@ int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t 
 // out_T / out_toff: compacted output rows (default T / 0); spec_stride / out_stride: row strides in complex elements (0: F).
 // Rows that are 16-byte aligned (even strides: the engine's own padded spec buffers) take the row-streaming kernel
 // dfx_k_df_apply_rows; dense rows of an odd F (the public dfx_df_apply on [B,T,F] arrays) the flat-stream kernel dfx_k_df_apply.
-template <int NPC, bool PF>
+template <int NPC, bool PF, bool PR = false>
 static int launch_dfa_rows(const DfxDfrArgs &A, int order, unsigned grid, hipStream_t s) {
     switch (order) {
-#define DFX_DFR_CASE(O_) case O_: dfx_launch((dfx_k_df_apply_rows<O_, NPC, PF>), dim3(grid), dim3(256), 0, s, A); break;
+#define DFX_DFR_CASE(O_) case O_: dfx_launch((dfx_k_df_apply_rows<O_, NPC, PF, 7, PR>), dim3(grid), dim3(256), 0, s, A); break;
         DFX_DFR_CASE(1) DFX_DFR_CASE(2) DFX_DFR_CASE(3) DFX_DFR_CASE(4) DFX_DFR_CASE(5) DFX_DFR_CASE(6) DFX_DFR_CASE(7) DFX_DFR_CASE(8)
         DFX_DFR_CASE(9) DFX_DFR_CASE(10) DFX_DFR_CASE(11) DFX_DFR_CASE(12) DFX_DFR_CASE(13) DFX_DFR_CASE(14) DFX_DFR_CASE(15) DFX_DFR_CASE(16)
 #undef DFX_DFR_CASE
@@ -746,7 +746,8 @@ static int launch_dfa_rows(const DfxDfrArgs &A, int order, unsigned grid, hipStr
 int dfx_launch_df_apply(const float *spec, const float *coefs, int coef_layout, const float *gains,
                         const dfx_bands *bands, int64_t B, int64_t T, int F, int nb_df, int order, int lookahead,
                         float pf_beta, float atten_lim, float *out, hipStream_t s, int64_t t_begin, int64_t t_end, int64_t coef_T,
-                        int64_t out_T, int64_t out_toff, int64_t spec_stride, int64_t out_stride, int pf_rs_channels) {
+                        int64_t out_T, int64_t out_toff, int64_t spec_stride, int64_t out_stride, int pf_rs_channels,
+                        const float *lim_rows, const float *beta_rows) {
     if (spec_stride <= 0) spec_stride = F;
     if (out_stride <= 0) out_stride = F;
     if (t_end < 0) t_end = T;
@@ -779,6 +780,7 @@ int dfx_launch_df_apply(const float *spec, const float *coefs, int coef_layout, 
             R.pf_beta = pf_beta;
             R.atten_lim = atten_lim;
             R.pf_ch = pf_rs_channels > 0 ? pf_rs_channels : 0;
+            R.lim_rows = lim_rows, R.beta_rows = beta_rows;
             R.t_begin = (int)t_begin;
             R.t_end = (int)t_end;
             R.rpw = 1;   // one frame per wave measured fastest (6.2 TB/s vs 5.9 at 4 and 5.4 at 16: the O-1 extra rows a wave reads are L2 hits)
@@ -795,6 +797,8 @@ int dfx_launch_df_apply(const float *spec, const float *coefs, int coef_layout, 
             if (nblk > 0x7fffffff) DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_df_apply: batch too large for one launch");
             const int np = ((F + 1) / 2 + 63) / 64;
             DfxKScope ks(DFX_K_DF_APPLY, s);
+            if (lim_rows || beta_rows)   // per-row settings: the instance that can apply them, whatever the scalars say
+                return np == 4 ? launch_dfa_rows<4, true, true>(R, order, (unsigned)nblk, s) : launch_dfa_rows<0, true, true>(R, order, (unsigned)nblk, s);
             const bool pf = pf_beta > 0.f || atten_lim > 0.f;
             if (np == 4) return pf ? launch_dfa_rows<4, true>(R, order, (unsigned)nblk, s) : launch_dfa_rows<4, false>(R, order, (unsigned)nblk, s);
             return pf ? launch_dfa_rows<0, true>(R, order, (unsigned)nblk, s) : launch_dfa_rows<0, false>(R, order, (unsigned)nblk, s);
@@ -832,6 +836,7 @@ int dfx_launch_df_apply(const float *spec, const float *coefs, int coef_layout, 
     A.pf_beta = pf_beta;
     A.atten_lim = atten_lim;
     A.pf_ch = pf_rs_channels > 0 ? pf_rs_channels : 0;
+    A.lim_rows = lim_rows, A.beta_rows = beta_rows;
     const int ROWS = DFX_DFA_ROWS;
     A.t_begin = (int)t_begin;
     A.t_end = (int)t_end;

@@ -1651,6 +1651,9 @@ struct DfxDfaArgs {
     // chunks_exact(4) walk over the frame's [pf_ch * F] bins (the pf_ch rows of a stream are consecutive clips): the last
     // (pf_ch * F) % 4 bins of the flattened frame are NOT filtered (mono, F = 481: bin 480).  0: deepfilternet3.py:448-454.
     int pf_ch = 0;
+    // per-stream settings of the streaming runtime (dfx_stream_set_*_streams): non-null = clip b takes lim_rows[b] / beta_rows[b] in place
+    // of atten_lim / pf_beta (one uniform load each per workgroup)
+    const float *lim_rows = nullptr, *beta_rows = nullptr;
 };
 
 // lib.rs:446-471 post_filter, one bin: g = min(|e| / (|n| + eps), 1).max(eps); g_sin = g * sin(g * pi / 2);
@@ -1690,7 +1693,7 @@ static __device__ __forceinline__ float2 dfx_dfa_finish(float2 y, float2 x, floa
 // t0-toff .. of this chunk staged in LDS (zeros outside the clip); gs / b2b: the chunk's gains and the bin->band map in LDS.
 static __device__ __forceinline__ float2 dfx_dfa_bin(const DfxDfaArgs &A, const float2 *xs, const float *gs,
                                                      const unsigned char *b2b, const float2 *coef_b, int t0, int t, int f,
-                                                     float2 x, int ch_off = 0) {
+                                                     float2 x, int ch_off, float pf_beta, float atten_lim) {
     float2 y;
     if (f < A.nbdf) {
         float re = 0.f, im = 0.f;
@@ -1710,10 +1713,10 @@ static __device__ __forceinline__ float2 dfx_dfa_bin(const DfxDfaArgs &A, const 
         y = x;
     }
     if (A.pf_ch > 0) {   // the runtime's post filter: Rust arithmetic, the tail of the flattened [pf_ch * F] frame left alone
-        if (A.pf_beta > 0.f && ch_off + f < ((A.pf_ch * A.F) & ~3)) y = dfx_dfa_post_filter_rs(y, x, A.pf_beta);
-        return dfx_dfa_finish(y, x, 0.f, A.atten_lim);
+        if (pf_beta > 0.f && ch_off + f < ((A.pf_ch * A.F) & ~3)) y = dfx_dfa_post_filter_rs(y, x, pf_beta);
+        return dfx_dfa_finish(y, x, 0.f, atten_lim);
     }
-    return dfx_dfa_finish(y, x, A.pf_beta, A.atten_lim);
+    return dfx_dfa_finish(y, x, pf_beta, atten_lim);
 }
 
 template <int ROWS>
@@ -1728,6 +1731,7 @@ __global__ void __launch_bounds__(DFX_DFA_THREADS) dfx_k_df_apply(DfxDfaArgs A) 
     if (b >= A.B) return;
     const int F = A.F, nd = A.nbdf;
     const int ch_off = A.pf_ch > 0 ? (int)(b % A.pf_ch) * F : 0;   // position of this row's bin 0 in its stream's flattened frame
+    const float pf_beta = A.beta_rows ? A.beta_rows[b] : A.pf_beta, atten_lim = A.lim_rows ? A.lim_rows[b] : A.atten_lim;   // (b is workgroup-uniform)
     const int t0 = A.t_begin + chunk * ROWS;
     const int nt = (A.t_end - t0) < ROWS ? (A.t_end - t0) : ROWS;
     const int halo = ROWS + A.order - 1;
@@ -1767,12 +1771,12 @@ __global__ void __launch_bounds__(DFX_DFA_THREADS) dfx_k_df_apply(DfxDfaArgs A) 
     for (int e = e0 + tid; e < a0; e += DFX_DFA_THREADS) {
         const int t = e / F, f = e - t * F;
         const float2 x = (f < nd) ? xs[(t - t0 + toff) * nd + f] : spec_b[e];
-        out_b[e] = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, t, f, x, ch_off);
+        out_b[e] = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, t, f, x, ch_off, pf_beta, atten_lim);
     }
     for (int e = a1 + tid; e < e1; e += DFX_DFA_THREADS) {
         const int t = e / F, f = e - t * F;
         const float2 x = (f < nd) ? xs[(t - t0 + toff) * nd + f] : spec_b[e];
-        out_b[e] = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, t, f, x, ch_off);
+        out_b[e] = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, t, f, x, ch_off, pf_beta, atten_lim);
     }
     const float4 *x4 = reinterpret_cast<const float4 *>(spec_b + a0);
     float4 *y4 = reinterpret_cast<float4 *>(out_b + a0);
@@ -1806,8 +1810,8 @@ __global__ void __launch_bounds__(DFX_DFA_THREADS) dfx_k_df_apply(DfxDfaArgs A) 
                 const float2 xa = xs[(tt[u] - t0 + toff) * nd + ff[u]], xb = xs[(tt[u] - t0 + toff) * nd + ff2[u]];
                 xv[u] = make_float4(xa.x, xa.y, xb.x, xb.y);
             }
-            const float2 ya = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, tt[u], ff[u], make_float2(xv[u].x, xv[u].y), ch_off);
-            const float2 yb = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, tt2[u], ff2[u], make_float2(xv[u].z, xv[u].w), ch_off);
+            const float2 ya = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, tt[u], ff[u], make_float2(xv[u].x, xv[u].y), ch_off, pf_beta, atten_lim);
+            const float2 yb = dfx_dfa_bin(A, xs, gs, b2b, coef_b, t0, tt2[u], ff2[u], make_float2(xv[u].z, xv[u].w), ch_off, pf_beta, atten_lim);
             y4[u ? i2 : i] = make_float4(ya.x, ya.y, yb.x, yb.y);
         }
     }
@@ -1845,6 +1849,7 @@ struct DfxDfrArgs {
     int chunks;           // chunks of rpw frames per clip
     int64_t items;        // work items = ceil(B / 8) * 8 * ceil(chunks / 4)
     int pf_ch = 0;        // > 0: the real-time runtime's post filter (see DfxDfaArgs::pf_ch): pf_ch consecutive clips are the channels of one stream
+    const float *lim_rows = nullptr, *beta_rows = nullptr;   // per-stream settings (see DfxDfaArgs): clip b's own atten_lim / pf_beta; read by the PR instances only
 };
 // A pass of enhance() whose kernels raised a fault (err[1]: fp16-split range, err[2]: a flag wait timed out and its workgroup ran on without its data)
 // must not hand back plausible samples: the finishing kernel looks at the words when it starts — every fault that can reach its inputs has been
@@ -1860,7 +1865,9 @@ __global__ void dfx_k_fault_mirror(const unsigned int *err, unsigned int *poison
 // then issued together and the band indices live in registers); NPC == 0: any F, one pass at a time.  PF: post filter / attenuation
 // limit compiled in (the common case, neither, then carries no sinf / sqrtf code and fewer live registers).
 // Addressing: everything but the lane index is wave-uniform (clip, frame, tap), so every access is <scalar base> + lane * 16.
-template <int O, int NPC, bool PF, int NT = 7>   // NT bit 0: non-temporal spec loads, bit 1: non-temporal stores, bit 2: non-temporal coefficient loads
+// PR (with PF): the clip's own attenuation limit / post-filter beta from A.lim_rows / A.beta_rows (the streaming runtime's per-stream settings); an
+// instance of its own, so that the instances every other caller runs keep their code and their register counts.
+template <int O, int NPC, bool PF, int NT = 7, bool PR = false>   // NT bit 0: non-temporal spec loads, bit 1: non-temporal stores, bit 2: non-temporal coefficient loads
 __global__ void __launch_bounds__(256) dfx_k_df_apply_rows(DfxDfrArgs A) {
     auto ld = [](const f32x4 *p) -> f32x4 { return (NT & 1) ? DFX_NT_LOAD(p) : *p; };
     auto ldc = [](const f32x4 *p) -> f32x4 { return (NT & 4) ? DFX_NT_LOAD(p) : *p; };
@@ -1904,16 +1911,25 @@ __global__ void __launch_bounds__(256) dfx_k_df_apply_rows(DfxDfrArgs A) {
     // (pf_ch > 0: libDF's post filter — Rust arithmetic, and the last (pf_ch * F) % 4 bins of the stream's flattened [pf_ch * F] frame are
     // left alone, lib.rs:446-471 — then the attenuation limit; see dfx_dfa_bin)
     const int pf_lim4 = (A.pf_ch * F) & ~3, ch_off = A.pf_ch > 0 ? (int)(b % A.pf_ch) * F : 0;
+    // the clip's own settings where the handle keeps them per stream: two scalar loads per wave and item, in front of the frame loop (the
+    // clip index is wave-uniform but comes out of a 64-bit division on the VALU: said again, so that the values stay in SGPRs like the
+    // kernel arguments they stand in for; B < 2^31: the grid)
+    float pf_beta = A.pf_beta, atten_lim = A.atten_lim;
+    if (PF && PR) {
+        const int bu = dfx_wave_uniform((int)b);
+        if (A.beta_rows) pf_beta = A.beta_rows[bu];
+        if (A.lim_rows) atten_lim = A.lim_rows[bu];
+    }
     auto finish2 = [&](f32x4 y, f32x4 x, bool second_is_pad, int f0) -> f32x4 {
         if (PF) {
             float2 ya = make_float2(y[0], y[1]), yb = make_float2(y[2], y[3]);
             const float2 xa = make_float2(x[0], x[1]), xb = make_float2(x[2], x[3]);
             if (A.pf_ch > 0) {
-                if (A.pf_beta > 0.f && ch_off + f0 < pf_lim4) ya = dfx_dfa_post_filter_rs(ya, xa, A.pf_beta);
-                if (A.pf_beta > 0.f && ch_off + f0 + 1 < pf_lim4) yb = dfx_dfa_post_filter_rs(yb, xb, A.pf_beta);
-                ya = dfx_dfa_finish(ya, xa, 0.f, A.atten_lim), yb = dfx_dfa_finish(yb, xb, 0.f, A.atten_lim);
+                if (pf_beta > 0.f && ch_off + f0 < pf_lim4) ya = dfx_dfa_post_filter_rs(ya, xa, pf_beta);
+                if (pf_beta > 0.f && ch_off + f0 + 1 < pf_lim4) yb = dfx_dfa_post_filter_rs(yb, xb, pf_beta);
+                ya = dfx_dfa_finish(ya, xa, 0.f, atten_lim), yb = dfx_dfa_finish(yb, xb, 0.f, atten_lim);
             } else {
-                ya = dfx_dfa_finish(ya, xa, A.pf_beta, A.atten_lim), yb = dfx_dfa_finish(yb, xb, A.pf_beta, A.atten_lim);
+                ya = dfx_dfa_finish(ya, xa, pf_beta, atten_lim), yb = dfx_dfa_finish(yb, xb, pf_beta, atten_lim);
             }
             y[0] = ya.x, y[1] = ya.y, y[2] = yb.x, y[3] = yb.y;
         }

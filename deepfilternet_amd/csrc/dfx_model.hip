@@ -154,6 +154,7 @@ struct DfxStreamCtx {
     std::function<int(hipStream_t)> df_post;  // set: state updates that nothing before the final deep filter reads — enqueued behind df_convp on
                                               //   its stream (joined through EV_C0P before df_out), or with df_pre when that kernel does not run
     float pf_beta;     // < 0: the model's setting
+    const float *lim_rows = nullptr, *beta_rows = nullptr;   // non-null: per-stream attenuation limit (linear) / post-filter beta [B] in place of the scalars
     float *out;        // [B, out_T, F][2]: local frame t of clip b is stored at frame t - out_toff
     int64_t out_T, out_toff;
     const struct DfxGate *gate = nullptr;  // per-stream stage gating (one new frame per pass); null: every frame runs every stage
@@ -174,6 +175,7 @@ enum { DFX_GATE_FROZEN = 1, DFX_GATE_GAINS = 2, DFX_GATE_ZEROS = 4, DFX_GATE_DF 
 struct DfxGate {
     unsigned char *flags;  // [B]
     float thr[3];          // min_db_thresh, max_db_erb_thresh, max_db_df_thresh
+    const float *thr_rows = nullptr;   // non-null: the same three per row [B][3] (per-stream thresholds: the rows of a stream hold the stream's entry)
     float *c0_win;         // [B, T, Fd, C]: slots T-kt .. T-2 = c0 of the last kt-1 frames the DF decoder ran on, T-1 = this frame
     void *pend2 = nullptr;           // fp16-split models: df_convp's pending sums instead, twice per stream (dfx_k_df_convp_step), with
     unsigned char *par = nullptr;    //   the half that is current and
@@ -269,13 +271,19 @@ static int launch_gate_pre(const float *x, int64_t x_stride, int hop, int64_t B,
 
 // tract.rs:658-672 apply_stages on the newest frame's lsnr (lsnr[b*T + T-1])
 // (multi-channel: the decision of a group is taken from its first channel's lsnr, tract.rs:468 `to_scalar`)
+// thr_rows: per-stream thresholds [B][3] in place of the three scalars (a finite thr_df only: a mask-only model passes -inf and has no stage 2)
 __global__ void dfx_k_gate_post(const float *lsnr, int64_t T, float thr_min, float thr_erb, float thr_df, unsigned char *flags,
-                                int64_t B, int ch) {
+                                int64_t B, int ch, const float *thr_rows) {
     const int64_t b = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (b >= B) return;
     unsigned char f = flags[b];
     if (f & DFX_GATE_FROZEN) return;
     const float v = lsnr[(b - b % ch) * T + T - 1];
+    if (thr_rows) {
+        const float *tr = thr_rows + (b - b % ch) * 3;
+        thr_min = tr[0], thr_erb = tr[1];
+        if (thr_df != -INFINITY) thr_df = tr[2];
+    }
     if (v < thr_min) f |= DFX_GATE_ZEROS;
     else if (v > thr_erb) f |= 0;
     else if (v > thr_df) f |= DFX_GATE_GAINS;

@@ -409,7 +409,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         if (gate) {  // stage decisions of the newest frame (tract.rs:658-672)
             // (a mask-only model has no stage 2: no stream is ever flagged for it, so its DF decoder's state and delay line never move)
             dfx_launch(dfx_k_gate_post, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const float *)lsnr, T, gate->thr[0],
-                       gate->thr[1], run_df ? gate->thr[2] : -INFINITY, gate->flags, B, gate->channels);
+                       gate->thr[1], run_df ? gate->thr[2] : -INFINITY, gate->flags, B, gate->channels, gate->thr_rows);
             DFX_LAUNCH_CHECK();
         }
         // ---- DfDecoder on x1 (:323-331)
@@ -959,7 +959,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         // chunks_exact(4) walk over the stream's flattened [channels * F] frame
         return dfx_launch_df_apply(spec, coefs, DFX_COEF_BOTF, mask, bands, B, sc->spec_T, c.fft_size / 2 + 1, run_df ? Fd : 0, O, c.df_lookahead, beta,
                                    atten_lim, sc->out, s, t_begin, T, T, sc->out_T, sc->out_toff, sc->spec_stride, sc->spec_stride,
-                                   sc->channels > 0 ? sc->channels : 1);
+                                   sc->channels > 0 ? sc->channels : 1, sc->lim_rows, sc->beta_rows);
     }
     // enhance(): the deep filter + gains are applied on the way into the inverse transform (dfx_k_synthesis_rows): spec_e never exists.
     // Where the transform cannot take them (dfx_synthesis_rows_ok) and without a transform: dfx_k_df_apply_rows -> spec_e -> dfx_k_synthesis (the

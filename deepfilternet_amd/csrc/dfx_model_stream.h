@@ -152,6 +152,29 @@ __global__ void __launch_bounds__(256) dfx_k_stream_pause(DfxPauseMask P, int ch
     }
 }
 
+// ---- settings that belong to one stream of a handle (dfx_stream_set_*_streams) ------------------------------------------------------------
+// The ids and their values travel as kernel arguments, like DfxRowIds (no upload, no wait).  DFX_SET_IDS ids per launch: with three values
+// per id (the thresholds) the argument block is 4 + 192 * 4 + 192 * 12 = 3076 bytes, inside the 4 KB a launch can carry.
+// One thread per row of the named streams: dst[row][0..W) = the stream's W values (row = id * ch + channel).  The host has resolved
+// duplicate ids (one entry per stream, the last occurrence's values), so no two threads write one row.
+#define DFX_SET_IDS 192
+template <int W>
+struct DfxRowVals {
+    int n;
+    int id[DFX_SET_IDS];
+    float v[DFX_SET_IDS * W];
+};
+template <int W>
+__global__ void __launch_bounds__(256) dfx_k_stream_set_rows(DfxRowVals<W> V, int ch, float *dst, int64_t B) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i >= V.n * ch) return;
+    const int k = i / ch;
+    const int64_t row = (int64_t)V.id[k] * ch + i % ch;
+    if (row >= B) return;
+#pragma unroll
+    for (int j = 0; j < W; ++j) dst[row * W + j] = V.v[k * W + j];
+}
+
 // ------------------------------------------------------------------------------------------------ streaming (dfx_stream_*)
 // Frame loop of DfTract::process (tract.rs:509-642) for many lockstep streams: every call runs the batch kernels on a window of
 // H history + n new frames per stream (DfxStreamCtx), with all recurrent state carried in the handle.
@@ -214,6 +237,16 @@ struct dfx_stream_state {
     std::vector<unsigned char> paused;   // [B / channels], this call: 1 = sits out
     bool any_paused = false;
     bool p_mixed = false, p_warm = false;   // this pass (stream_process_impl)
+    // Settings per stream (dfx_stream_set_*_streams): in the reference the attenuation limit, the post-filter beta and the thresholds belong to
+    // one DfTract, i.e. to one caller (capi.rs:136-156, tract.rs:160-170).  The host keeps every row's values (what dfx_stream_get_settings
+    // reports; the handle-wide setters write all rows); the device arrays — own allocation, made by the first per-stream setter — are read by
+    // the finishing kernel (lim, beta) and dfx_k_gate_post (thr) only while the handle is per-row in that setting (*_rows).  A handle-wide
+    // setter makes the handle uniform in its setting again: passes then take the scalars above, as on a handle that never was per-row, and
+    // the device array of that setting is stale until the next per-stream setter refills it.
+    std::vector<float> row_lim_db, row_beta, row_thr;   // [B] |dB| (100 = off), [B] beta (resolved: the model's where none was set), [B][3]
+    bool lim_rows = false, beta_rows = false, thr_rows = false;
+    unsigned char *set_buf = nullptr;   // float lim [B] (linear), beta [B], thr [B][3]
+    size_t sb_lim = 0, sb_beta = 0, sb_thr = 0;
     // (Replaying a steady-state call from a hipGraph was built in round 1 and removed in round 4: on ROCm 7.2 the replay of the hop's kernel nodes
     // took 2.0-2.2 ms per call where plain launches take 0.4.)
 };
@@ -307,6 +340,11 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     s->birth_dev = take((size_t)B * 8);
     s->tz_rows = take((size_t)B * 4);
     s->birth.assign((size_t)B, 0);
+    s->row_lim_db.assign((size_t)B, 100.f);
+    s->row_beta.assign((size_t)B, c.mask_pf ? c.pf_beta : 0.f);
+    s->row_thr.resize((size_t)B * 3);
+    for (int64_t b = 0; b < B; ++b)
+        for (int j = 0; j < 3; ++j) s->row_thr[(size_t)b * 3 + j] = s->thr[j];
     dfx_model_workspace_bytes(m, B, H + n, &s->model_ws_bytes);
     s->model_ws = take((size_t)s->model_ws_bytes);
     s->bytes = off;
@@ -326,6 +364,7 @@ extern "C" void dfx_stream_free(dfx_stream_state *s) {
     if (!s) return;
     if (s->buf) (void)hipFree(s->buf);
     if (s->gate_buf) (void)hipFree(s->gate_buf);
+    if (s->set_buf) (void)hipFree(s->set_buf);
     delete s;
 }
 
@@ -458,6 +497,9 @@ extern "C" int dfx_stream_set_thresholds(dfx_stream_state *s, float min_db_thres
     s->thr[0] = min_db_thresh;
     s->thr[1] = max_db_erb_thresh;
     s->thr[2] = max_db_df_thresh;
+    for (int64_t b = 0; b < s->B; ++b)
+        for (int j = 0; j < 3; ++j) s->row_thr[(size_t)b * 3 + j] = s->thr[j];
+    s->thr_rows = false;   // uniform again: passes take the scalars
     return DFX_OK;
 }
 
@@ -540,12 +582,126 @@ extern "C" int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db) {
     if (lim >= 100.f) s->lim = 0.f;
     else if (lim < 0.01f) s->lim = 1.f;
     else s->lim = powf(10.f, -lim / 20.f);
+    s->row_lim_db.assign((size_t)s->B, lim >= 100.f ? 100.f : lim);
+    s->lim_rows = false;   // uniform again: passes take the scalar (lim == 1: the undelayed pass-through, a handle-wide mode)
     return DFX_OK;
 }
 
 extern "C" int dfx_stream_set_post_filter_beta(dfx_stream_state *s, float beta) {
     if (!s || beta < 0.f) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_post_filter_beta: bad arguments");
     s->pf_beta = beta;
+    s->row_beta.assign((size_t)s->B, beta);
+    s->beta_rows = false;
+    return DFX_OK;
+}
+
+// ---- the same three settings for single streams (in the reference they are properties of one DfTract, i.e. of one caller) ----------------
+// Linear limit of a per-stream |dB|: like dfx_stream_set_atten_lim, except that |dB| < 0.01 does not select the handle's undelayed
+// pass-through (a handle-wide mode: the network would idle for everybody) but mixes with the largest float below 1, as dfx_enhance does
+// (dfx_model_enhance.h:161-162): the stream's noisy signal comes back delayed like everybody's, and its state keeps advancing.
+static float stream_row_lim(float lim_db_abs) {
+    if (lim_db_abs >= 100.f) return 0.f;
+    if (lim_db_abs < 0.01f) return 0.99999994f;
+    const float lim = powf(10.f, -lim_db_abs / 20.f);
+    return lim < 1.f ? lim : 0.99999994f;
+}
+
+// which: 0 attenuation limit (W = 1), 1 post-filter beta (W = 1), 2 thresholds (W = 3).  Validates everything before anything changes; then
+// — all on `stream`, nothing waits for the device — the setting's device array is brought up to date if the handle was uniform in it (every
+// row takes the handle's value), and the named streams' rows are written, DFX_SET_IDS streams per launch.
+template <int W>
+static int stream_set_rows(dfx_stream_state *s, const char *who, int which, const int64_t *ids, int64_t count, const float *vals, void *stream) {
+    if (!s || count < 0 || (count > 0 && (!ids || !vals))) DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: null handle or array", who);
+    const int ch = s->channels;
+    const int64_t ns = s->B / ch, B = s->B;
+    for (int64_t i = 0; i < count; ++i) {
+        if (ids[i] < 0 || ids[i] >= ns) DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: stream index %lld is not in [0, %lld)", who, (long long)ids[i], (long long)ns);
+        for (int j = 0; j < W; ++j)
+            if (std::isnan(vals[i * W + j])) DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: value %d of entry %lld is NaN", who, j, (long long)i);
+        if (which == 1 && vals[i] < 0.f) DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: beta of entry %lld is negative", who, (long long)i);
+    }
+    if (count == 0) return DFX_OK;
+    if (int rc = dfx_require_device()) return rc;
+    hipStream_t hs = dfx_stream(stream);
+    if (!s->set_buf) {
+        auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+        s->sb_lim = 0, s->sb_beta = al((size_t)B * 4), s->sb_thr = s->sb_beta + al((size_t)B * 4);
+        const size_t bytes = s->sb_thr + al((size_t)B * 12);
+        if (hipMalloc(reinterpret_cast<void **>(&s->set_buf), bytes) != hipSuccess) {
+            s->set_buf = nullptr;
+            DFX_FAIL(DFX_ERR_ALLOC, "%s: device allocation of %zu bytes failed", who, bytes);
+        }
+    }
+    float *dst = reinterpret_cast<float *>(s->set_buf + (which == 0 ? s->sb_lim : which == 1 ? s->sb_beta : s->sb_thr));
+    bool &on = which == 0 ? s->lim_rows : which == 1 ? s->beta_rows : s->thr_rows;
+    if (!on) {   // uniform so far: every row of the device array takes the handle's value (W fills of stride W)
+        const dfx_model_cfg &c = s->m->cfg;
+        // (a handle in pass-through mode leaves it: its other streams mix like a per-stream |dB| < 0.01)
+        if (which == 0 && s->lim == 1.f) s->lim = stream_row_lim(0.f);
+        const float uni[3] = {which == 0 ? s->lim : which == 1 ? (s->pf_beta >= 0.f ? s->pf_beta : (c.mask_pf ? c.pf_beta : 0.f)) : s->thr[0], s->thr[1], s->thr[2]};
+        for (int j = 0; j < W; ++j) {
+            dfx_launch(dfx_k_fill_rows, dim3((unsigned)nn_grid(dfx_ceil_div(B, 256), 16)), dim3(256), 0, hs, dst + j, (int64_t)W, (int64_t)1, B, uni[j]);
+            DFX_LAUNCH_CHECK();
+        }
+    }
+    // the host's copy, in the caller's order (duplicate ids: the last occurrence wins) ...
+    std::vector<float> &host = which == 0 ? s->row_lim_db : which == 1 ? s->row_beta : s->row_thr;
+    for (int64_t i = 0; i < count; ++i)
+        for (int k = 0; k < ch; ++k)
+            for (int j = 0; j < W; ++j) {
+                float v = vals[i * W + j];
+                if (which == 0) v = fabsf(v) >= 100.f ? 100.f : fabsf(v);
+                host[(size_t)(ids[i] * ch + k) * W + j] = v;
+            }
+    // ... and from it the device rows, every named stream once
+    std::vector<unsigned char> seen((size_t)ns, 0);
+    DfxRowVals<W> V;
+    V.n = 0;
+    auto flush = [&]() -> int {
+        if (V.n == 0) return DFX_OK;
+        dfx_launch(dfx_k_stream_set_rows<W>, dim3((unsigned)dfx_ceil_div((int64_t)V.n * ch, 256)), dim3(256), 0, hs, V, ch, dst, B);
+        DFX_LAUNCH_CHECK();
+        V.n = 0;
+        return DFX_OK;
+    };
+    for (int64_t i = 0; i < count; ++i) {
+        if (seen[(size_t)ids[i]]) continue;
+        seen[(size_t)ids[i]] = 1;
+        V.id[V.n] = (int)ids[i];
+        for (int j = 0; j < W; ++j) {
+            const float v = host[(size_t)(ids[i] * ch) * W + j];
+            V.v[V.n * W + j] = which == 0 ? stream_row_lim(v) : v;
+        }
+        if (++V.n == DFX_SET_IDS)
+            if (int rc = flush()) return rc;
+    }
+    if (int rc = flush()) return rc;
+    on = true;
+    return DFX_OK;
+}
+
+// df_set_atten_lim (capi.rs:136-144, tract.rs:387-398) of single streams
+extern "C" int dfx_stream_set_atten_lim_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *lim_db, void *stream) {
+    return stream_set_rows<1>(s, "dfx_stream_set_atten_lim_streams", 0, ids, count, lim_db, stream);
+}
+// df_set_post_filter_beta (capi.rs:146-156) of single streams
+extern "C" int dfx_stream_set_post_filter_beta_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *beta, void *stream) {
+    return stream_set_rows<1>(s, "dfx_stream_set_post_filter_beta_streams", 1, ids, count, beta, stream);
+}
+// RuntimeParams::with_thresholds (tract.rs:160-170) of single streams
+extern "C" int dfx_stream_set_thresholds_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *thr, void *stream) {
+    return stream_set_rows<3>(s, "dfx_stream_set_thresholds_streams", 2, ids, count, thr, stream);
+}
+// what was set, from the host's copy: [streams / channels][5] = |lim dB| (100: off), beta, min_db, max_db_erb, max_db_df
+extern "C" int dfx_stream_get_settings(const dfx_stream_state *s, float *out_host) {
+    if (!s || !out_host) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_get_settings: null argument");
+    const int64_t ns = s->B / s->channels;
+    for (int64_t k = 0; k < ns; ++k) {
+        const size_t r = (size_t)(k * s->channels);
+        out_host[k * 5 + 0] = s->row_lim_db[r];
+        out_host[k * 5 + 1] = s->row_beta[r];
+        for (int j = 0; j < 3; ++j) out_host[k * 5 + 2 + j] = s->row_thr[r * 3 + j];
+    }
     return DFX_OK;
 }
 
@@ -850,6 +1006,8 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         }
         if (side) sc.erb_pre = erb_ring, sc.df_pre = side_pre, sc.df_post = side_post;
         sc.pf_beta = S->pf_beta;
+        if (S->lim_rows) sc.lim_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_lim);     // per-stream settings: the finishing kernel
+        if (S->beta_rows) sc.beta_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_beta);  //   takes each row's own values
         sc.out = out_spec;  // local frame t of clip b lands at out_spec[(b*n + t - H) * Fp]
         sc.out_T = n;
         sc.out_toff = H;
@@ -861,6 +1019,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
             gate.flags = gflags;
             gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
             if (!silence) gate.thr[0] = -INFINITY, gate.thr[1] = gate.thr[2] = INFINITY;   // pausable, not gated: every stage runs on every hop
+            else if (S->thr_rows) gate.thr_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_thr), gate.thr[0] = gate.thr[1] = gate.thr[2] = 0.f;
             gate.c0_win = gp(S->g_c0_win);
             if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
             sc.gate = &gate;
@@ -1140,6 +1299,7 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
         gate.channels = S->channels;
         gate.flags = gflags;
         gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
+        if (S->thr_rows) gate.thr_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_thr), gate.thr[0] = gate.thr[1] = gate.thr[2] = 0.f;
         gate.c0_win = gp(S->g_c0_win);
         if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
         sc.gate = &gate;

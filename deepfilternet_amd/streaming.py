@@ -32,6 +32,15 @@ reference handle each).  Its input rows are still read and computed, then discar
 A pause is not silence: on a gated handle the stream's silent-input counter neither rises nor clears.  ``reset([i])`` followed by
 paused calls reserves a slot.  A paused row still costs its lane; a pausable handle runs one hop per pass in the per-stream state forms
 of a gated handle, so declare it only where it is needed.
+
+Settings per stream: in the reference the attenuation limit, the post-filter beta and the thresholds belong to one ``DfTract``, i.e. to one
+caller (capi.rs:136-156, tract.rs:160-170).  ``rt.set_atten_lim(12, streams=[3])``, ``rt.set_post_filter_beta([0.02, 0.05], streams=[3, 17])``
+and ``rt.set_thresholds(-10, 30, 20, streams=ids)`` set them for single streams of a running handle; ``rt.settings`` reports every stream's
+values.  A setter takes effect with the next ``process`` call and does not wait for the device; resets leave settings alone (a new caller
+sets its own after ``reset([i])``), and a paused stream's settings can be changed.  Without ``streams`` the setters are handle-wide, as
+before: they set every stream's value and make the handle uniform in that setting again.  The undelayed pass-through (``set_atten_lim(0)``)
+is a handle-wide mode; ``set_atten_lim(0, streams=[i])`` mixes with a limit just below 1 instead: stream i's noisy input comes back delayed
+like every other stream's output, and its state keeps advancing.  The steady hop costs no extra launch on a handle with per-stream settings.
 """
 from __future__ import annotations
 
@@ -86,34 +95,76 @@ class DfStream:
         """Hops by which the output lags the input (the model's lookahead), on top of the STFT's fft-hop samples."""
         return int(_lib.lib().dfx_stream_delay_frames(self._h))
 
-    def set_atten_lim(self, lim_db: float) -> None:
-        """df_set_atten_lim (capi.rs:136, tract.rs:387-398): |dB| >= 100 = no limit, < 0.01 = pass the input through."""
-        _lib.check(_lib.lib().dfx_stream_set_atten_lim(self._h, float(lim_db)))
+    def _stream_ids(self, streams) -> torch.Tensor:
+        ids = torch.as_tensor(streams).reshape(-1)
+        if ids.numel() and (ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool):
+            raise TypeError("stream indices must be integers")
+        return ids.to("cpu", torch.int64).contiguous()
 
-    def set_post_filter_beta(self, beta: float) -> None:
-        """df_set_post_filter_beta (capi.rs:146): 0 disables the post filter."""
-        _lib.check(_lib.lib().dfx_stream_set_post_filter_beta(self._h, float(beta)))
+    def _set_streams(self, fn, streams, values, width: int) -> None:
+        """One per-stream setter call: ``values`` are ``width`` scalars (broadcast over the ids) or sequences with one entry per id."""
+        ids = self._stream_ids(streams)
+        cols = []
+        for v in values:
+            v = torch.as_tensor(v, dtype=torch.float32).to("cpu")
+            if v.dim() == 0:
+                v = v.expand(ids.numel())
+            v = v.reshape(-1)
+            if v.numel() != ids.numel():
+                raise ValueError(f"{ids.numel()} stream indices but {v.numel()} values")
+            cols.append(v)
+        vals = torch.stack(cols, 1).contiguous()   # [count, width]
+        assert vals.shape == (ids.numel(), width)
+        _lib.check(fn(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), C.cast(vals.data_ptr(), C.POINTER(C.c_float)),
+                      _lib.stream()))
+
+    def set_atten_lim(self, lim_db, streams=None) -> None:
+        """df_set_atten_lim (capi.rs:136, tract.rs:387-398): |dB| >= 100 = no limit.  ``streams=None``: the whole handle, and |dB| < 0.01 =
+        pass the input through undelayed (a handle-wide mode: the network idles).  ``streams`` = a sequence or integer tensor of stream
+        indices: those streams alone, ``lim_db`` a scalar or one value per index; there |dB| < 0.01 mixes with a limit just below 1 (the
+        stream's input comes back delayed like everybody's output).  Does not wait for the device."""
+        if streams is None:
+            _lib.check(_lib.lib().dfx_stream_set_atten_lim(self._h, float(lim_db)))
+        else:
+            self._set_streams(_lib.lib().dfx_stream_set_atten_lim_streams, streams, [lim_db], 1)
+
+    def set_post_filter_beta(self, beta, streams=None) -> None:
+        """df_set_post_filter_beta (capi.rs:146): 0 disables the post filter.  ``streams`` as in ``set_atten_lim``."""
+        if streams is None:
+            _lib.check(_lib.lib().dfx_stream_set_post_filter_beta(self._h, float(beta)))
+        else:
+            self._set_streams(_lib.lib().dfx_stream_set_post_filter_beta_streams, streams, [beta], 1)
 
     def set_gating(self, enable: bool) -> None:
         """DfTract::process's stage skipping and silent-input shortcut (tract.rs:513-525,658-672), per stream."""
         _lib.check(_lib.lib().dfx_stream_set_gating(self._h, int(bool(enable))))
 
-    def set_thresholds(self, min_db_thresh: float, max_db_erb_thresh: float, max_db_df_thresh: float) -> None:
-        """RuntimeParams::with_thresholds (tract.rs:160-170)."""
-        _lib.check(_lib.lib().dfx_stream_set_thresholds(self._h, float(min_db_thresh), float(max_db_erb_thresh),
-                                                        float(max_db_df_thresh)))
+    def set_thresholds(self, min_db_thresh, max_db_erb_thresh, max_db_df_thresh, streams=None) -> None:
+        """RuntimeParams::with_thresholds (tract.rs:160-170).  ``streams`` as in ``set_atten_lim`` (stored on a handle without gating,
+        in force once gating is on)."""
+        if streams is None:
+            _lib.check(_lib.lib().dfx_stream_set_thresholds(self._h, float(min_db_thresh), float(max_db_erb_thresh),
+                                                            float(max_db_df_thresh)))
+        else:
+            self._set_streams(_lib.lib().dfx_stream_set_thresholds_streams, streams, [min_db_thresh, max_db_erb_thresh, max_db_df_thresh], 3)
+
+    @property
+    def settings(self) -> dict:
+        """Every stream's settings as they were set (CPU tensors, n = streams // channels): ``atten_lim_db`` [n] (|dB|, 100 = off),
+        ``post_filter_beta`` [n] (the model's value where none was set), ``thresholds`` [n, 3] (min_db, max_db_erb, max_db_df)."""
+        out = torch.zeros(self.streams // self.channels, 5, dtype=torch.float32)
+        _lib.check(_lib.lib().dfx_stream_get_settings(self._h, C.cast(out.data_ptr(), C.POINTER(C.c_float))))
+        return {"atten_lim_db": out[:, 0].clone(), "post_filter_beta": out[:, 1].clone(), "thresholds": out[:, 2:].clone()}
 
     def reset(self, streams=None) -> None:
         """``None``: the whole handle goes back to the state after creation.  A sequence or integer tensor of stream indices: those
         streams start over like the streams of a fresh handle (``delay_frames`` hops of silence, then their own signal since the reset,
-        enhanced and delayed), every other stream is untouched; settings are handle-wide and stay.  Does not wait for the device."""
+        enhanced and delayed), every other stream is untouched.  Settings stay, in both forms — the handle's and every stream's own
+        (``set_atten_lim(..., streams=...)`` and its neighbours): a new caller sets its own after the reset.  Does not wait for the device."""
         if streams is None:
             _lib.check(_lib.lib().dfx_stream_reset(self._h, _lib.stream()))
             return
-        ids = torch.as_tensor(streams).reshape(-1)
-        if ids.numel() and (ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool):
-            raise TypeError("stream indices must be integers")
-        ids = ids.to("cpu", torch.int64).contiguous()
+        ids = self._stream_ids(streams)
         _lib.check(_lib.lib().dfx_stream_reset_streams(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), _lib.stream()))
 
     @property

@@ -329,6 +329,21 @@ int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int1
  *   A mask-only model (dfx_model_set_run_df(m, 0), to be set before the handle's first call) never runs stage 2: its DF decoder's state
  *   never moves, gating decides between zeros / pass / mask only, and dfx_stream_process_raw reports gains (stage bit 2) with zero-filled
  *   coefficients and never bit 8.
+ *   Per-stream settings (dfx_stream_set_atten_lim_streams, ..._post_filter_beta_streams, ..._thresholds_streams): in the reference the
+ *   attenuation limit, the post-filter beta and the thresholds belong to one DfTract, i.e. to one caller (capi.rs:136-156,
+ *   tract.rs:160-170); here every stream of a handle can have its own.  With `channels` rows per stream a stream's value holds for all its
+ *   rows.  A setter is enqueued on `stream` like dfx_stream_reset_streams and never waits for the device; it takes effect with the next
+ *   dfx_stream_process call enqueued behind it, for the frames that call outputs — the moment at which a handle-wide setter called at the
+ *   same point takes effect.  Resets (of the handle or of single streams) leave settings alone: a new caller sets its own after the reset;
+ *   a paused stream's settings can be changed while it sits out.  The handle-wide setters keep their behaviour: each sets every stream's
+ *   value of its setting and makes the handle uniform in it again, and a handle that is uniform in a setting enqueues exactly what a handle
+ *   without per-stream settings enqueues.  The undelayed pass-through (|dB| < 0.01) is a handle-wide mode and is reached through
+ *   dfx_stream_set_atten_lim only: it returns the input undelayed and leaves the network idle for every stream.  A per-stream |dB| < 0.01
+ *   mixes with lim = 0.99999994 instead, as dfx_enhance does: the stream's noisy signal comes back delayed like everybody's output and its
+ *   state keeps advancing (a handle in pass-through mode leaves it with the first per-stream limit; its other streams then mix the same
+ *   way).  Thresholds set on a handle without gating are stored and take effect once gating is on; a pausable handle that is not gated keeps
+ *   running every stage on every hop, and a mask-only model keeps having no DF threshold.  A per-row handle enqueues the same kernels per
+ *   hop as a uniform one: the finishing kernel and the stage decision read each row's values from small device arrays.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dfx_stream_state dfx_stream_state;
 int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out);
@@ -336,7 +351,7 @@ void dfx_stream_free(dfx_stream_state *s);
 int dfx_stream_reset(dfx_stream_state *s, void *stream);                 /* back to the state after create */
 /* Streams ids[0..count) start over as after dfx_stream_create; every other stream is untouched.  ids: HOST array of stream
  * indices in [0, rows / channels) (a multi-channel stream is reset as a whole), duplicates allowed.  Settings (attenuation limit,
- * post-filter beta, gating, thresholds, channels) are handle-wide and stay.  Enqueued on `stream`, ordered with dfx_stream_process
+ * post-filter beta, thresholds — handle-wide or the stream's own — gating, channels) stay: a new caller sets its own.  Enqueued on `stream`, ordered with dfx_stream_process
  * calls on the same stream; does not wait for the device. */
 int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, void *stream);
 /* hops of network time each stream has consumed since its own last reset (host array, [rows / channels]); host bookkeeping, no device access */
@@ -349,6 +364,19 @@ int dfx_stream_set_channels(dfx_stream_state *s, int channels, int reduce_mask);
 int dfx_stream_set_gating(dfx_stream_state *s, int enable);              /* DfTract::process's per-frame stage decisions, per stream */
 int dfx_stream_set_thresholds(dfx_stream_state *s, float min_db_thresh, float max_db_erb_thresh,
                               float max_db_df_thresh);                   /* RuntimeParams::with_thresholds (tract.rs:160-170) */
+/* The same three settings for the streams ids[0..count) alone.  ids: HOST array of stream indices in [0, rows / channels); the values are
+ * HOST arrays with one entry (the thresholds: three — min_db, max_db_erb, max_db_df) per id; duplicate ids: the last occurrence wins.
+ * count == 0 is a no-op.  A null handle or array, an index out of range, a negative beta or a NaN fail with DFX_ERR_INVALID_ARG and change
+ * nothing.  Enqueued on `stream` (ids and values travel as kernel arguments, 192 streams per launch); no wait for the device. */
+int dfx_stream_set_atten_lim_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *lim_db /*[count]*/,
+                                     void *stream);                      /* df_set_atten_lim (capi.rs:136-144, tract.rs:387-398): |dB| >= 100 off, < 0.01 lim = 0.99999994 (delayed, not the bypass) */
+int dfx_stream_set_post_filter_beta_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *beta /*[count]*/,
+                                            void *stream);               /* df_set_post_filter_beta (capi.rs:146-156): 0 disables it for the stream */
+int dfx_stream_set_thresholds_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const float *thr /*[count][3]*/,
+                                      void *stream);                     /* RuntimeParams::with_thresholds (tract.rs:160-170) */
+/* What was set, from the host's copy (no device access): out_host [rows / channels][5] = lim_db (|dB|; 100: off), beta (the model's value
+ * where none was set), min_db, max_db_erb, max_db_df  (the reference keeps them in DfTract / RuntimeParams: tract.rs:150-189,387-398) */
+int dfx_stream_get_settings(const dfx_stream_state *s, float *out_host);
 int dfx_stream_process(dfx_stream_state *s, const float *x, int64_t n_frames, float *y, float *lsnr, void *stream);
 /* Accepted only at a reset point (no hop consumed since create / dfx_stream_reset); else DFX_ERR_INVALID_ARG. */
 int dfx_stream_set_pausable(dfx_stream_state *s, int enable);

@@ -2,11 +2,14 @@
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
     python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact] [--paused FRACTION]
+                                  [--per-stream-settings]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
 --paused FRACTION: a pausable handle (DfStream(pausable=True)); every call pauses that share of the streams, a block that rotates through
 the pool (0: a pausable handle on which nobody pauses).
+--per-stream-settings: every stream gets its own attenuation limit and post-filter beta (and, with --gating, thresholds) before the first call
+(DfStream.set_*(..., streams=ids)); the JSON line also carries the host time of one setter call over all ids (setter_host_ms).
 --exact: the model is created under DFX_EXACT_FP32=1 (every contraction in fp32: the one-hop GRU layers on dfx_k_gru_step_x32).
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
@@ -34,6 +37,8 @@ def main() -> None:
     ap.add_argument("--churn", type=int, default=0, help="reset this many streams before every call, rotating through the pool")
     ap.add_argument("--paused", type=float, default=None, metavar="FRACTION",
                     help="pausable handle; this share of the streams (a rotating block) sits every call out")
+    ap.add_argument("--per-stream-settings", action="store_true",
+                    help="a distinct attenuation limit and post-filter beta per stream (with --gating also thresholds), set per stream")
     ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
     if args.exact:
@@ -62,6 +67,21 @@ def main() -> None:
                 rt.reset([(churn_pos + k) % nslots for k in range(args.churn)])
                 churn_pos = (churn_pos + args.churn) % nslots
 
+        setter_ms = None
+        if args.per_stream_settings:   # streams distinct values each; the host time of a setter call over all ids = median of 5 calls
+            ids = torch.arange(args.streams)
+            lims = (6.0 + 24.0 * torch.arange(args.streams) / args.streams).tolist()
+            betas = (0.01 + 0.04 * torch.arange(args.streams) / args.streams).tolist()
+            times = []
+            for _ in range(5):
+                t = time.perf_counter()
+                rt.set_atten_lim(lims, streams=ids)
+                times.append((time.perf_counter() - t) * 1e3)
+            setter_ms = sorted(times)[2]
+            rt.set_post_filter_beta(betas, streams=ids)
+            if args.gating:
+                k = torch.arange(args.streams) / args.streams
+                rt.set_thresholds((-12.0 + 4.0 * k).tolist(), (28.0 + 4.0 * k).tolist(), (18.0 + 4.0 * k).tolist(), streams=ids)
         n_paused, pause_pos = int(round((args.paused or 0.0) * args.streams)), 0
 
         def mask():   # the next block of the pool sits this call out (a host array: the mask travels as kernel arguments)
@@ -99,6 +119,7 @@ def main() -> None:
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
                           "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "paused": args.paused, "exact_fp32": exact,
+                          "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         del rt
 
