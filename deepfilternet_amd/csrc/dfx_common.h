@@ -98,7 +98,9 @@ int dfx_launch_analysis_mem(const dfx_state *st, const float *x, int64_t B, int6
                             hipStream_t s);
 int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_len, int64_t x_stride, int nb_df,
                         float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride = 0, bool x_i16 = false,
-                        const int64_t *x_lens = nullptr);
+                        const int64_t *x_lens = nullptr,
+                        void *spec_ps = nullptr,         // non-null: also the pre-split copy of spec_feat ([B, T / hop, nb_df] x 8 bytes, dfx_pack_h3);
+                        unsigned int *err = nullptr);    //   spec_feat may then be null.  err: the model's error words (range guard of that split)
 // dfx_enhance_varlen: the rows' sample counts (host) -> meta [3][B] on the device: samples, frames ((samples + pad_n) / hop), output samples.
 // The counts travel as kernel arguments: the caller's array is not read after the return.
 int dfx_launch_varlen_rows(const int64_t *lens, int64_t B, int64_t *meta, int hop, int pad_n, hipStream_t s);
@@ -131,7 +133,9 @@ int dfx_launch_synthesis_rows(const dfx_state *st, const float *spec, int64_t sp
 int dfx_launch_norm_scan(const float *erb_in, float *erb_out, int E, const float *spec_in, int64_t spec_frame_stride,
                          float *spec_out, int Fn, int64_t C, int64_t T, float alpha, float *erb_state,
                          float *unit_state, hipStream_t s, int64_t erb_out_cs = 0,   // > 0: floats between the clips of erb_out / spec_out (< 16 frames)
-                         int64_t spec_out_cs = 0);
+                         int64_t spec_out_cs = 0, void *spec_ps = nullptr, unsigned int *err = nullptr);   // spec_ps / err: as in dfx_features_padded
+// the pre-split copy of an fp32 feat_spec of n complex values
+int dfx_launch_pack_h3(const float *feat, void *feat_ps, int64_t n, unsigned int *err, hipStream_t s);
 // Mask + MF.DF + post filter + atten_lim on frames [t_begin, t_end) of every clip (t_end < 0: T); coef_T: frames per clip of the
 // coefficient / gain arrays (default T); out_T / out_toff: compacted output rows (default T / 0); spec_stride / out_stride: row
 // strides in complex elements (0: F; even strides = 16-byte aligned rows take the row-streaming kernel)

@@ -507,22 +507,36 @@ int dfx_launch_analysis_mem(const dfx_state *st, const float *x, int64_t B, int6
 
 int dfx_launch_norm_scan(const float *erb_in, float *erb_out, int E, const float *spec_in, int64_t spec_frame_stride,
                          float *spec_out, int Fn, int64_t C, int64_t T, float alpha, float *erb_state,
-                         float *unit_state, hipStream_t s, int64_t erb_out_cs, int64_t spec_out_cs) {
+                         float *unit_state, hipStream_t s, int64_t erb_out_cs, int64_t spec_out_cs, void *spec_ps, unsigned int *err) {
     const int nch = (erb_in ? E : 0) + (spec_in ? Fn : 0);
     const int64_t n = C * nch;
     if (n <= 0) return DFX_OK;
+    if (spec_ps && (!spec_in || spec_out_cs > 0)) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_launch_norm_scan: the pre-split copy is dense and needs the complex half");
+    if (spec_in && !spec_out && (!spec_ps || T < 16)) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_launch_norm_scan: no output for the complex half");
     if ((erb_out_cs > 0 || spec_out_cs > 0) && T >= 16) DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_launch_norm_scan: strided outputs are for calls of < 16 frames");
     DfxKScope ks(DFX_K_NORM_SCAN, s);
     // four lanes per (row, channel) when there are frames to share (the frame-by-frame streaming runtime keeps one lane per channel)
     if (T >= 16) {
         dfx_launch(dfx_k_norm_scan4, dim3((unsigned)dfx_ceil_div(4 * n, 256)), dim3(256), 0, s, erb_in, erb_out, E,
                    reinterpret_cast<const float2 *>(spec_in), spec_frame_stride, reinterpret_cast<float2 *>(spec_out), Fn, C,
-                   T, alpha, erb_state, unit_state);
+                   T, alpha, erb_state, unit_state, reinterpret_cast<uint2 *>(spec_ps), err);
     } else {
         dfx_launch(dfx_k_norm_scan, dim3((unsigned)dfx_ceil_div(n, 64)), dim3(64), 0, s, erb_in, erb_out, E,
                    reinterpret_cast<const float2 *>(spec_in), spec_frame_stride, reinterpret_cast<float2 *>(spec_out), Fn, C,
                    T, alpha, erb_state, unit_state, erb_out_cs, spec_out_cs / 2);
+        if (spec_ps) {   // (a pass of a few frames: the copy from the fp32 values the scan has just written)
+            DFX_LAUNCH_CHECK();
+            return dfx_launch_pack_h3(spec_out, spec_ps, C * T * Fn, err, s);
+        }
     }
+    DFX_LAUNCH_CHECK();
+    return DFX_OK;
+}
+
+int dfx_launch_pack_h3(const float *feat, void *feat_ps, int64_t n, unsigned int *err, hipStream_t s) {
+    if (n <= 0) return DFX_OK;
+    dfx_launch(dfx_k_pack_h3, dim3((unsigned)grid_for(dfx_ceil_div(n, 256))), dim3(256), 0, s, reinterpret_cast<const float2 *>(feat),
+               reinterpret_cast<uint2 *>(feat_ps), n, err);
     DFX_LAUNCH_CHECK();
     return DFX_OK;
 }
@@ -711,19 +725,19 @@ extern "C" int dfx_features(const dfx_state *st, const float *x, int64_t B, int6
 // dfx_features over rows of T samples of which only the first x_len exist in memory (the rest are zeros): enhance()'s end padding
 int dfx_features_padded(const dfx_state *st, const float *x, int64_t B, int64_t T, int64_t x_len, int64_t x_stride, int nb_df,
                         float alpha, float *spec, float *erb_feat, float *spec_feat, void *stream, int64_t spec_stride, bool x_i16,
-                        const int64_t *x_lens) {
+                        const int64_t *x_lens, void *spec_ps, unsigned int *err) {
     if (spec_stride <= 0) spec_stride = st ? st->N / 2 + 1 : 0;
     if (!st || B < 0 || T < 0 || x_len < 0 || x_len > T || x_stride < x_len || nb_df <= 0 || nb_df > st->N / 2 + 1)
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_features: bad arguments");
     if (int rc = dfx_require_device()) return rc;
     const int64_t Tf = T / st->hop;
     if (B == 0 || Tf == 0) return DFX_OK;
-    if (!x || !spec || !erb_feat || !spec_feat) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_features: null buffer");
+    if (!x || !spec || !erb_feat || (!spec_feat && !spec_ps)) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_features: null buffer");
     // enhance.py:190-197: spec = analysis(x); erb_norm(erb(spec)); unit_norm(spec[..., :nb_df])
     if (int rc = dfx_launch_analysis(st, x, B, T, x_stride, nullptr, nullptr, spec, erb_feat, dfx_stream(stream), x_len, spec_stride, x_i16, x_lens))
         return rc;
     return dfx_launch_norm_scan(erb_feat, erb_feat, st->nb, spec, spec_stride, spec_feat, nb_df, B, Tf, alpha, nullptr,
-                                nullptr, dfx_stream(stream));
+                                nullptr, dfx_stream(stream), 0, 0, spec_ps, err);
 }
 
 // frames [t_begin, t_end) of every clip (t_end < 0: T); coef_T: frames per clip of the coefficient / gain arrays (default T);

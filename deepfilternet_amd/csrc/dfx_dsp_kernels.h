@@ -1398,6 +1398,25 @@ __global__ void dfx_k_erb_inv(const float *gains, int64_t rows, int F, int nb, c
 }
 
 #define DFX_SCAN_UNROLL 16
+// One unit-normed complex value as the fp16-split DF-encoder kernels read it (the pre-split copy of feat_spec, PS instances of dfx_k_df_enc_h3 /
+// dfx_k_df_convp_h3): 8 bytes, word 0 = {f16 hi(re), f16 hi(im)}, word 1 = {f16 lo(re), f16 lo(im)} with hi = f16(x), lo = f16(x - f32(hi)), both
+// round-to-nearest-even — dfx_split8's operations on the same values, so the halves those kernels would have made of every tap themselves (up to
+// 18 times per value).  The range guard of the split travels with it: amax is what dfx_split8_g tracks.
+static __device__ __forceinline__ uint2 dfx_pack_h3(float re, float im, float &amax) {
+    amax = fmaxf(amax, fmaxf(fabsf(re), fabsf(im)));
+    const uint16_t hr = dfx_f32_to_f16_bits(re), hi = dfx_f32_to_f16_bits(im);
+    const uint16_t lr = dfx_f32_to_f16_bits(re - dfx_f16_bits_to_f32(hr)), li = dfx_f32_to_f16_bits(im - dfx_f16_bits_to_f32(hi));
+    return make_uint2((unsigned)hr | ((unsigned)hi << 16), (unsigned)lr | ((unsigned)li << 16));
+}
+// the same for an array that exists in fp32 only (dfx_model_forward: the caller's feat_spec)
+__global__ void __launch_bounds__(256) dfx_k_pack_h3(const float2 *in, uint2 *out, int64_t n, unsigned int *err) {
+    float amax = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const float2 v = in[i];
+        out[i] = dfx_pack_h3(v.x, v.y, amax);
+    }
+    if (amax >= DFX_H3_LIMIT && err) dfx_raise(err + 1);
+}
 // Exponential mean norm of the ERB features (lib.rs:244-251) and exponential unit norm of the complex features
 // (lib.rs:253-259) — true recurrences over time, so one thread owns one (row, channel) and walks T sequentially; the
 // loads do not depend on the recurrence and are issued DFX_SCAN_UNROLL frames ahead.  Channels [0,E) are ERB bands,
@@ -1498,7 +1517,9 @@ __global__ void dfx_k_norm_scan(const float *erb_in, float *erb_out, int E, cons
 // frame.
 __global__ void __launch_bounds__(256) dfx_k_norm_scan4(const float *erb_in, float *erb_out, int E, const float2 *spec_in,
                                                         int64_t spec_frame_stride, float2 *spec_out, int Fn, int64_t C, int64_t T, float alpha,
-                                                        float *erb_state, float *unit_state) {
+                                                        float *erb_state, float *unit_state,
+                                                        uint2 *spec_ps = nullptr,      // non-null: the pre-split copy of spec_out (dfx_pack_h3), dense [C, T, Fn];
+                                                        unsigned int *err = nullptr) { // spec_out may then be null.  err: the model's error words (the split's range guard)
 #pragma clang fp contract(off)  // the Rust reference never fuses x*(1-a) + s*a into an FMA (lib.rs:244-259)
     constexpr int G = DFX_SCAN_UNROLL / 4;   // groups of 4 frames per batch
     const int nch = (erb_in ? E : 0) + (spec_in ? Fn : 0);
@@ -1565,6 +1586,12 @@ __global__ void __launch_bounds__(256) dfx_k_norm_scan4(const float *erb_in, flo
         else s = 0.001f + (Fn > 1 ? (0.0001f - 0.001f) / (float)(Fn - 1) : 0.f) * (float)ch;
         const float2 *in = spec_in + c * T * spec_frame_stride + ch;
         float2 *out = spec_out + c * T * Fn + ch;
+        uint2 *ps = spec_ps + c * T * Fn + ch;
+        float amax = 0.f;
+        auto put = [&](int64_t tt, float2 o) {   // (the value is in registers here: its split costs no pass over memory)
+            if (spec_out) out[tt * Fn] = o;
+            if (spec_ps) ps[tt * Fn] = dfx_pack_h3(o.x, o.y, amax);
+        };
         int64_t t = 0;
         const int64_t nbatch = T / DFX_SCAN_UNROLL;
         float2 v[G] = {}, nv[G] = {};
@@ -1588,7 +1615,7 @@ __global__ void __launch_bounds__(256) dfx_k_norm_scan4(const float *erb_in, flo
                     if (i == j) mine = s;
                 }
                 const float d = sqrtf(mine);
-                out[(t + 4 * g + j) * Fn] = make_float2(v[g].x / d, v[g].y / d);
+                put(t + 4 * g + j, make_float2(v[g].x / d, v[g].y / d));
             }
 #pragma unroll
             for (int g = 0; g < G; ++g) v[g] = nv[g];
@@ -1608,10 +1635,11 @@ __global__ void __launch_bounds__(256) dfx_k_norm_scan4(const float *erb_in, flo
             }
             if (have) {
                 const float d = sqrtf(mine);
-                out[(t + j) * Fn] = make_float2(x.x / d, x.y / d);
+                put(t + j, make_float2(x.x / d, x.y / d));
             }
         }
         if (unit_state && j == 0) unit_state[c * Fn + ch] = s;
+        if (amax >= DFX_H3_LIMIT && err) dfx_raise(err + 1);
     }
 }
 

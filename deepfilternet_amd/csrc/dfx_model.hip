@@ -130,6 +130,7 @@ struct DfxFinish {
     int64_t spec_stride;   // row stride (complex elements) of enhance()'s own spec / spec_e buffers: F rounded up to even, so that
                            // every row is 16-byte aligned (dfx_k_df_apply_rows); dfx_model_forward's caller-owned arrays are dense
     bool out_i16 = false;  // y points at int16_t PCM samples (dfx_enhance_pcm16)
+    bool feat_ps_made = false;   // the pre-split copy of feat_spec is already in the model workspace (Ws::fps: the norm scan wrote it)
 };
 // Streaming (dfx_stream_process): a forward pass over a window.  Every feature / activation array holds T = H + n frames per clip
 // (H history frames, then the n new ones); only the new frames are computed (kernels take t_begin, per-frame kernels a DfxRowMap),
@@ -493,6 +494,7 @@ struct dfx_model {
     unsigned int *d_sync = nullptr;
     unsigned int *d_psync = nullptr;    // pair form of the persistent GRU phase: [DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX / 2][48] words
     mutable unsigned int seq_pbase = 0;       // step counter base of the follower hand-overs (yprog / giprog), monotonic like seq_base
+    mutable int64_t passes_ps = 0;   // batch passes whose c0 kernels read the pre-split copy of feat_spec (DFX_Q_PASSES_C0_PRESPLIT)
     mutable int64_t passes_seq = 0, passes_ev = 0;   // passes that ran the persistent phase / that gave it up because another process held the device's ticket (DFX_Q_TICKET_*)
     mutable unsigned int seq_base = 0;  // flag value of "nothing of the current forward pass yet"
     unsigned long long *d_trace = nullptr;   // dev aid (DFX_SEQ_TRACE=1): chunk timestamps of the last persistent GRU launch
@@ -509,6 +511,7 @@ struct dfx_model {
         int dftail_every = 0;           // DFX_SEQ_DFTAIL_EVERY (0: the rule in forward_impl)
         bool tail_split = true;         // the ERB decoder's linear_out on a stream of its own beside the decoder tail (round 6; DFX_TAIL_SPLIT=0 in -DDFX_DEV builds)
         int64_t convp_elems = (int64_t)1 << 29;   // DFX_CONVP_ELEMS (test hook)
+        bool c0_presplit = true;        // DFX_C0_PRESPLIT=0 (test hook): batch passes run the unsplit instances of dfx_k_df_enc_h3 / dfx_k_df_convp_h3 on the fp32 feat_spec
         bool erb_enc_split = false;     // DFX_ERB_ENC_SPLIT=1 (test hook): batch passes run the ERB encoder as three launches (dfx_k_erb_enc, dfx_k_pwconv_f x 2) instead of dfx_k_erb_enc4
     } sw;
     // Error words, written by kernels, read by the host (page-locked host memory the device can store to: dfx_env_err_words_alloc):
@@ -1224,6 +1227,8 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
             if (cel && atoll(cel) > 0) m->sw.convp_elems = atoll(cel);
             const char *ees = getenv("DFX_ERB_ENC_SPLIT");   // test hook: the three-launch form of the ERB encoder in batch passes
             m->sw.erb_enc_split = ees && ees[0] == '1';
+            const char *cps = getenv("DFX_C0_PRESPLIT");     // test hook: the c0 kernels of batch passes split their feat_spec patches themselves
+            m->sw.c0_presplit = !(cps && cps[0] == '0');
         }
 #ifdef DFX_DEV
         {   // dev A/Bs of the phase's side work (product builds have no such switches)
@@ -1367,6 +1372,7 @@ extern "C" int dfx_model_query(const dfx_model *m, int what, int64_t *value) {
         case DFX_Q_PASSES_PERSISTENT: *value = m->passes_seq; return DFX_OK;
         case DFX_Q_PASSES_TICKET_BUSY: *value = m->passes_ev; return DFX_OK;
         case DFX_Q_SPIN_LIMIT: *value = m->spin_limit; return DFX_OK;
+        case DFX_Q_PASSES_C0_PRESPLIT: *value = m->passes_ps; return DFX_OK;
     }
     DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_query: unknown item %d", what);
 }
@@ -1385,14 +1391,38 @@ extern "C" int dfx_model_cfg_get(const dfx_model *m, dfx_model_cfg *out) {
     return DFX_OK;
 }
 
+// Does a pass read the pre-split copy of feat_spec (Ws::fps)?  Batch passes on the fp16-split path whose shape takes the fused c0 kernels
+// (forward_impl: fuse_h3); never the streaming runtime.  One rule for forward_impl and for enhance(), which has the norm scan write the copy.
+static inline bool dfx_c0_presplit(const dfx_model *m, bool streaming) {
+    return !streaming && m->sw.c0_presplit && m->fuse_c0 && !m->c0_batch_unfused && !m->exact_fp32 && m->cfg.conv_ch % 32 == 0 && m->cp_h3;
+}
+
+// df_fc_emb + linear_in behind df_conv1 as the fan-out kernels (dfx_k_enc_fan, and inside dfx_k_df_enc_h3)?
+static inline bool dfx_enc_fan_ok(const dfx_model *m) {
+    const dfx_model_cfg &c = m->cfg;
+    return m->efan_groups > 0 && !c.enc_concat && (int64_t)c.conv_ch * c.nb_erb / 4 == 16 * (int64_t)m->efan_groups;
+}
+// Does the DF branch of the encoder run as the one kernel dfx_k_df_enc_h3 on the fp16-split path (forward_impl: `dfenc` = fuse_h3 && this)?
+// feat_T: frames per clip of the feature arrays (0: T).  The limits are the kernel's 32-bit element offsets; beyond them the two kernels run.
+static inline bool dfx_dfenc_ok(const dfx_model *m, int64_t B, int64_t T, int64_t feat_T) {
+    const dfx_model_cfg &c = m->cfg;
+    const int64_t emb = (int64_t)c.conv_ch * c.nb_erb / 4;
+    return dfx_enc_fan_ok(m) && m->dfenc_chunks > 0 && B * T * emb < ((int64_t)1 << 31) && B * (feat_T > 0 ? feat_T : T) * c.nb_df < ((int64_t)1 << 29);
+}
+// ... and is the copy ALL such a pass reads of feat_spec?  The front takes the fused DF encoder and df_convp its PS instance: enhance() then has
+// the norm scan store the copy INSTEAD of the fp32 values (the scan is bound by its stores).  forward_impl decides with the same two functions.
+static inline bool dfx_feat_spec_unread(const dfx_model *m, int64_t B, int64_t T) { return dfx_c0_presplit(m, false) && dfx_dfenc_ok(m, B, T, 0); }
+// where model_forward_lane places the model's arrays inside the workspace it is given
+static inline float *dfx_ws_base(void *workspace) { return reinterpret_cast<float *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
+
 // ------------------------------------------------------------------------------------------------ workspace plan
 namespace {
 struct Ws {
     // offsets in floats, each 64-float (256 B) aligned
-    size_t e0, e1, e2, e3, c0, c1, emb_in, emb, xa, xb, gi, xa2, xb2, gi2, demb, d3, d2, d1, mask, c0p, xdf, coefs, lsnr, skp_e, skp_d, total;
+    size_t e0, e1, e2, e3, c0, c1, emb_in, emb, xa, xb, gi, xa2, xb2, gi2, demb, d3, d2, d1, mask, c0p, xdf, coefs, lsnr, skp_e, skp_d, fps, total;
     size_t pgi[DFX_MAX_GRU_LAYERS], py[DFX_MAX_GRU_LAYERS], ph[DFX_MAX_GRU_LAYERS];  // layer-pipelined GRU phase: gi, y, h state per layer
 };
-Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0) {
+Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0, bool presplit = false) {   // presplit: dfx_c0_presplit (batch passes of the model)
     Ws w{};
     size_t off = 0;
     auto take = [&](size_t n) {
@@ -1426,6 +1456,7 @@ Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0) {
     w.lsnr = take(R);
     w.skp_e = take(c.emb_gru_skip_enc == DFX_SKIP_GROUPEDLINEAR ? R * emb : 0);   // grouped-linear skips around the embedding GRUs
     w.skp_d = take(c.emb_gru_skip == DFX_SKIP_GROUPEDLINEAR ? R * emb : 0);
+    w.fps = take(presplit ? R * Fd * 2 : 0);   // the pre-split copy of feat_spec: 8 bytes per complex value (dfx_pack_h3), read by the PS instances of the c0 kernels
     const int nlayers = 1 + (c.emb_num_layers - 1) + c.df_num_layers;
     for (int l = 0; l < DFX_MAX_GRU_LAYERS; ++l) {
         const bool used = l < nlayers;
@@ -1440,7 +1471,7 @@ Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0) {
 
 extern "C" int dfx_model_workspace_bytes(const dfx_model *m, int64_t B, int64_t T, int64_t *bytes) {
     if (!m || !bytes || B < 0 || T < 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_workspace_bytes: bad arguments");
-    *bytes = (int64_t)(plan_ws(m->cfg, m->fuse_c0 && !m->c0_batch_unfused, B * T, B).total * sizeof(float)) + 256;
+    *bytes = (int64_t)(plan_ws(m->cfg, m->fuse_c0 && !m->c0_batch_unfused, B * T, B, dfx_c0_presplit(m, false)).total * sizeof(float)) + 256;
     return DFX_OK;
 }
 

@@ -101,17 +101,27 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
     float *fe = reinterpret_cast<float *>(base + w.feat_erb), *fs = reinterpret_cast<float *>(base + w.feat_spec);
     // F.pad(audio, (0, n_fft)) (enhance.py:230-233) is implicit: the analysis reads zeros past the T samples of a row
     const int64_t sstride = enh_spec_stride(st);
-    int rc = dfx_features_padded(st, x, B, Tp, T, x_stride, c.nb_df, c.norm_alpha, spec, fe, fs, (void *)s, sstride, pcm16, rows.len);
+    // the pre-split copy of feat_spec for the c0 kernels of the pass (dfx_c0_presplit) comes out of the norm scan, into its slot of the model workspace
+    int64_t mb = 0;
+    dfx_model_workspace_bytes(m, B, Tf, &mb);
+    void *fps = dfx_c0_presplit(m, false) ? dfx_ws_base(base + w.model) + plan_ws(c, m->fuse_c0 && !m->c0_batch_unfused, B * Tf, B, true).fps : nullptr;
+    const bool fs_unread = fps && Tf >= 16 && dfx_feat_spec_unread(m, B, Tf);   // (Tf < 16: the one-lane scan, the copy is made from its fp32 output)
+    int rc = dfx_features_padded(st, x, B, Tp, T, x_stride, c.nb_df, c.norm_alpha, spec, fe, fs_unread ? nullptr : fs, (void *)s, sstride, pcm16, rows.len, fps,
+                                 m->d_err);
     if (rc) return rc;
     if (rows.short_frames) {   // (2) above: spectrum and features of the frames behind a shorter row's end
         DfxTails t;
         t.add(spec, Tf * sstride * 2, Tf * sstride * 2, sstride * 2);
         t.add(fe, Tf * c.nb_erb, Tf * c.nb_erb, c.nb_erb);
-        t.add(fs, Tf * c.nb_df * 2, Tf * c.nb_df * 2, c.nb_df * 2);
+        // the pre-split copy like feat_spec (zero words are the halves of 0.f): in its place where the fp32 values are not written, else a launch of its own
+        t.add(fs_unread ? fps : fs, Tf * c.nb_df * 2, Tf * c.nb_df * 2, c.nb_df * 2);
         if ((rc = dfx_launch_zero_tails(t, rows.frames, B, s))) return rc;
+        if (fps && !fs_unread) {
+            DfxTails tp;
+            tp.add(fps, Tf * c.nb_df * 2, Tf * c.nb_df * 2, c.nb_df * 2);
+            if ((rc = dfx_launch_zero_tails(tp, rows.frames, B, s))) return rc;
+        }
     }
-    int64_t mb = 0;
-    dfx_model_workspace_bytes(m, B, Tf, &mb);
     // the synthesis is enqueued by the model forward (per time chunk when the GRU phase is pipelined); with pad it stores exactly
     // the window audio[:, d : orig_len + d] of enhance.py:248-249
     DfxFinish fin;
@@ -122,6 +132,7 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
     fin.out_len = pad ? T : Tf * st->hop;
     fin.spec_stride = sstride;
     fin.out_i16 = pcm16;
+    fin.feat_ps_made = fps != nullptr;
     return model_forward_lane(m, st->bands, spec, fe, fs, B, Tf, lim, spec_e, nullptr, nullptr, nullptr, base + w.model, mb, (void *)s, ln,
                               signal_front, &fin);
 }

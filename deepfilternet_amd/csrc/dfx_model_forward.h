@@ -38,7 +38,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     const int Lk = sc ? 0 : c.conv_lookahead;
     const int64_t t_zero = sc ? sc->t_zero : 0;
     const int *tzr = sc ? sc->t_zero_rows : nullptr;   // per-stream t_zero (streams of the handle that started over at different hops)
-    const Ws w = plan_ws(c, m->fuse_c0 && !m->c0_batch_unfused, R, B);
+    const Ws w = plan_ws(c, m->fuse_c0 && !m->c0_batch_unfused, R, B, dfx_c0_presplit(m, false));
     const int64_t sstride = fin ? fin->spec_stride : 0;  // 0: dense rows of F bins
     hipStream_t fin_s = s;                               // stream of the finishing kernels (deep filter, synthesis)
     const int E = c.nb_erb, Fd = c.nb_df, O = c.df_order, NO = 2 * O, emb = C * E / 4, L = c.conv_lookahead;
@@ -141,6 +141,10 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
     if (sc && !c0_fused) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
     const float *cp_feat = c0_fused ? feat_spec : nullptr;
     const bool fuse_h3 = c0_fused && !m->exact_fp32 && C % 32 == 0 && m->cp_h3;  // fp16-split matrix ops (default)
+    // batch passes on the fp16-split path: the two kernels that recompute c0 read the pre-split copy of feat_spec (PS instances; DFX_C0_PRESPLIT=0:
+    // the unsplit ones — test hook).  enhance() has the norm scan write the copy; for a caller's own feat_spec (dfx_model_forward) it is made here.
+    // Streaming passes (feature windows, per-stream t_zero, dfx_k_df_convp_step), exact mode and other shapes keep the fp32 features.
+    const uint2 *fps = dfx_c0_presplit(m, sc != nullptr) ? reinterpret_cast<const uint2 *>(ws + w.fps) : nullptr;
     // frame-resident ERB encoder head / decoder tail (dfx_k_erb_enc, dfx_k_erb_dec10 / dfx_k_erb_tail) where a frame fits the LDS; else layer by layer
     const bool fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
     const bool fuse_tail = fuse_dec && erb_tail_ok<C>(m, E);
@@ -256,11 +260,11 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
             }
         } else if (fuse_h3) {
             switch (kt) {
-                case 1: return launch_convp_h3<C, 1>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr);
-                case 2: return launch_convp_h3<C, 2>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr);
-                case 3: return launch_convp_h3<C, 3>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr);
-                case 4: return launch_convp_h3<C, 4>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr);
-                default: return launch_convp_h3<C, 5>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr);
+                case 1: return launch_convp_h3<C, 1>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr, fps);
+                case 2: return launch_convp_h3<C, 2>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr, fps);
+                case 3: return launch_convp_h3<C, 3>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr, fps);
+                case 4: return launch_convp_h3<C, 4>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr, fps);
+                default: return launch_convp_h3<C, 5>(m, feat_spec, c0p, B, T, Fd, NO, st, t0, t_zero, Lk, t1, featT, tzr, fps);
             }
         } else if (kt <= 5 && NO <= 16) {
             switch (kt) {
@@ -317,7 +321,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         return launch_pw<C>(DFX_PW_MODE_DW3, m, m->erb3, e2, nullptr, e3, Rk, E / 4, E / 4, 1, st, rm);
     };
     // cemb = relu(df_fc_emb(c1.flatten)); emb_in = e3.flatten + cemb (:179-182), then enc.emb_gru's linear_in (SqueezedGRU_S :149-158).
-    const bool enc_fan = m->efan_groups > 0 && !c.enc_concat && emb == 16 * m->efan_groups;
+    const bool enc_fan = dfx_enc_fan_ok(m);
     auto emb_range = [&](int64_t Rk, DfxRowMap rm, hipStream_t st) -> int {
         int r;
         if (enc_fan) return launch_enc_fan(m, c1, e3, c.emb_gru_skip_enc != DFX_SKIP_NONE ? emb_in : nullptr, xa, Rk, st, rm);
@@ -330,10 +334,11 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         return launch_glin(m, m->enc_in, emb_in, DFX_ACT_RELU, nullptr, xa, Rk, st, rm);
     };
     // the DF branch of the encoder as one kernel behind the ERB convolutions (it adds e3), c1 never stored
-    const bool dfenc = fuse_h3 && enc_fan && m->dfenc_chunks > 0 && B * T * (int64_t)emb < ((int64_t)1 << 31) &&
-                       B * (featT > 0 ? featT : T) * Fd < ((int64_t)1 << 29);   // (32-bit element offsets inside the kernel; beyond: the two kernels)
+    const bool dfenc = fuse_h3 && dfx_dfenc_ok(m, B, T, featT);   // (32-bit element offsets inside the kernel; beyond: the two kernels)
     {   // ---- the front: the frames [t_begin, T) that this pass computes
         if (c0_fused) {
+            m->passes_ps += fps ? 1 : 0;
+            if (fps && !(fin && fin->feat_ps_made) && (rc = dfx_launch_pack_h3(feat_spec, ws + w.fps, R * Fd, m->d_err, x1))) return rc;
             if ((rc = signal(EV_C0, x1)) || (rc = wait(EV_C0, x2))) return rc;  // df_convp only needs feat_spec
             if (!dfenc && dfx_dev_stage(3) && (rc = df1_range(t_begin, T, x1))) return rc;
         } else {
@@ -378,7 +383,7 @@ static int forward_impl(const dfx_model *m, const dfx_bands *bands, const float 
         if (dfx_dev_stage(2) && (rc = erb_range(t_begin, T, Rn, rmw, s))) return rc;
         if ((rc = wait(EV_C1, s))) return rc;
         if (dfenc) {
-            if (dfx_dev_stage(3) && (rc = launch_df_enc<C>(m, feat_spec, e3, c.emb_gru_skip_enc != DFX_SKIP_NONE ? emb_in : nullptr, xa, B, T, Fd, s, t_begin, Lk, T, featT))) return rc;
+            if (dfx_dev_stage(3) && (rc = launch_df_enc<C>(m, feat_spec, e3, c.emb_gru_skip_enc != DFX_SKIP_NONE ? emb_in : nullptr, xa, B, T, Fd, s, t_begin, Lk, T, featT, fps))) return rc;
         } else if (dfx_dev_stage(3) && (rc = emb_range(Rn, rmw, s))) return rc;
         // the chip-filling front of this chunk is enqueued: the next chunk of a pipelined dfx_enhance may start its own front
         // (it then overlaps this chunk's GRU chain, which occupies only a few CUs)
@@ -1005,7 +1010,7 @@ static int model_forward_lane(const dfx_model *m, const dfx_bands *bands, const 
     if (workspace_bytes < need) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_forward: workspace too small (%lld < %lld bytes)", (long long)workspace_bytes, (long long)need);
     if (((uintptr_t)spec & 15) || ((uintptr_t)spec_e & 15) || ((uintptr_t)feat_erb & 15) || ((uintptr_t)feat_spec & 15))
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_forward: buffers must be 16-byte aligned");
-    float *ws = reinterpret_cast<float *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255);
+    float *ws = dfx_ws_base(workspace);
     hipStream_t s = dfx_stream(stream);
     switch (m->cfg.conv_ch) {
         case 16: return forward_impl<16>(m, bands, spec, feat_erb, feat_spec, B, T, atten_lim, spec_e, mask, lsnr, df_coefs, ws, s, ln, signal_front, fin);

@@ -129,7 +129,8 @@ constexpr int DFX_CONVP_GRAIN = 16;
 template <int C, int KT>
 static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *out, int64_t B, int64_t T, int Fd, int NO,
                            hipStream_t s, int64_t t_begin = 0, int64_t t_zero = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0,
-                           const int *t_zero_rows = nullptr) {
+                           const int *t_zero_rows = nullptr,
+                           const uint2 *feat_ps = nullptr) {   // non-null (batch passes): the pre-split copy of feat_spec, read by the PS instance
     if constexpr (C % 32 != 0) {
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "fp16-split df_convp needs conv_ch %% 32 == 0");
     } else {
@@ -143,7 +144,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
                 for (int64_t b0 = 0; b0 < B; b0 += bmax) {
                     const int64_t nb = B - b0 < bmax ? B - b0 : bmax;
                     if (int r = launch_convp_h3<C, KT>(m, feat_spec + b0 * per_clip * 2, out + b0 * (int64_t)(NO / 2) * T * Fd * 2, nb, T, Fd, NO, s, t_begin, t_zero, L,
-                                                       t_end, feat_T, t_zero_rows ? t_zero_rows + b0 : nullptr))
+                                                       t_end, feat_T, t_zero_rows ? t_zero_rows + b0 : nullptr, feat_ps ? feat_ps + b0 * per_clip : nullptr))
                         return r;
                 }
                 return DFX_OK;
@@ -152,6 +153,7 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
         DfxCphArgs A;
         A.t_end = t_end;
         A.feat = feat_spec;
+        A.feat_ps = feat_ps;
         A.feat_T = feat_T;
         A.w0f = reinterpret_cast<const dfx_h8 *>(m->p(m->c0_h3));
         A.bias0 = m->p(m->cin_b);
@@ -183,7 +185,8 @@ static int launch_convp_h3(const dfx_model *m, const float *feat_spec, float *ou
         // (capping the launch at 64 ... 192 resident workgroups, so that the rest of the chip is free for the front's critical path, measured
         // +0.1 ... +0.5 ms per step: profiles/r04_exact_and_convp_cap.log)
         DfxKScope ks(DFX_K_DF_CONVP, s);
-        dfx_launch((dfx_k_df_convp_h3<C, KT>), dim3(nn_grid(dfx_ceil_div(nruns, 4), 2 * DFX_CONVP_GRAIN)), dim3(256), 0, s, A);
+        if (feat_ps) dfx_launch((dfx_k_df_convp_h3<C, KT, true>), dim3(nn_grid(dfx_ceil_div(nruns, 4), 2 * DFX_CONVP_GRAIN)), dim3(256), 0, s, A);
+        else dfx_launch((dfx_k_df_convp_h3<C, KT>), dim3(nn_grid(dfx_ceil_div(nruns, 4), 2 * DFX_CONVP_GRAIN)), dim3(256), 0, s, A);
         DFX_LAUNCH_CHECK();
         return DFX_OK;
     }
@@ -622,13 +625,14 @@ static int launch_enc_fan(const dfx_model *m, const float *c1, const float *e3, 
 // The DF branch of the encoder in one kernel: feat_spec -> (c0 -> c1 -> df_fc_emb + e3 -> linear_in) -> xa (dfx_k_df_enc_h3); frames [t_begin, t_end)
 template <int C>
 static int launch_df_enc(const dfx_model *m, const float *feat_spec, const float *e3, float *emb_in, float *xa, int64_t B, int64_t T, int Fin,
-                         hipStream_t s, int64_t t_begin, int L, int64_t t_end, int64_t feat_T) {
+                         hipStream_t s, int64_t t_begin, int L, int64_t t_end, int64_t feat_T, const uint2 *feat_ps = nullptr) {   // feat_ps: as in launch_convp_h3
     if constexpr (C % 32 != 0) {
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "fused DF encoder needs conv_ch %% 32 == 0");
     } else {
         if (B * T * (int64_t)m->fc_emb.G * 16 >= ((int64_t)1 << 31) || B * (feat_T > 0 ? feat_T : T) * Fin >= ((int64_t)1 << 29))
             DFX_FAIL(DFX_ERR_UNSUPPORTED, "fused DF encoder: batch too large for one launch (32-bit element offsets)");
         DfxDfEncArgs A;
+        A.feat_ps = feat_ps;
         A.feat = feat_spec;
         A.w0f = reinterpret_cast<const dfx_h8 *>(m->p(m->c0_h3));
         A.bias0 = m->p(m->cin_b);
@@ -651,7 +655,8 @@ static int launch_df_enc(const dfx_model *m, const float *feat_spec, const float
         while (tiles * A.nsplit < (int64_t)dfx_env_num_cus() * 4 * 3 && A.Fout % (2 * A.nsplit) == 0 && (A.Fout / (2 * A.nsplit)) % unit == 0) A.nsplit *= 2;
         tiles *= A.nsplit;
         DfxKScope ks(DFX_K_PWCONV, s);
-        dfx_launch(dfx_k_df_enc_h3<C>, dim3((unsigned)nn_grid(dfx_ceil_div(tiles, 4), 3)), dim3(DFX_PW_THREADS), 0, s, A);
+        if (feat_ps) dfx_launch((dfx_k_df_enc_h3<C, true>), dim3((unsigned)nn_grid(dfx_ceil_div(tiles, 4), 3)), dim3(DFX_PW_THREADS), 0, s, A);
+        else dfx_launch(dfx_k_df_enc_h3<C>, dim3((unsigned)nn_grid(dfx_ceil_div(tiles, 4), 3)), dim3(DFX_PW_THREADS), 0, s, A);
         DFX_LAUNCH_CHECK();
         return DFX_OK;
     }

@@ -507,16 +507,32 @@ static __device__ __forceinline__ void dfx_c0_patch_load(const float *__restrict
     }
 }
 
-template <int C>
-static __device__ __forceinline__ void dfx_c0_tile_h3(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
-                                                      const float4 (&bias0)[C / 16], float unscale0, const float2 (&raw)[4],
-                                                      bool keep, float (&dst)[C / 4], float &amax) {
-    constexpr int NT = C / 16;
-    float x[8];
+// The pre-split copy of feat_spec (dfx_pack_h3 in dfx_dsp_kernels.h: 8 bytes per complex value, word 0 = the f16 hi halves of (re, im), word 1 =
+// the lo halves): a lane's four taps are four 8-byte loads whose words 0 ARE the B operand's hi half (k-slots 2 i, 2 i + 1 = re, im of tap i) and
+// whose words 1 are its lo half.  An invalid tap is two zero words (the halves of 0.f).
+typedef unsigned dfx_words4 __attribute__((vector_size(16)));
+struct DfxPatchPs {   // a lane's four taps as the PS instances hold them: their words 0 and their words 1 — the two operands, bit for bit
+    dfx_words4 h, l;
+};
+static __device__ __forceinline__ void dfx_c0_patch_ps(const DfxPatchPs &pk, dfx_h8 &ph, dfx_h8 &pl) {
+    ph = __builtin_bit_cast(dfx_h8, pk.h);
+    pl = __builtin_bit_cast(dfx_h8, pk.l);
+}
+// tap i of a patch: the loaded element, or zeros where the tap is outside (`in` false)
+static __device__ __forceinline__ void dfx_put_tap(float2 (&p)[4], int i, bool in, float2 v) { p[i] = make_float2(in ? v.x : 0.f, in ? v.y : 0.f); }
+static __device__ __forceinline__ void dfx_put_tap(DfxPatchPs &p, int i, bool in, uint2 v) { p.h[i] = in ? v.x : 0u, p.l[i] = in ? v.y : 0u; }
+static __device__ __forceinline__ void dfx_copy_patch(float2 (&d)[4], const float2 (&s)[4]) {
 #pragma unroll
-    for (int i = 0; i < 4; ++i) x[2 * i] = raw[i].x, x[2 * i + 1] = raw[i].y;
-    dfx_h8 ph, pl;
-    dfx_split8_g(x, ph, pl, amax);
+    for (int i = 0; i < 4; ++i) d[i] = s[i];
+}
+static __device__ __forceinline__ void dfx_copy_patch(DfxPatchPs &d, const DfxPatchPs &s) { d = s; }
+
+// (the products and the epilogue of a c0 tile, behind the B operand's halves)
+template <int C>
+static __device__ __forceinline__ void dfx_c0_tile_h3p(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
+                                                       const float4 (&bias0)[C / 16], float unscale0, const dfx_h8 ph, const dfx_h8 pl,
+                                                       bool keep, float (&dst)[C / 4]) {
+    constexpr int NT = C / 16;
     f32x4 acc[NT];  // the NT chains are independent: term-major order keeps dependent MFMAs NT issues apart
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0l[nt], ph, f32x4{0.f, 0.f, 0.f, 0.f});
@@ -531,6 +547,25 @@ static __device__ __forceinline__ void dfx_c0_tile_h3(const dfx_h8 (&w0h)[C / 16
         dst[4 * nt + 2] = keep ? fmaxf(acc[nt][2] * unscale0 + bias0[nt].z, 0.f) : 0.f;
         dst[4 * nt + 3] = keep ? fmaxf(acc[nt][3] * unscale0 + bias0[nt].w, 0.f) : 0.f;
     }
+}
+template <int C>
+static __device__ __forceinline__ void dfx_c0_tile_h3(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
+                                                      const float4 (&bias0)[C / 16], float unscale0, const float2 (&raw)[4],
+                                                      bool keep, float (&dst)[C / 4], float &amax) {
+    float x[8];
+#pragma unroll
+    for (int i = 0; i < 4; ++i) x[2 * i] = raw[i].x, x[2 * i + 1] = raw[i].y;
+    dfx_h8 ph, pl;
+    dfx_split8_g(x, ph, pl, amax);
+    dfx_c0_tile_h3p<C>(w0h, w0l, bias0, unscale0, ph, pl, keep, dst);
+}
+template <int C>   // the patch from the pre-split copy: no split, and its range guard sits where the copy was made
+static __device__ __forceinline__ void dfx_c0_tile_h3(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
+                                                      const float4 (&bias0)[C / 16], float unscale0, const DfxPatchPs &raw,
+                                                      bool keep, float (&dst)[C / 4], float &) {
+    dfx_h8 ph, pl;
+    dfx_c0_patch_ps(raw, ph, pl);
+    dfx_c0_tile_h3p<C>(w0h, w0l, bias0, unscale0, ph, pl, keep, dst);
 }
 
 struct DfxC01hArgs {
@@ -770,10 +805,21 @@ struct DfxDfEncArgs {
     int64_t t_begin, t_end;
     unsigned int *err;
     int64_t feat_T = 0;
+    const uint2 *feat_ps = nullptr;   // PS instances: the pre-split copy of feat (same shape, dfx_pack_h3), read instead of it
 };
 
-template <int C>
+// PS: the patches come from the pre-split copy of feat_spec (batch passes: dfx_k_norm_scan4 writes it beside / instead of the fp32 values): a tap's
+// load IS its two operand words — the patch split (2 x 16 conversions, 8 subtracts and the range guard per bin and lane) is gone, everything behind
+// the B operand is the same expression for expression: the same c0 bits.
+// The PS instance also computes the tap geometry once per TILE instead of once per tap: at the head of a tile a lane parks, for each of its four taps, the element offset of (its frame's tap row, tap column at input bin
+// 1) — or -1 where the tap is padding (k >= 18), its row lies outside the clip or the lane is dead: nothing of that depends on the bin.  A patch
+// is then one 16-byte LDS read, and per tap an add of the (wave-uniform) bin, a clamped address and a zero select — no compare but `offset >= 0`
+// in the bins 1 .. Fin - 2; the two edge bins keep the column check.  `keep` of a c0 tile is wave-uniform but for dead lanes, whose patches are
+// zeros and whose results are never stored (every store is guarded by `live`): the sixteen selects of the epilogue are gone.
+template <int C, bool PS = false>
 __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArgs A) {
+    using Patch = std::conditional_t<PS, DfxPatchPs, float2[4]>;   // a lane's four taps in registers
+    using Elem = std::conditional_t<PS, uint2, float2>;             // a tap in memory
     constexpr int CPL = C / 4, NT = C / 16, KC = C / 32, C4 = C / 4;
     static_assert(C % 32 == 0, "one k-chunk is 32 channels");
     __shared__ float4 dws[3 * C4];
@@ -799,8 +845,9 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
     const int T32 = (int)A.T, Fin = A.Fin, Lk = A.L, Fout = A.Fout, emb = Fout * C / A.cpg / 2;   // emb = groups * 16 = Fout * KC / cpg * 16
     const int64_t fT = A.feat_T > 0 ? A.feat_T : (int64_t)T32;
     // the four taps (of the 3x3 window over (t, f), padded to 16) this lane feeds into the k index of the matrix op, packed (dt + 64 |
-    // (df + 1) << 8 | ok << 16) and parked in LDS: the kernel sits at the 168-register edge of three waves per SIMD
-    {
+    // (df + 1) << 8 | ok << 16) and parked in LDS: the kernel sits at the 168-register edge of three waves per SIMD (the unsplit instance;
+    // the PS instance parks a tile's offsets there, below)
+    if constexpr (!PS) {
         int ti[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
@@ -818,22 +865,53 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
         const int t = (int)A.t_begin + (int)(rl - b * Tn);   // this lane's frame
         const bool live = rl < NFR;
         // 32-bit element offsets from the (scalar) array bases: B * feat_T * Fin < 2^29 and B * T * emb < 2^31 are checked by the host
-        const float2 *feat2 = reinterpret_cast<const float2 *>(A.feat);
+        const Elem *feat2;
+        if constexpr (PS) feat2 = A.feat_ps;
+        else feat2 = reinterpret_cast<const float2 *>(A.feat);
         const unsigned cbase = b * (unsigned)fT * (unsigned)Fin;
         const unsigned row = b * (unsigned)T32 + (unsigned)t;
-        float2 raw[2][4];   // taps 1 and 2 (and, before the first bin, tap 0 in raw[0])
-        auto issue_to = [&](float2 (&dst)[4], int j, int fo) {   // patch j (input bin fo * stride + j - 1) of this lane's frame
+        Patch raw[2];    // taps 1 and 2 (and, before the first bin, tap 0 in raw[0])
+        if constexpr (PS) {   // this tile's tap offsets into the lane's slot of tis (lane-private: the wave's LDS operations complete in order)
+            int ti[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                const int tap = 4 * q + i, kt = tap / 3, tin = t + kt - 2 + Lk;
+                ti[i] = live && tap < 9 && tin - Lk >= 0 && tin < T32 ? (int)(cbase + (unsigned)(tin * Fin + (tap - 3 * kt))) : -1;
+            }
+#pragma unroll
+            for (int i = 0; i < 4; ++i) tis[4 * tid + i] = ti[i];
+        }
+        auto issue_to = [&](Patch &dst, int j, int fo) {   // patch j (input bin fo * stride + j - 1) of this lane's frame
             const int fi = fo * A.stride + j - 1;
             const bool ok = live && fo < fo1 && fi >= 0 && fi < Fin;
             int zt = tid;
             DFX_OPAQUE(zt);   // (a read per use, not a value carried in registers)
             const int tinfo[4] = {tis[4 * zt], tis[4 * zt + 1], tis[4 * zt + 2], tis[4 * zt + 3]};
+            if constexpr (PS) {
+                // tinfo[i] + fi - 1 = the element of tap i (its column is fi - 1 + kf); a tap outside reads the array's first element and is zeroed
+                if (fo < fo1 && fi >= 1 && fi <= Fin - 2) {   // (wave-uniform) every tap column is a bin of the frame
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int tin = t + (tinfo[i] & 0xff) - 64, fin = fi + ((tinfo[i] >> 8) & 0xff) - 1;
-                float2 v = make_float2(0.f, 0.f);
-                if (ok && (tinfo[i] >> 16) && tin - Lk >= 0 && tin < T32 && fin >= 0 && fin < Fin) v = feat2[cbase + (unsigned)(tin * Fin + fin)];
-                dst[i] = v;
+                    for (int i = 0; i < 4; ++i) {
+                        const bool in = tinfo[i] >= 0;
+                        dfx_put_tap(dst, i, in, feat2[in ? (unsigned)(tinfo[i] + fi - 1) : 0u]);
+                    }
+                } else {
+                    const bool fok = fo < fo1 && fi >= 0 && fi < Fin;
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) {
+                        const int tap = 4 * q + i, fin = fi + (tap - 3 * (tap / 3)) - 1;
+                        const bool in = fok && tinfo[i] >= 0 && fin >= 0 && fin < Fin;
+                        dfx_put_tap(dst, i, in, feat2[in ? (unsigned)(tinfo[i] + fi - 1) : 0u]);
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    const int tin = t + (tinfo[i] & 0xff) - 64, fin = fi + ((tinfo[i] >> 8) & 0xff) - 1;
+                    float2 v = make_float2(0.f, 0.f);
+                    if (ok && (tinfo[i] >> 16) && tin - Lk >= 0 && tin < T32 && fin >= 0 && fin < Fin) v = feat2[cbase + (unsigned)(tin * Fin + fin)];
+                    dst[i] = v;
+                }
             }
         };
         // One c0 tile (input bin fo * stride + j - 1 of this lane's frame): its patch -> split -> three products per 16 channels -> ReLU, added
@@ -842,16 +920,20 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
         // 2 fo + 1): it is computed once — two tiles per bin instead of three (24 instead of 36 of the bin's 67 matrix ops, a third of the patch loads, splits and
         // epilogues).  The parked term is w0 * v = what `0 + w0 * v` is in the three-tile form: the same bits.  It waits in LDS, lane-private
         // (16 registers the kernel does not have at three waves per SIMD).
-        auto c0_tile = [&](auto jc, auto addc, auto nextc, int fo, float2 (&rw)[4], float (&u)[CPL], bool refill) {
+        auto c0_tile = [&](auto jc, auto addc, auto nextc, int fo, Patch &rw, float (&u)[CPL], bool refill) {
             constexpr int j = decltype(jc)::value;
             constexpr bool ADD = decltype(addc)::value, NEXT = decltype(nextc)::value;
-            float x[8];
-#pragma unroll
-            for (int i = 0; i < 4; ++i) x[2 * i] = rw[i].x, x[2 * i + 1] = rw[i].y;
             const int fi = fo * A.stride + j - 1;
             const bool keep = live && fi >= 0 && fi < Fin;
             dfx_h8 ph, pl;
-            dfx_split8_g(x, ph, pl, amax);
+            if constexpr (PS) {
+                dfx_c0_patch_ps(rw, ph, pl);
+            } else {
+                float x[8];
+#pragma unroll
+                for (int i = 0; i < 4; ++i) x[2 * i] = rw[i].x, x[2 * i + 1] = rw[i].y;
+                dfx_split8_g(x, ph, pl, amax);
+            }
             if (refill) issue_to(rw, j, fo + 1);   // the patch registers are free again: the same patch of the next bin (beyond the last: zeros, no loads)
             int z0 = 0;
             DFX_OPAQUE(z0);     // (loop-invariant LDS reads: not to be hoisted back into registers)
@@ -868,22 +950,32 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
             for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0h[nt], pl, acc[nt]);
 #pragma unroll
             for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0h[nt], ph, acc[nt]);
+            auto epilogue = [&](auto allc) {   // ALL: every lane keeps its values (no select)
+                constexpr bool ALL = decltype(allc)::value;
 #pragma unroll
-            for (int nt = 0; nt < NT; ++nt) {
-                const float4 bz = b0s[4 * nt + q];
-                const float v0 = keep ? fmaxf(acc[nt][0] * A.unscale0 + bz.x, 0.f) : 0.f, v1 = keep ? fmaxf(acc[nt][1] * A.unscale0 + bz.y, 0.f) : 0.f;
-                const float v2 = keep ? fmaxf(acc[nt][2] * A.unscale0 + bz.z, 0.f) : 0.f, v3 = keep ? fmaxf(acc[nt][3] * A.unscale0 + bz.w, 0.f) : 0.f;
-                if constexpr (ADD) {
-                    const float4 w = dws[j * C4 + 4 * nt + q];
-                    u[4 * nt + 0] += w.x * v0;
-                    u[4 * nt + 1] += w.y * v1;
-                    u[4 * nt + 2] += w.z * v2;
-                    u[4 * nt + 3] += w.w * v3;
+                for (int nt = 0; nt < NT; ++nt) {
+                    const float4 bz = b0s[4 * nt + q];
+                    const float v0 = ALL || keep ? fmaxf(acc[nt][0] * A.unscale0 + bz.x, 0.f) : 0.f, v1 = ALL || keep ? fmaxf(acc[nt][1] * A.unscale0 + bz.y, 0.f) : 0.f;
+                    const float v2 = ALL || keep ? fmaxf(acc[nt][2] * A.unscale0 + bz.z, 0.f) : 0.f, v3 = ALL || keep ? fmaxf(acc[nt][3] * A.unscale0 + bz.w, 0.f) : 0.f;
+                    if constexpr (ADD) {
+                        const float4 w = dws[j * C4 + 4 * nt + q];
+                        u[4 * nt + 0] += w.x * v0;
+                        u[4 * nt + 1] += w.y * v1;
+                        u[4 * nt + 2] += w.z * v2;
+                        u[4 * nt + 3] += w.w * v3;
+                    }
+                    if constexpr (NEXT) {
+                        const float4 wn = dws[4 * nt + q];
+                        uns[nt * DFX_PW_THREADS + tid] = make_float4(0.f + wn.x * v0, 0.f + wn.y * v1, 0.f + wn.z * v2, 0.f + wn.w * v3);
+                    }
                 }
-                if constexpr (NEXT) {
-                    const float4 wn = dws[4 * nt + q];
-                    uns[nt * DFX_PW_THREADS + tid] = make_float4(0.f + wn.x * v0, 0.f + wn.y * v1, 0.f + wn.z * v2, 0.f + wn.w * v3);
-                }
+            };
+            if constexpr (PS) {
+                // inside the bins (wave-uniform) `keep` is `live`: a dead lane's column holds what its zero patches give and is never stored
+                if (fi >= 0 && fi < Fin) epilogue(std::true_type{});
+                else epilogue(std::false_type{});
+            } else {
+                epilogue(std::false_type{});
             }
         };
         using I0 = std::integral_constant<int, 0>;
@@ -996,6 +1088,7 @@ struct DfxCphArgs {
     unsigned int *err;        // as in DfxC01hArgs
     int64_t feat_T = 0;       // as in DfxC01hArgs
     const int *t_zero_rows = nullptr;   // non-null: t_zero per clip (streams of a handle that started over at different hops); null: the scalar
+    const uint2 *feat_ps = nullptr;     // PS instances of dfx_k_df_convp_h3: the pre-split copy of feat (as in DfxDfEncArgs)
 };
 
 // (Two 16-bin blocks per wave side by side — two independent tiles in one instruction stream, df_conv0's fragments in LDS to make room for the
@@ -1009,8 +1102,14 @@ struct DfxCphArgs {
 // 1.56 instead of 1.90 ms, one wave's matrix ops under the other's vector work; but beside the GRU phase or beside the front the step got 0.7-1.4 ms
 // SLOWER (14.0-14.8 vs 13.3 ms, every placement): two 256-register waves per SIMD leave no room for another kernel's wave, where this kernel's
 // single 352-register wave leaves 160 registers per SIMD to the kernels it runs beside.  Removed; profiles/r05_convp_pending_sums.log.)
-template <int C, int KT>
+// PS: the patches come from the pre-split copy of feat_spec, as in dfx_k_df_enc_h3<C, true>; the patch geometry is the unsplit instance's.
+// (An unchecked patch path for the frames and bin blocks whose taps all lie inside, beside the checked one in the five times unrolled frame loop,
+// was built and measured: the kernel 7.9 instead of 7.2 ms under the GRU phase, the step 11.46 instead of 10.71 ms.  Removed;
+// profiles/c0_presplit_variants.log.)
+template <int C, int KT, bool PS = false>
 __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
+    using Patch = std::conditional_t<PS, DfxPatchPs, float2[4]>;   // a lane's four taps in registers
+    using Elem = std::conditional_t<PS, uint2, float2>;             // a tap in memory
     constexpr int CPL = C / 4, NT = C / 16, KC = C >= 32 ? C / 32 : 1;
     static_assert(C % 32 == 0, "one k-chunk is 32 channels");
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
@@ -1054,7 +1153,9 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         tdf[i] = tap - 3 * kt - 1;
         toff[i] = (kt - 2 + Lk) * Fd + tdf[i];
     }
-    const float2 *feat2 = reinterpret_cast<const float2 *>(A.feat);
+    const Elem *feat2;
+    if constexpr (PS) feat2 = A.feat_ps;
+    else feat2 = reinterpret_cast<const float2 *>(A.feat);
     for (int64_t run = (int64_t)blockIdx.x * 4 + dfx_wave_uniform(wave); run < nruns; run += (int64_t)gridDim.x * 4) {
         const int seg = (int)(run % A.nseg);
         const int64_t rest = run / A.nseg;
@@ -1067,7 +1168,7 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         const unsigned cbase = (unsigned)b * (unsigned)fT * (unsigned)Fd;   // scalar
         const int64_t tz = A.t_zero_rows ? (int64_t)A.t_zero_rows[b] : A.t_zero;   // scalar
         // the patch of frame t (scalar) and this lane's bin: four taps, zero outside the clip / the bins / the causal padding
-        auto patch = [&](int t, bool ok, float2 (&rw)[4]) {
+        auto patch = [&](int t, bool ok, Patch &rw) {
             const unsigned pbase = cbase + (unsigned)(t * Fd + f);
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -1075,13 +1176,12 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
                 // branch-free: a tap outside reads the clip's first element (always there) and is zeroed by a select — an exec-masked load is a
                 // save / branch / restore sequence per tap
                 const bool in = ok && tin - Lk >= 0 && tin < T32 && fin >= 0 && fin < Fd;
-                const float2 v = feat2[in ? pbase + (unsigned)toff[i] : cbase];
-                rw[i] = make_float2(in ? v.x : 0.f, in ? v.y : 0.f);
+                dfx_put_tap(rw, i, in, feat2[in ? pbase + (unsigned)toff[i] : cbase]);
             }
         };
         dfx_h8 xh[KT][KC], xl[KT][KC];  // frame tau lives in slot (tau - t0) mod KT
-        float2 raw[4];
-        auto make_frame = [&](dfx_h8 (&dh)[KC], dfx_h8 (&dl)[KC], int64_t tau, const float2 (&rw)[4]) {
+        Patch raw;
+        auto make_frame = [&](dfx_h8 (&dh)[KC], dfx_h8 (&dl)[KC], int64_t tau, const Patch &rw) {
             float c0v[CPL];
             // frames before the clip are the zero padding of c0 itself (wave-uniform test)
             dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, rw, fvalid && tau >= tz, c0v, amax);
@@ -1100,9 +1200,8 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
                 constexpr int ph = decltype(pc)::value;
                 const int64_t t = tb + ph;
                 if (t < t1) {  // wave-uniform
-                    float2 cur[4];
-#pragma unroll
-                    for (int i = 0; i < 4; ++i) cur[i] = raw[i];
+                    Patch cur;
+                    dfx_copy_patch(cur, raw);
                     patch((int)t + 1, fvalid && t + 1 < t1, raw);
                     make_frame(xh[ph], xl[ph], t, cur);
                     // three independent accumulation chains (one per product term), summed small-to-large at the end

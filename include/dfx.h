@@ -228,6 +228,7 @@ int dfx_model_check(const dfx_model *m);
 #define DFX_Q_PASSES_PERSISTENT 5   /* big passes of this handle that ran the persistent GRU phase */
 #define DFX_Q_PASSES_TICKET_BUSY 6  /* big passes that took the event-synchronised form because another PROCESS held the device's ticket for its own
                                        persistent phase (/dev/shm/dfx_persistent_<PCI bus id>.lock, DFX_DEVICE_TICKET=0: no ticket) */
+#define DFX_Q_PASSES_C0_PRESPLIT 7  /* batch passes whose fused DF-encoder kernels read the pre-split copy of feat_spec (default; DFX_C0_PRESPLIT=0: none) */
 int dfx_model_query(const dfx_model *m, int what, int64_t *value);
 
 /* Scratch memory the caller must provide (device bytes) for a [B, T-frames] batch. */
