@@ -8,6 +8,7 @@
 #include <atomic>
 #include <map>
 #include <mutex>
+#include <type_traits>
 #include <fcntl.h>
 #include <sys/file.h>
 #include <sys/stat.h>

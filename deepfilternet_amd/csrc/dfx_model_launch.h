@@ -2,6 +2,27 @@
 // A part of dfx_model.hip (one translation unit: included from there, in this order — launch helpers, forward pass, streaming, enhance()).
 #pragma once
 
+// ------------------------------------------------------------------------------------------------ run-time values as template arguments
+// f is a generic lambda and is handed a std::integral_constant; it reads the value as decltype(arg)::value.
+template <class F>
+static int dfx_with_bool(bool b, F &&f) {
+    return b ? f(std::true_type{}) : f(std::false_type{});
+}
+// df_pathway_kernel_size_t: the kernels are instantiated for 1 .. 5 frames; anything else takes the widest instance (the callers refuse
+// what that cannot compute).  KMIN = 2: no instance for one frame (dfx_k_df_convp_step has none).
+template <int KMIN, class F>
+static int dfx_with_kt(int kt, F &&f) {
+    if constexpr (KMIN <= 1) {
+        if (kt == 1) return f(std::integral_constant<int, 1>{});
+    }
+    switch (kt) {
+        case 2: return f(std::integral_constant<int, 2>{});
+        case 3: return f(std::integral_constant<int, 3>{});
+        case 4: return f(std::integral_constant<int, 4>{});
+        default: return f(std::integral_constant<int, 5>{});
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ launch helpers
 static int nn_grid(int64_t tiles, int per_cu) {
     const int64_t cap = (int64_t)dfx_env_num_cus() * per_cu;
@@ -27,55 +48,42 @@ static int launch_pw(int mode, const dfx_model *m, const PwW &w, const float *x,
     A.rm = rm;
     DfxKScope ks(DFX_K_PWCONV, s);
     // frame-staged form (coalesced loads / stores through wave-private LDS strips; same bits): whenever whole frames make whole tiles
-    constexpr bool staged = true;
-    if (staged && dfx_pwf_ok(C, Fin, Fout)) {
+    if (dfx_pwf_ok(C, Fin, Fout)) {
         const size_t smem = dfx_pwf_smem(C, Fin, Fout);
         const int gridf = nn_grid(dfx_ceil_div(dfx_ceil_div(R, dfx_pwf_group(C, Fin, Fout)), 4), 2);
-        const bool n4 = dfx_pwf_nvi(C, Fin, Fout) == 4;
-        auto go = [&](auto kern) -> int {
-            DFX_HIP(dfx_env_set_max_dyn_smem((const void *)kern, smem));
-            dfx_launch(kern, dim3((unsigned)gridf), dim3(DFX_PW_THREADS), smem, s, A);
-            return DFX_OK;
-        };
-        int rc;
+        bool h3 = false;   // fp16-split pointwise contraction (default); without wt_h3 and in exact mode: the fp32 instances
         if constexpr (C % 32 == 0) {
-            if (!m->exact_fp32 && w.wt_h3) {   // fp16-split pointwise contraction (default)
+            if (!m->exact_fp32 && w.wt_h3) {
+                h3 = true;
                 A.wt_h3 = reinterpret_cast<const dfx_h8 *>(m->p(w.wt_h3));
                 A.unscale = w.unscale;
                 A.err = m->d_err;
-                if (mode == DFX_PW_MODE_DW3) {
-                    if (skip) rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, true, 4, true>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, true, DFX_PWF_MAXV, true>);
-                    else rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, false, 4, true>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, false, DFX_PWF_MAXV, true>);
-                } else {
-                    if (skip) rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, true, 4, true>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, true, DFX_PWF_MAXV, true>);
-                    else rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, false, 4, true>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, false, DFX_PWF_MAXV, true>);
-                }
-                if (rc) return rc;
-                DFX_LAUNCH_CHECK();
-                return DFX_OK;
             }
         }
-        if (mode == DFX_PW_MODE_DW3) {
-            if (skip) rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, true, 4>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, true, DFX_PWF_MAXV>);
-            else rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, false, 4>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DW3, false, DFX_PWF_MAXV>);
-        } else {
-            if (skip) rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, true, 4>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, true, DFX_PWF_MAXV>);
-            else rc = n4 ? go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, false, 4>) : go(dfx_k_pwconv_f<C, DFX_PW_MODE_DWT3, false, DFX_PWF_MAXV>);
-        }
-        if (rc) return rc;
-        DFX_LAUNCH_CHECK();
-        return DFX_OK;
+        auto go = [&](auto dw3, auto sk, auto n4, auto split) -> int {
+            constexpr int MODE = decltype(dw3)::value ? DFX_PW_MODE_DW3 : DFX_PW_MODE_DWT3, NV = decltype(n4)::value ? 4 : DFX_PWF_MAXV;
+            auto kern = dfx_k_pwconv_f<C, MODE, decltype(sk)::value, NV, decltype(split)::value && C % 32 == 0>;
+            DFX_HIP(dfx_env_set_max_dyn_smem((const void *)kern, smem));
+            dfx_launch(kern, dim3((unsigned)gridf), dim3(DFX_PW_THREADS), smem, s, A);
+            DFX_LAUNCH_CHECK();
+            return DFX_OK;
+        };
+        return dfx_with_bool(mode == DFX_PW_MODE_DW3, [&](auto dw3) {
+            return dfx_with_bool(skip != nullptr, [&](auto sk) {
+                return dfx_with_bool(dfx_pwf_nvi(C, Fin, Fout) == 4, [&](auto n4) {
+                    return dfx_with_bool(h3, [&](auto split) { return go(dw3, sk, n4, split); });
+                });
+            });
+        });
     }
     const int grid = nn_grid(dfx_ceil_div(R * Fout, 64), 8);
-    if (mode == DFX_PW_MODE_DW3) {
-        if (skip) dfx_launch(dfx_k_pwconv<C, DFX_PW_MODE_DW3, true>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
-        else dfx_launch(dfx_k_pwconv<C, DFX_PW_MODE_DW3, false>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
-    } else {
-        if (skip) dfx_launch(dfx_k_pwconv<C, DFX_PW_MODE_DWT3, true>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
-        else dfx_launch(dfx_k_pwconv<C, DFX_PW_MODE_DWT3, false>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
-    }
-    DFX_LAUNCH_CHECK();
-    return DFX_OK;
+    return dfx_with_bool(mode == DFX_PW_MODE_DW3, [&](auto dw3) {
+        return dfx_with_bool(skip != nullptr, [&](auto sk) {
+            dfx_launch(dfx_k_pwconv<C, decltype(dw3)::value ? DFX_PW_MODE_DW3 : DFX_PW_MODE_DWT3, decltype(sk)::value>, dim3(grid), dim3(DFX_PW_THREADS), 0, s, A);
+            DFX_LAUNCH_CHECK();
+            return DFX_OK;
+        });
+    });
 }
 
 template <int C, int KT>
@@ -283,27 +291,26 @@ static int launch_erb_dec10(const dfx_model *m, const float *d2, const float *e1
     A.E = E;
     A.rm = rm;
     DfxKScope ks(DFX_K_ERB_DEC, s);
-    constexpr bool staged = true;
-    if (staged && dfx_dec10f_ok(C, E)) {   // whole frames streamed through LDS strips (dfx_k_erb_dec10_f)
+    if (dfx_dec10f_ok(C, E)) {   // whole frames streamed through LDS strips (dfx_k_erb_dec10_f)
         DfxDec10fArgs AA;
         AA.a = A;
         const size_t smemf = DFX_DEC10F_SMEM(C, E);
-        const dim3 grid((unsigned)nn_grid(dfx_ceil_div(R, 4), 2));
+        bool h3 = false;
         if constexpr (C % 32 == 0) {
             if (!m->exact_fp32 && m->ct1.wt_h3) {
+                h3 = true;
                 AA.wt_h3 = reinterpret_cast<const dfx_h8 *>(m->p(m->ct1.wt_h3));
                 AA.unscale = m->ct1.unscale;
                 AA.err = m->d_err;
-                DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_erb_dec10_f<C, true>, smemf));
-                dfx_launch(dfx_k_erb_dec10_f<C, true>, grid, dim3(256), smemf, s, AA);
-                DFX_LAUNCH_CHECK();
-                return DFX_OK;
             }
         }
-        DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_erb_dec10_f<C, false>, smemf));
-        dfx_launch(dfx_k_erb_dec10_f<C, false>, grid, dim3(256), smemf, s, AA);
-        DFX_LAUNCH_CHECK();
-        return DFX_OK;
+        return dfx_with_bool(h3, [&](auto split) {
+            auto kern = dfx_k_erb_dec10_f<C, decltype(split)::value && C % 32 == 0>;
+            DFX_HIP(dfx_env_set_max_dyn_smem((const void *)kern, smemf));
+            dfx_launch(kern, dim3((unsigned)nn_grid(dfx_ceil_div(R, 4), 2)), dim3(256), smemf, s, AA);
+            DFX_LAUNCH_CHECK();
+            return DFX_OK;
+        });
     }
     const size_t smem = DFX_DEC10_SMEM(C, E);
     DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_erb_dec10<C>, smem));

@@ -1026,13 +1026,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         }
         float *ws = reinterpret_cast<float *>(((uintptr_t)(S->buf + S->model_ws) + 255) & ~(uintptr_t)255);
         const DfxLane *ln = &m->lanes[0];
-        switch (c.conv_ch) {
-            case 16: rc = forward_impl<16>(m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, ln, false, nullptr, &sc); break;
-            case 32: rc = forward_impl<32>(m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, ln, false, nullptr, &sc); break;
-            case 64: rc = forward_impl<64>(m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, ln, false, nullptr, &sc); break;
-            default: DFX_FAIL(DFX_ERR_UNSUPPORTED, "conv_ch");
-        }
-        if (rc) return rc;
+        if ((rc = forward_conv_ch(c.conv_ch, m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, ln, false, nullptr, &sc))) return rc;
         if (stepped) S->hflip ^= 1;   // (like lin_pos: this form is neither replayed from a graph nor walked hop by hop by the caller)
         S->c0ring_ok = sc.c0ring_used;   // any pass that did not go through the step kernel (several hops, gated, run_df off) leaves the sums behind
         if (gated && c.df_pathway_kernel_size_t > 1) {  // the DF decoder's delay line moves where that decoder ran
@@ -1305,13 +1299,7 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
         sc.gate = &gate;
         float *ws = reinterpret_cast<float *>(((uintptr_t)(S->buf + S->model_ws) + 255) & ~(uintptr_t)255);
         const DfxLane *ln = &m->lanes[0];
-        switch (c.conv_ch) {
-            case 16: rc = forward_impl<16>(m, st->bands, fp(S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, fp(S->lsnr), cbuf, ws, s, ln, false, nullptr, &sc); break;
-            case 32: rc = forward_impl<32>(m, st->bands, fp(S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, fp(S->lsnr), cbuf, ws, s, ln, false, nullptr, &sc); break;
-            case 64: rc = forward_impl<64>(m, st->bands, fp(S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, fp(S->lsnr), cbuf, ws, s, ln, false, nullptr, &sc); break;
-            default: DFX_FAIL(DFX_ERR_UNSUPPORTED, "conv_ch");
-        }
-        if (rc) return rc;
+        if ((rc = forward_conv_ch(c.conv_ch, m, st->bands, fp(S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, fp(S->lsnr), cbuf, ws, s, ln, false, nullptr, &sc))) return rc;
         if (c.df_pathway_kernel_size_t > 1) {
             if (S->g_pend2_ok)
                 dfx_launch(dfx_k_gate_pend_commit, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const unsigned char *)gflags,
