@@ -355,6 +355,10 @@ struct DfxGateTable {
     int64_t row[DFX_GATE_MAX_ENTRIES];
     unsigned char mask[DFX_GATE_MAX_ENTRIES], want[DFX_GATE_MAX_ENTRIES];
     int n;
+    void add(float *dst_, const float *src_, int64_t row_, unsigned char mask_, unsigned char want_) {   // host
+        dst[n] = dst_, src[n] = src_, row[n] = row_, mask[n] = mask_, want[n] = want_;
+        ++n;
+    }
 };
 __global__ void dfx_k_gate_commit(DfxGateTable G, const unsigned char *flags, int64_t B) {
     const int64_t b = blockIdx.x;

@@ -236,7 +236,6 @@ struct dfx_stream_state {
     bool fresh = true;        // no hop consumed since create / dfx_stream_reset
     std::vector<unsigned char> paused;   // [B / channels], this call: 1 = sits out
     bool any_paused = false;
-    bool p_mixed = false, p_warm = false;   // this pass (stream_process_impl)
     // Settings per stream (dfx_stream_set_*_streams): in the reference the attenuation limit, the post-filter beta and the thresholds belong to
     // one DfTract, i.e. to one caller (capi.rs:136-156, tract.rs:160-170).  The host keeps every row's values (what dfx_stream_get_settings
     // reports; the handle-wide setters write all rows); the device arrays — own allocation, made by the first per-stream setter — are read by
@@ -261,6 +260,13 @@ static int stream_copy_rows(const float *src, int64_t src_stride, int64_t src_le
     return DFX_OK;
 }
 
+// Bytes per stream of df_convp's pending sums (dfx_k_df_convp_step): [kt-1][nfb][64 lanes] x 16 bytes.  A gated handle keeps them twice
+// per stream (DfxGate::pend2: the half that is current and the one being built).
+static inline size_t stream_c0ring_row_bytes(const dfx_model_cfg &c) {
+    return (size_t)(c.df_pathway_kernel_size_t - 1) * ((c.nb_df + 15) / 16) * 64 * 16;
+}
+static inline size_t stream_pend2_row_bytes(const dfx_model_cfg &c) { return 2 * stream_c0ring_row_bytes(c); }
+
 extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out) {
     if (!m || !st || !out || streams <= 0 || max_frames <= 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: bad arguments");
     const dfx_model_cfg &c = m->cfg;
@@ -282,7 +288,6 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     // history in front of the new frames: 2 frames for the 3-tap input convolutions + kt-1 frames of (recomputed) c0 for df_convp
     const int hist_conv = 2 + (c.df_pathway_kernel_size_t - 1), hist_df = c.df_order - 1 - c.df_lookahead;
     s->H = hist_conv > hist_df ? hist_conv : hist_df;
-    s->layers = c.emb_num_layers + (c.emb_num_layers - 1) + c.df_num_layers;
     s->layers = (int)(m->enc_gru.size() + m->dec_gru.size() + m->df_gru.size());
     const int64_t B = streams, n = max_frames, H = s->H, Hs = s->H + s->L, F = (st->N / 2 + 1 + 7) & ~(int64_t)7 /* padded rows */, E = c.nb_erb, Fd = c.nb_df,
                   ML = st->N - st->hop;
@@ -317,21 +322,16 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         if (lin_env && (size_t)B * (Hs + n + slack) * F * 8 <= ((size_t)3 << 29)) {
             s->lin_cap = Hs + n + slack;
             s->spec_lin = take((size_t)B * s->lin_cap * F * 8);
-            constexpr bool feat_env = true;
-            if (feat_env) {
-                s->feat_cap = H + n + slack;   // the same slack: the three windows reach the end in the same call
-                s->fe_lin = take((size_t)B * s->feat_cap * E * 4);
-                s->fs_lin = take((size_t)B * s->feat_cap * Fd * 8);
-            }
+            s->feat_cap = H + n + slack;   // the same slack: the three windows reach the end in the same call
+            s->fe_lin = take((size_t)B * s->feat_cap * E * 4);
+            s->fs_lin = take((size_t)B * s->feat_cap * Fd * 8);
         }
     }
     s->h_state = take((size_t)s->layers * B * 256 * 4);
     s->h_state2 = take((size_t)s->layers * B * 256 * 4);
-    {   // pending sums of dfx_k_df_convp_step: [B][kt-1][nfb][64 lanes] x 16 bytes (4096 streams of the released model: 101 MB)
-        const int kt = c.df_pathway_kernel_size_t;
-        const size_t rb = kt >= 2 && c.conv_ch % 32 == 0 ? (size_t)B * (kt - 1) * ((Fd + 15) / 16) * 64 * 16 : 0;
-        constexpr bool ring_env = true;
-        if (rb > 0 && rb <= ((size_t)1 << 30) && ring_env && !m->exact_fp32) {   // (only the fp16-split step kernel keeps pending sums)
+    {   // pending sums of dfx_k_df_convp_step (4096 streams of the released model: 101 MB)
+        const size_t rb = c.df_pathway_kernel_size_t >= 2 && c.conv_ch % 32 == 0 ? (size_t)B * stream_c0ring_row_bytes(c) : 0;
+        if (rb > 0 && rb <= ((size_t)1 << 30) && !m->exact_fp32) {   // (only the fp16-split step kernel keeps pending sums)
             s->c0ring_bytes = rb;
             s->c0ring = take(rb);
         }
@@ -406,6 +406,26 @@ extern "C" int dfx_stream_reset(dfx_stream_state *s, void *stream) {
     return DFX_OK;
 }
 
+// df_convp's state of one stream, as both a stream's start (stream_state_rows) and the warm-up of a started stream (DfxStreamPass::warm_rows)
+// zero it: the pending sums of an ungated pass, and — per_stream: the handle's passes keep the gated runtime's forms — the per-stream
+// delay line in whichever form the handle has (pending sums twice with parity and count, or the window of c0 frames).
+static bool stream_convp_rows(const dfx_stream_state *S, bool per_stream, DfxRowClear &R) {
+    const dfx_model_cfg &c = S->m->cfg;
+    bool ok = true;
+    if (S->c0ring_bytes) ok = R.add(S->buf + S->c0ring, (int64_t)stream_c0ring_row_bytes(c), (int64_t)stream_c0ring_row_bytes(c)) && ok;
+    if (!per_stream) return ok;
+    unsigned char *g = S->gate_buf;
+    if (S->g_pend2_ok) {
+        ok = R.add(g + S->g_pend2, (int64_t)stream_pend2_row_bytes(c), (int64_t)stream_pend2_row_bytes(c)) && ok;
+        ok = R.add(g + S->g_par, 1, 1) && ok;
+        ok = R.add(g + S->g_cnt, 4, 4) && ok;
+    } else if (c.df_pathway_kernel_size_t > 1) {
+        const int64_t wb = (int64_t)(S->H + 1) * c.nb_df * c.conv_ch * 4;
+        ok = R.add(g + S->g_c0_win, wb, wb) && ok;
+    }
+    return ok;
+}
+
 // The rows of every state array that a stream's start zeroes, in whichever form currently holds the state (both ring parities, the
 // linear windows' history at lin_pos, both GRU buffers, the pending sums, the gate arrays and shadow copies).
 static int stream_state_rows(const dfx_stream_state *S, DfxRowClear &R) {
@@ -428,25 +448,15 @@ static int stream_state_rows(const dfx_stream_state *S, DfxRowClear &R) {
     }
     add(S->buf + S->h_state, 1024, 1024, S->layers, B * 1024);
     add(S->buf + S->h_state2, 1024, 1024, S->layers, B * 1024);
-    if (S->c0ring_bytes) add(S->buf + S->c0ring, (int64_t)(S->c0ring_bytes / (size_t)B), (int64_t)(S->c0ring_bytes / (size_t)B));
     if (S->gate_buf) {
         unsigned char *g = S->gate_buf;
-        const int kt = c.df_pathway_kernel_size_t;
         add(g + S->g_flags, 1, 1);
         add(g + S->g_counter, 4, 4);
         add(g + S->g_sh_erb, E * 4, E * 4);
         add(g + S->g_sh_unit, Fd * 4, Fd * 4);
         add(g + S->g_sh_h, 1024, 1024, S->layers, B * 1024);
-        if (S->g_pend2_ok) {
-            const int64_t pb = (int64_t)2 * (kt - 1) * ((Fd + 15) / 16) * 64 * 16;
-            add(g + S->g_pend2, pb, pb);
-            add(g + S->g_par, 1, 1);
-            add(g + S->g_cnt, 4, 4);
-        } else if (kt > 1) {
-            const int64_t wb = (int64_t)(H + 1) * Fd * c.conv_ch * 4;
-            add(g + S->g_c0_win, wb, wb);
-        }
     }
+    ok = stream_convp_rows(S, S->gate_buf != nullptr, R) && ok;
     if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream reset: more state arrays than DFX_ROWS_MAX_ENTRIES");
     return DFX_OK;
 }
@@ -534,7 +544,7 @@ static int stream_gate_alloc(dfx_stream_state *s, const char *who) {
             const int kt = c.df_pathway_kernel_size_t;
             s->g_pend2_ok = kt >= 2 && kt <= 5 && c.conv_ch % 32 == 0 && s->m->fuse_c0 && !s->m->exact_fp32 && s->m->cp_h3;
             if (s->g_pend2_ok) {
-                s->g_pend2 = take((size_t)B * 2 * (kt - 1) * ((c.nb_df + 15) / 16) * 64 * 16);
+                s->g_pend2 = take((size_t)B * stream_pend2_row_bytes(c));
                 s->g_par = take((size_t)B);
                 s->g_cnt = take((size_t)B * 4);
             }
@@ -705,24 +715,225 @@ extern "C" int dfx_stream_get_settings(const dfx_stream_state *s, float *out_hos
     return DFX_OK;
 }
 
-// one call's kernels, enqueued on s (and the model's auxiliary streams); does not advance the handle's counters
-// x / y / lsnr_out rows may be strided (xs, ys, ls; -1: packed): a gated call of n hops is n one-hop passes over the caller's arrays
-static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s, int64_t xs = -1,
-                       int64_t ys = -1, int64_t ls = -1) {
-    const dfx_model *m = S->m;
-    const dfx_state *st = S->st;
-    const dfx_model_cfg &c = m->cfg;
-    const int64_t B = S->B, H = S->H, L = S->L, Hs = H + L, F = st->N / 2 + 1, E = c.nb_erb, Fd = c.nb_df, hop = st->hop, ML = st->N - hop;
-    auto fp = [&](size_t o) { return reinterpret_cast<float *>(S->buf + o); };
-    auto gp = [&](size_t o) { return reinterpret_cast<float *>(S->gate_buf + o); };
-    if (xs < 0) xs = n * hop;
-    if (ys < 0) ys = n * hop;
-    if (ls < 0) ls = n;
-    int rc;
-    // per-stream state forms: gated handles, and pausable ones (there `silence` — the silent-input test and the stage decisions — may be off)
-    const bool silence = S->gated && S->gate_buf, gated = (S->gated || S->pausable) && S->gate_buf;
+// ---- what a pass (DfxStreamPass) and the features-only pass (dfx_stream_process_raw) share: each launch below has this one spelling -------
+static inline float *stream_fp(const dfx_stream_state *S, size_t o) { return reinterpret_cast<float *>(S->buf + o); }
+static inline float *stream_gp(const dfx_stream_state *S, size_t o) { return reinterpret_cast<float *>(S->gate_buf + o); }
+// the buffer that holds the GRU states (other: the one the one-step kernel writes, dfx_k_gru_step_h3)
+static inline float *stream_h(const dfx_stream_state *S, bool other = false) { return stream_fp(S, (S->hflip != 0) != other ? S->h_state2 : S->h_state); }
+
+// The row copies of one array that a pass takes; whoever holds the list decides which stream it is enqueued on.
+struct DfxCopyList {
+    struct Rows { const float *src; int64_t src_stride, src_len, src_off; float *dst; int64_t dst_stride, len; } c[4];
+    int n = 0;
+    void add(const float *src, int64_t src_stride, int64_t src_len, int64_t src_off, float *dst, int64_t dst_stride, int64_t len) {
+        c[n++] = Rows{src, src_stride, src_len, src_off, dst, dst_stride, len};
+    }
+    int emit(int64_t B, hipStream_t on) {
+        for (int i = 0; i < n; ++i)
+            if (int r = stream_copy_rows(c[i].src, c[i].src_stride, c[i].src_len, c[i].src_off, c[i].dst, c[i].dst_stride, c[i].len, B, on)) return r;
+        n = 0;
+        return DFX_OK;
+    }
+};
+
+// Hand-over from the linear windows to the ring form: the windows' last frames become the ring form's history (current parity), listed
+// in the arrays' copy lists.  The feature windows alone (spec: false) when only they change form: the pass-through, whose features do not
+// advance; all three for a path that keeps every window in ring form (dfx_stream_process_raw).
+static void stream_to_ring(dfx_stream_state *S, bool spec, DfxCopyList &cp_spec, DfxCopyList &cp_fe, DfxCopyList &cp_fs) {
+    const int64_t H = S->H, Hs = S->H + S->L, E = S->m->cfg.nb_erb, D2 = S->m->cfg.nb_df * 2, F2 = S->Fp * 2, capf = S->feat_cap;
+    if (S->feat_owns) {
+        cp_fe.add(stream_fp(S, S->fe_lin), capf * E, capf * E, S->lin_pos * E, stream_fp(S, S->hist_fe[S->flip]), H * E, H * E);
+        cp_fs.add(stream_fp(S, S->fs_lin), capf * D2, capf * D2, S->lin_pos * D2, stream_fp(S, S->hist_fs[S->flip]), H * D2, H * D2);
+        S->feat_owns = false;
+    }
+    if (spec && S->lin_owns) {
+        cp_spec.add(stream_fp(S, S->spec_lin), S->lin_cap * F2, S->lin_cap * F2, S->lin_pos * F2, stream_fp(S, S->hist_spec[S->flip]), Hs * F2, Hs * F2);
+        S->lin_owns = false;
+    }
+}
+
+// One step of a history ring: window = [history ; n new frames, the first `skip` of them as zeros], the next call's history (other
+// parity) = its last h frames.
+static int stream_ring_step(const dfx_stream_state *S, const size_t *hist, const float *nw, float *work, int64_t h, int64_t n, int64_t row, int64_t skip,
+                            hipStream_t on) {
+    DfxKScope ks(DFX_K_COPY_ROWS, on);
+    dfx_launch(dfx_k_ring_step, dim3((unsigned)nn_grid(dfx_ceil_div(S->B * (h + n) * row, 256), 16)), dim3(256), 0, on, (const float *)stream_fp(S, hist[S->flip]),
+               nw, work, stream_fp(S, hist[S->flip ^ 1]), S->B, h, n, row, skip);
+    DFX_LAUNCH_CHECK();
+    return DFX_OK;
+}
+
+// The gate of a pass over the handle's per-stream forms.  silence: the handle is gated (else pausable only: every stage runs on every hop).
+static void stream_fill_gate(const dfx_stream_state *S, bool silence, DfxGate &gate) {
+    gate.channels = S->channels;
+    gate.flags = S->gate_buf + S->g_flags;
+    gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
+    if (!silence) gate.thr[0] = -INFINITY, gate.thr[1] = gate.thr[2] = INFINITY;
+    else if (S->thr_rows) gate.thr_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_thr), gate.thr[0] = gate.thr[1] = gate.thr[2] = 0.f;
+    gate.c0_win = stream_gp(S, S->g_c0_win);
+    if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
+}
+
+// After a gated network pass over T frames: the DF decoder's delay line moves where that decoder ran.
+static int stream_commit_delay_line(const dfx_stream_state *S, int64_t T, hipStream_t s) {
+    const dfx_model_cfg &c = S->m->cfg;
+    if (c.df_pathway_kernel_size_t <= 1) return DFX_OK;
+    const unsigned char *gflags = S->gate_buf + S->g_flags;
+    if (S->g_pend2_ok)
+        dfx_launch(dfx_k_gate_pend_commit, dim3((unsigned)dfx_ceil_div(S->B, 256)), dim3(256), 0, s, gflags, S->gate_buf + S->g_par,
+                   reinterpret_cast<int *>(S->gate_buf + S->g_cnt), S->B);
+    else
+        dfx_launch(dfx_k_gate_c0_shift, dim3((unsigned)S->B, 4), dim3(256), 0, s, gflags, stream_gp(S, S->g_c0_win), S->B, T, c.df_pathway_kernel_size_t,
+                   (int64_t)c.nb_df * c.conv_ch);
+    DFX_LAUNCH_CHECK();
+    return DFX_OK;
+}
+
+// Shadow copies of the state a gated pass updates in place, so that the streams that turn out not to advance (frozen, or a decoder stage
+// skipped) can be given their state back after the pass.  h: the GRU states too (the layers run in place).
+static int stream_shadow_state(const dfx_stream_state *S, bool h, hipStream_t s) {
+    const dfx_model_cfg &c = S->m->cfg;
+    DFX_HIP(hipMemcpyAsync(stream_gp(S, S->g_sh_erb), stream_fp(S, S->erb_state), (size_t)S->B * c.nb_erb * 4, hipMemcpyDeviceToDevice, s));
+    DFX_HIP(hipMemcpyAsync(stream_gp(S, S->g_sh_unit), stream_fp(S, S->unit_state), (size_t)S->B * c.nb_df * 4, hipMemcpyDeviceToDevice, s));
+    if (h) DFX_HIP(hipMemcpyAsync(stream_gp(S, S->g_sh_h), stream_h(S), (size_t)S->layers * S->B * 256 * 4, hipMemcpyDeviceToDevice, s));
+    return DFX_OK;
+}
+
+// The double-buffered arrays that a path does not touch keep their contents across the parity flip.
+static int stream_carry_parity(const dfx_stream_state *S, bool ana, bool syn, bool feat, bool spec, hipStream_t s) {
+    const dfx_model_cfg &c = S->m->cfg;
+    const size_t B = (size_t)S->B, ML = (size_t)(S->st->N - S->st->hop);
+    const int f = S->flip;
+    if (ana) DFX_HIP(hipMemcpyAsync(stream_fp(S, S->ana_mem[f ^ 1]), stream_fp(S, S->ana_mem[f]), B * ML * 4, hipMemcpyDeviceToDevice, s));
+    if (syn) DFX_HIP(hipMemcpyAsync(stream_fp(S, S->syn_mem[f ^ 1]), stream_fp(S, S->syn_mem[f]), B * ML * 4, hipMemcpyDeviceToDevice, s));
+    if (feat) {
+        DFX_HIP(hipMemcpyAsync(stream_fp(S, S->hist_fe[f ^ 1]), stream_fp(S, S->hist_fe[f]), B * S->H * c.nb_erb * 4, hipMemcpyDeviceToDevice, s));
+        DFX_HIP(hipMemcpyAsync(stream_fp(S, S->hist_fs[f ^ 1]), stream_fp(S, S->hist_fs[f]), B * S->H * c.nb_df * 8, hipMemcpyDeviceToDevice, s));
+    }
+    if (spec) DFX_HIP(hipMemcpyAsync(stream_fp(S, S->hist_spec[f ^ 1]), stream_fp(S, S->hist_spec[f]), B * (S->H + S->L) * S->Fp * 8, hipMemcpyDeviceToDevice, s));
+    return DFX_OK;
+}
+
+// One pass of n hops over a handle: one call's kernels, enqueued on s (and the model's auxiliary streams).  It does not advance the handle's
+// counters (stream_process_impl).  x / y / lsnr_out rows are strided (xs, ys, ls): a call of several passes walks the caller's arrays.
+// plan() decides everything and does the host bookkeeping of the three windows; the steps after it enqueue, in the order stream_body runs them.
+struct DfxStreamPass {
+    // ---- what stream_body was handed
+    dfx_stream_state *S;
+    const float *x;
+    int64_t n;
+    float *y, *lsnr_out;
+    hipStream_t s;
+    int64_t xs, ys, ls;
+    bool p_mixed, p_warm;   // streams that started over on their own: one that takes part is younger than the window / than the lookahead
+    const dfx_model_cfg &c;
+    // ---- the plan (plan())
+    const dfx_model *m;
+    const dfx_state *st;
+    int64_t B, H, L, Hs, E, Fd, D2, hop, ML, Fp, F2, capf, T, a0, skip, lin_pos0;
+    bool silence, gated, bypass, lin, flin, mixed, warm, step_all;
+    unsigned char *gflags;
+    int *gcount;
+    float *am_in, *am_out, *sm_in, *sm_out, *new_spec, *new_fe, *new_fs, *work_fe, *work_fs, *work_spec, *out_spec;
+    const float *spec_win, *fe_win, *fs_win;   // the windows the network reads ...
+    int64_t spec_win_T, feat_T;                // ... and their clip strides in frames (feat_T 0: T)
+    float *norm_fe, *norm_fs;                  // where the normalised features of the new hops go
+    int64_t norm_fe_cs, norm_fs_cs;
+    DfxCopyList cp_spec, cp_fe, cp_fs;         // the copies of this pass, by array
+    // ---- what the enqueue has done
+    bool stepped = false, erb_done = false, side_done = false;
+
+    float *fp(size_t o) const { return stream_fp(S, o); }
+    float *gp(size_t o) const { return stream_gp(S, o); }
+
+    int plan() {
+        m = S->m, st = S->st;
+        B = S->B, H = S->H, L = S->L, Hs = H + L, E = c.nb_erb, Fd = c.nb_df, D2 = Fd * 2, hop = st->hop, ML = st->N - hop;
+        Fp = S->Fp, F2 = Fp * 2;   // the handle's spectra have rows of Fp >= F bins
+        capf = S->feat_cap, T = H + n, a0 = S->frames;
+        // per-stream state forms: gated handles, and pausable ones (there `silence` — the silent-input test and the stage decisions — may be off)
+        silence = S->gated && S->gate_buf, gated = (S->gated || S->pausable) && S->gate_buf;
+        if (gated && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "gated streaming passes carry one hop");
+        gflags = gated ? S->gate_buf + S->g_flags : nullptr;
+        gcount = gated ? reinterpret_cast<int *>(S->gate_buf + S->g_counter) : nullptr;
+        bypass = S->lim == 1.f;   // the pass-through (tract.rs:540-543)
+        // ---- windows: [history ; new].  Net position p uses the features of hop p + L, so the hops of this call are the positions
+        // a0 - L .. a0 + n - 1 - L; positions < 0 do not exist: their features are zero for the taps of later positions (the causal
+        // padding of pad_feat, deepfilternet3.py:357-361) and they are not computed.
+        skip = a0 < L ? ((L - a0) < n ? (L - a0) : n) : 0;
+        // one new hop, plain launches: every GRU layer is ONE launch (projection + recurrence + gates) that leaves the new states in the
+        // other buffer (several new hops: the projection and the recurrence kernel of the batch path, in place)
+        step_all = n - skip == 1;
+        // streams that started over on their own (dfx_stream_reset_streams): mixed — one of them is still younger than the window, the pass takes
+        // t_zero per stream; warm — one of them is younger than the lookahead (the caller passes one hop at a time then): dfx_k_stream_warm
+        mixed = !bypass && skip < n && p_mixed, warm = mixed && p_warm;
+        if (warm && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "warm-up hops of a reset stream are passed one at a time");
+        am_in = fp(S->ana_mem[S->flip]), am_out = fp(S->ana_mem[S->flip ^ 1]);
+        sm_in = fp(S->syn_mem[S->flip]), sm_out = fp(S->syn_mem[S->flip ^ 1]);
+        new_spec = fp(S->new_spec), new_fe = fp(S->new_fe), new_fs = fp(S->new_fs);
+        work_fe = fp(S->work_fe), work_fs = fp(S->work_fs), work_spec = fp(S->work_spec), out_spec = fp(S->out_spec);
+        plan_windows();
+        return DFX_OK;
+    }
+
+    // Host bookkeeping of the three windows for this pass: which form owns the state, where the windows are, the copies the pass needs
+    // (listed in cp_spec / cp_fe / cp_fs; erb_window / df_window / spec_window enqueue them).  Every change of lin_pos / lin_owns / feat_owns
+    // of a pass is made here (this form is never replayed from a graph nor walked hop by hop by the caller).
+    void plan_windows() {
+        // Rolling spectra: linear (sliding window, see dfx_stream_state::spec_lin) or ring; a handle has one of them for good (lin), so only
+        // dfx_stream_process_raw ever takes the state back to the ring form.
+        lin = S->lin_cap > 0;
+        // The feature windows of the encoder take the same form when the kernels that read them accept a clip stride (the fp16-split DF
+        // encoder: DfxC01hArgs::feat_T): [B, feat_cap, E] and [B, feat_cap, Fd, 2] with the same slack as the spectra, so that all three
+        // windows sit at lin_pos and go back to the front in the same call.  feat_owns: the linear form holds the feature history.
+        const bool feat_lin_ok = lin && capf > 0 && m->fuse_c0 && !m->exact_fp32 && c.conv_ch % 32 == 0 && m->cp_h3;
+        flin = feat_lin_ok && !bypass && skip == 0;   // (warm-up hops zero their features: the ring step does that)
+        // (pass-through: the features do not advance, their history waits in the ring form)
+        if (!flin) stream_to_ring(S, false, cp_spec, cp_fe, cp_fs);
+        spec_win = work_spec, spec_win_T = Hs + n;
+        if (lin) {
+            float *L0 = fp(S->spec_lin);
+            const int64_t cap = S->lin_cap;
+            if (!S->lin_owns) {   // the ring form's history becomes the window's first Hs frames
+                cp_spec.add(fp(S->hist_spec[S->flip]), Hs * F2, Hs * F2, 0, L0, cap * F2, Hs * F2);
+                S->lin_pos = 0;
+                S->lin_owns = true;
+            } else if (S->lin_pos + Hs + n > cap) {   // the windows have reached the end: their last frames go back to the front (no overlap: lin_pos >= Hs)
+                cp_spec.add(L0, cap * F2, cap * F2, S->lin_pos * F2, L0, cap * F2, Hs * F2);
+                if (S->feat_owns) {
+                    cp_fe.add(fp(S->fe_lin), capf * E, capf * E, S->lin_pos * E, fp(S->fe_lin), capf * E, H * E);
+                    cp_fs.add(fp(S->fs_lin), capf * D2, capf * D2, S->lin_pos * D2, fp(S->fs_lin), capf * D2, H * D2);
+                }
+                S->lin_pos = 0;
+            }
+            cp_spec.add(new_spec, n * F2, n * F2, 0, L0 + (S->lin_pos + Hs) * F2, cap * F2, n * F2);
+            spec_win = L0 + S->lin_pos * F2, spec_win_T = cap;
+        }
+        fe_win = work_fe, fs_win = work_fs, feat_T = 0;
+        norm_fe = new_fe, norm_fs = new_fs, norm_fe_cs = norm_fs_cs = 0;
+        if (flin) {
+            float *Lfe = fp(S->fe_lin), *Lfs = fp(S->fs_lin);
+            if (!S->feat_owns) {   // the ring form's history becomes the windows' first H frames
+                cp_fe.add(fp(S->hist_fe[S->flip]), H * E, H * E, 0, Lfe + S->lin_pos * E, capf * E, H * E);
+                cp_fs.add(fp(S->hist_fs[S->flip]), H * D2, H * D2, 0, Lfs + S->lin_pos * D2, capf * D2, H * D2);
+                S->feat_owns = true;
+            }
+            fe_win = Lfe + S->lin_pos * E, fs_win = Lfs + S->lin_pos * D2;
+            feat_T = capf;
+            if (n < 16) {   // the norms write the new frames straight into the windows (no append copies)
+                norm_fe = Lfe + (S->lin_pos + H) * E, norm_fs = Lfs + (S->lin_pos + H) * D2;
+                norm_fe_cs = capf * E, norm_fs_cs = capf * D2;
+            } else {
+                cp_fe.add(new_fe, n * E, n * E, 0, Lfe + (S->lin_pos + H) * E, capf * E, n * E);
+                cp_fs.add(new_fs, n * D2, n * D2, 0, Lfs + (S->lin_pos + H) * D2, capf * D2, n * D2);
+            }
+        }
+        lin_pos0 = S->lin_pos;   // where this pass's windows are
+        if (lin) S->lin_pos += n;
+    }
+
     // pausable handles: this pass's paused rows are flagged behind dfx_k_gate_pre (bump: the hops by which the handle's count will advance)
-    auto pause_rows = [&](hipStream_t on, int bump) -> int {
+    int pause_rows(int bump) {
         if (!S->pausable || (silence && !S->any_paused)) return DFX_OK;
         const int ch = S->channels;
         const int64_t ns = B / ch;
@@ -735,251 +946,101 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
                 for (int k = 0; k < P.n; ++k)
                     if (S->paused[(size_t)(k0 + k)]) P.bits[k >> 5] |= 1u << (k & 31), any = true;
             if (!any && silence) continue;
-            dfx_launch(dfx_k_stream_pause, dim3((unsigned)dfx_ceil_div((int64_t)P.n * ch, 256)), dim3(256), 0, on, P, ch, S->gate_buf + S->g_flags, (int)!silence,
-                       reinterpret_cast<int *>(S->gate_buf + S->g_counter),
+            dfx_launch(dfx_k_stream_pause, dim3((unsigned)dfx_ceil_div((int64_t)P.n * ch, 256)), dim3(256), 0, s, P, ch, gflags, (int)!silence, gcount,
                        silence ? (const int *)reinterpret_cast<int *>(S->gate_buf + S->g_sh_counter) : (const int *)nullptr,
                        reinterpret_cast<int64_t *>(S->buf + S->birth_dev), bump);
             DFX_LAUNCH_CHECK();
         }
         return DFX_OK;
-    };
-    auto gate_pre = [&](hipStream_t on) -> int {   // the silent-input test of the pass (gated handles), then the rows that sit it out
+    }
+
+    // Per-stream forms only: the silent-input test of the pass (gated handles; tract.rs:513-525), the rows that sit it out, and — unless the
+    // pass-through follows, which leaves that state alone — the shadow copies of the in-place state.
+    int open_gate() {
+        if (!gated) return DFX_OK;
         if (silence) {
             if (S->pausable && S->any_paused)
-                DFX_HIP(hipMemcpyAsync(S->gate_buf + S->g_sh_counter, S->gate_buf + S->g_counter, (size_t)B * 4, hipMemcpyDeviceToDevice, on));
-            if (int r = launch_gate_pre(x, xs, (int)hop, B, reinterpret_cast<int *>(S->gate_buf + S->g_counter), S->gate_buf + S->g_flags, S->channels, on)) return r;
+                DFX_HIP(hipMemcpyAsync(S->gate_buf + S->g_sh_counter, S->gate_buf + S->g_counter, (size_t)B * 4, hipMemcpyDeviceToDevice, s));
+            if (int r = launch_gate_pre(x, xs, (int)hop, B, gcount, gflags, S->channels, s)) return r;
         }
-        return pause_rows(on, S->lim != 1.f ? 1 : 0);
-    };
-    if (gated && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "gated streaming passes carry one hop");
-    // ---- rolling spectra: linear (sliding window, see dfx_stream_state::spec_lin) or ring.  spec_window() brings the form this call uses
-    // up to date with the other one if that one holds the state, appends the call's new frames and returns the window [Hs + n frames]
-    // and the clip stride (in frames) the deep filter has to use.
-    const bool lin = S->lin_cap > 0;
-    const int64_t Fp = S->Fp, F2 = Fp * 2;   // the handle's spectra have rows of Fp >= F bins
-    // The feature windows of the encoder take the same form when the kernels that read them accept a clip stride (the fp16-split DF
-    // encoder: DfxC01hArgs::feat_T): [B, feat_cap, E] and [B, feat_cap, Fd, 2] with the same slack as the spectra, so that all three
-    // windows sit at lin_pos and go back to the front in the same call.  feat_owns: the linear form holds the feature history.
-    const bool feat_lin_ok = lin && S->feat_cap > 0 && m->fuse_c0 && !m->exact_fp32 && c.conv_ch % 32 == 0 && m->cp_h3;
-    struct RowCopy { const float *src; int64_t src_stride, src_len, src_off; float *dst; int64_t dst_stride, len; };
-    struct CopyList {
-        RowCopy c[4];
-        int n = 0;
-        void add(const float *src, int64_t src_stride, int64_t src_len, int64_t src_off, float *dst, int64_t dst_stride, int64_t len) {
-            c[n++] = RowCopy{src, src_stride, src_len, src_off, dst, dst_stride, len};
-        }
-    } cp_spec, cp_fe, cp_fs;   // the copies of this call, by array: the caller decides which stream each list is enqueued on
-    auto emit = [&](CopyList &l, hipStream_t on) -> int {
-        for (int i = 0; i < l.n; ++i)
-            if (int r = stream_copy_rows(l.c[i].src, l.c[i].src_stride, l.c[i].src_len, l.c[i].src_off, l.c[i].dst, l.c[i].dst_stride, l.c[i].len, B, on)) return r;
-        l.n = 0;
-        return DFX_OK;
-    };
-    const int64_t capf = S->feat_cap, E1 = E, D2 = Fd * 2;
-    auto hold = [&](float *win, int64_t cap, int64_t row, int64_t pos, int64_t h, hipStream_t on) -> int {   // frozen streams keep their history (dfx_k_gate_hold)
-        dfx_launch(dfx_k_gate_hold, dim3((unsigned)B, (unsigned)(row > 1024 ? 4 : 1)), dim3(256), 0, on, (const unsigned char *)(S->gate_buf + S->g_flags), win,
-                   cap, row, pos, h, B);
+        if (int r = pause_rows(bypass ? 0 : 1)) return r;
+        // (the GRU states: only when the layers run in place — the one-step kernel leaves the old states in the other buffer)
+        return bypass ? DFX_OK : stream_shadow_state(S, !step_all, s);
+    }
+
+    // who keeps which state (dfx_k_gate_commit), then the frozen streams' answer and the skip counters
+    int close_gate(const DfxGateTable &G, bool undecided) {
+        dfx_launch(dfx_k_gate_commit, dim3((unsigned)B), dim3(128), 0, s, G, (const unsigned char *)gflags, B);
+        DFX_LAUNCH_CHECK();
+        dfx_launch(dfx_k_gate_finish, dim3((unsigned)B), dim3(128), 0, s, (const unsigned char *)gflags, gcount, y, ys, (int)hop, lsnr_out, ls, B, (int)undecided);
         DFX_LAUNCH_CHECK();
         return DFX_OK;
-    };
-    auto feat_to_ring = [&]() {   // the feature windows' last H frames become the ring form's history
-        cp_fe.add(fp(S->fe_lin), capf * E1, capf * E1, S->lin_pos * E1, fp(S->hist_fe[S->flip]), H * E1, H * E1);
-        cp_fs.add(fp(S->fs_lin), capf * D2, capf * D2, S->lin_pos * D2, fp(S->hist_fs[S->flip]), H * D2, H * D2);
-        S->feat_owns = false;
-    };
-    // spec_window(): host-side bookkeeping of the rolling spectra for this call (which form, where the window is) with the copies it takes
-    // listed in cp_spec (and, when the windows go back to the front, in cp_fe / cp_fs); the ring form is stepped on `s` right away.
-    // The caller advances lin_pos by n when it is done with the windows.
-    const float *spec_ring_src = nullptr;
-    auto spec_window = [&](const float *new_spec, const float **win, int64_t *win_T) -> int {
-        if (lin) {
-            float *L0 = fp(S->spec_lin);
-            const int64_t cap = S->lin_cap;
-            if (!S->lin_owns) {   // the ring form's history becomes the window's first Hs frames
-                cp_spec.add(fp(S->hist_spec[S->flip]), Hs * F2, Hs * F2, 0, L0, cap * F2, Hs * F2);
-                S->lin_pos = 0;
-                S->lin_owns = true;
-            } else if (S->lin_pos + Hs + n > cap) {   // the windows have reached the end: their last frames go back to the front (no overlap: lin_pos >= Hs)
-                cp_spec.add(L0, cap * F2, cap * F2, S->lin_pos * F2, L0, cap * F2, Hs * F2);
-                if (S->feat_owns) {
-                    cp_fe.add(fp(S->fe_lin), capf * E1, capf * E1, S->lin_pos * E1, fp(S->fe_lin), capf * E1, H * E1);
-                    cp_fs.add(fp(S->fs_lin), capf * D2, capf * D2, S->lin_pos * D2, fp(S->fs_lin), capf * D2, H * D2);
-                }
-                S->lin_pos = 0;
-            }
-            cp_spec.add(new_spec, n * F2, n * F2, 0, L0 + (S->lin_pos + Hs) * F2, cap * F2, n * F2);
-            *win = L0 + S->lin_pos * F2;
-            *win_T = cap;
-            return DFX_OK;
-        }
-        if (S->lin_owns) {   // back to the ring form (gating was switched on): the windows' last frames are its history
-            if (S->feat_owns) feat_to_ring();
-            cp_spec.add(fp(S->spec_lin), S->lin_cap * F2, S->lin_cap * F2, S->lin_pos * F2, fp(S->hist_spec[S->flip]), Hs * F2, Hs * F2);
-            S->lin_owns = false;
-            int r;
-            if ((r = emit(cp_spec, s)) || (r = emit(cp_fe, s)) || (r = emit(cp_fs, s))) return r;
-        }
-        spec_ring_src = new_spec;   // the ring step itself is enqueued by spec_ring(): like the copies, where the caller wants it
-        *win = fp(S->work_spec);
-        *win_T = Hs + n;
-        return DFX_OK;
-    };
-    auto spec_ring = [&](hipStream_t on) -> int {
-        if (!spec_ring_src) return DFX_OK;
-        DfxKScope ks(DFX_K_COPY_ROWS, on);
-        dfx_launch(dfx_k_ring_step, dim3((unsigned)nn_grid(dfx_ceil_div(B * (Hs + n) * F2, 256), 16)), dim3(256), 0, on,
-                   (const float *)fp(S->hist_spec[S->flip]), spec_ring_src, fp(S->work_spec), fp(S->hist_spec[S->flip ^ 1]), B, Hs, n, F2, (int64_t)0);
-        DFX_LAUNCH_CHECK();
-        spec_ring_src = nullptr;
-        return DFX_OK;
-    };
-    if (S->lim == 1.f) {
-        // tract.rs:509-543 with atten_lim == 1: the silent-input counter, the STFT analysis and the rolling spectra still advance (so
-        // that switching the limit back mid-stream continues from the right history); features, network and synthesis do not run, the
-        // hop is passed through undelayed with lsnr = 35 — unless the stream has been silent for more than 5 hops (zeros, -15).
-        unsigned char *gflags = gated ? S->gate_buf + S->g_flags : nullptr;
-        if (gated && (rc = gate_pre(s))) return rc;
-        float *am_in = fp(S->ana_mem[S->flip]), *am_out = fp(S->ana_mem[S->flip ^ 1]);
-        float *new_spec = fp(S->new_spec);
+    }
+
+    // tract.rs:509-543 with atten_lim == 1: the silent-input counter, the STFT analysis and the rolling spectra still advance (so
+    // that switching the limit back mid-stream continues from the right history); features, network and synthesis do not run, the
+    // hop is passed through undelayed with lsnr = 35 — unless the stream has been silent for more than 5 hops (zeros, -15).
+    int pass_through() {
+        int rc;
         if ((rc = dfx_launch_analysis(st, x, B, n * hop, xs, am_in, am_out, new_spec, nullptr, s, -1, Fp))) return rc;
-        {
-            const float *win = nullptr;
-            int64_t win_T = 0;
-            if (S->feat_owns) feat_to_ring();   // (the features do not advance here: their history waits in the ring form)
-            if ((rc = spec_window(new_spec, &win, &win_T)) || (rc = emit(cp_fe, s)) || (rc = emit(cp_fs, s)) || (rc = emit(cp_spec, s)) || (rc = spec_ring(s))) return rc;
-            if (gated && lin && (rc = hold(fp(S->spec_lin), S->lin_cap, F2, S->lin_pos, Hs, s))) return rc;
-            if (lin) S->lin_pos += n;
-        }
-        // what this path does not touch keeps its contents across the parity flip
-        DFX_HIP(hipMemcpyAsync(fp(S->syn_mem[S->flip ^ 1]), fp(S->syn_mem[S->flip]), (size_t)B * ML * 4, hipMemcpyDeviceToDevice, s));
-        DFX_HIP(hipMemcpyAsync(fp(S->hist_fe[S->flip ^ 1]), fp(S->hist_fe[S->flip]), (size_t)B * H * E * 4, hipMemcpyDeviceToDevice, s));
-        DFX_HIP(hipMemcpyAsync(fp(S->hist_fs[S->flip ^ 1]), fp(S->hist_fs[S->flip]), (size_t)B * H * Fd * 8, hipMemcpyDeviceToDevice, s));
+        if ((rc = erb_window(s)) || (rc = df_window(s)) || (rc = spec_window(s))) return rc;
+        if ((rc = stream_carry_parity(S, false, true, true, false, s))) return rc;
         if ((rc = stream_copy_rows(x, xs, n * hop, 0, y, ys, n * hop, B, s))) return rc;
         if (lsnr_out) {
             dfx_launch(dfx_k_fill_rows, dim3((unsigned)nn_grid(dfx_ceil_div(B * n, 256), 16)), dim3(256), 0, s, lsnr_out, ls, n, B, 35.f);
             DFX_LAUNCH_CHECK();
         }
-        if (gated) {  // frozen streams: zeros / -15, and their analysis memory and rolling spectra stay where they were
-            DfxGateTable G;
-            G.n = 0;
-            const unsigned char FZ = DFX_GATE_FROZEN;
-            G.dst[0] = am_out, G.src[0] = am_in, G.row[0] = ML, G.mask[0] = FZ, G.want[0] = FZ;
-            G.dst[1] = fp(S->hist_spec[S->flip ^ 1]), G.src[1] = fp(S->hist_spec[S->flip]), G.row[1] = Hs * F2, G.mask[1] = FZ, G.want[1] = FZ;
-            G.n = lin ? 1 : 2;   // (linear window: dfx_k_gate_hold above)
-            dfx_launch(dfx_k_gate_commit, dim3((unsigned)B), dim3(128), 0, s, G, (const unsigned char *)gflags, B);
-            DFX_LAUNCH_CHECK();
-            dfx_launch(dfx_k_gate_finish, dim3((unsigned)B), dim3(128), 0, s, (const unsigned char *)gflags,
-                       reinterpret_cast<int *>(S->gate_buf + S->g_counter), y, ys, (int)hop, lsnr_out, ls, B, 1 /* no stage decision was taken */);
-            DFX_LAUNCH_CHECK();
-        }
+        if (!gated) return DFX_OK;
+        // frozen streams: zeros / -15, and their analysis memory and rolling spectra stay where they were
+        DfxGateTable G;
+        G.n = 0;
+        G.add(am_out, am_in, ML, DFX_GATE_FROZEN, DFX_GATE_FROZEN);
+        if (!lin) G.add(fp(S->hist_spec[S->flip ^ 1]), fp(S->hist_spec[S->flip]), Hs * F2, DFX_GATE_FROZEN, DFX_GATE_FROZEN);   // (linear window: dfx_k_gate_hold)
+        return close_gate(G, true /* no stage decision was taken */);
+    }
+
+    // ---- STFT + features of the n new hops (state: analysis memory, running means)
+    int features() {
+        int rc;
+        if ((rc = dfx_launch_analysis(st, x, B, n * hop, xs, am_in, nullptr, new_spec, new_fe, s, -1, Fp))) return rc;   // (am_out: spec_window)
+        if ((rc = dfx_launch_norm_scan(new_fe, norm_fe, (int)E, new_spec, Fp, norm_fs, (int)Fd, B, n, c.norm_alpha, fp(S->erb_state), fp(S->unit_state), s,
+                                       norm_fe_cs, norm_fs_cs)))
+            return rc;
+        if (skip > 0) DFX_HIP(hipMemsetAsync(out_spec, 0, (size_t)B * n * Fp * 8, s));  // warm-up hops: zero spectra (tract.rs rolling buffers)
         return DFX_OK;
     }
-    unsigned char *gflags = gated ? S->gate_buf + S->g_flags : nullptr;
-    int *gcount = gated ? reinterpret_cast<int *>(S->gate_buf + S->g_counter) : nullptr;
-    // one new hop, plain launches: every GRU layer is ONE launch (projection + recurrence + gates) that leaves the new states in the
-    // other buffer (several new hops: the projection and the recurrence kernel of the batch path, in place)
-    const int64_t skip_early = S->frames < L ? ((L - S->frames) < n ? (L - S->frames) : n) : 0;
-    const bool step_all = n - skip_early == 1;
-    if (gated) {
-        // silent-input shortcut (tract.rs:513-525) + a copy of the in-place state, so that the streams that turn out not to advance
-        // (frozen, or a decoder stage skipped) can be given their state back after the pass
-        if ((rc = gate_pre(s))) return rc;
-        DFX_HIP(hipMemcpyAsync(gp(S->g_sh_erb), fp(S->erb_state), (size_t)B * E * 4, hipMemcpyDeviceToDevice, s));
-        DFX_HIP(hipMemcpyAsync(gp(S->g_sh_unit), fp(S->unit_state), (size_t)B * Fd * 4, hipMemcpyDeviceToDevice, s));
-        // (the GRU states: only when the layers run in place — the one-step kernel leaves the old states in the other buffer)
-        if (!step_all) DFX_HIP(hipMemcpyAsync(gp(S->g_sh_h), fp(S->hflip ? S->h_state2 : S->h_state), (size_t)S->layers * B * 256 * 4, hipMemcpyDeviceToDevice, s));
-    }
-    // ---- STFT + features of the n new hops (state: analysis memory, running means)
-    float *am_in = fp(S->ana_mem[S->flip]), *am_out = fp(S->ana_mem[S->flip ^ 1]);
-    float *sm_in = fp(S->syn_mem[S->flip]), *sm_out = fp(S->syn_mem[S->flip ^ 1]);
-    float *new_spec = fp(S->new_spec), *new_fe = fp(S->new_fe), *new_fs = fp(S->new_fs);
-    // The linear form: what only the DF branch needs (the DF feature window) is enqueued on that branch's stream (DfxStreamCtx::df_pre), what
-    // only the final deep filter or the NEXT call needs (the spectrum window, the analysis memory) behind df_convp on its stream
-    // (DfxStreamCtx::df_post) — in front of the encoder these four small launches were 40 us of a 520 us hop at 4096 streams
-    constexpr bool side_env = true;
-    const bool side = side_env;   // (either form of the windows: the ring steps are deferred like the copies)
-    if ((rc = dfx_launch_analysis(st, x, B, n * hop, xs, am_in, side ? nullptr : am_out, new_spec, new_fe, s, -1, Fp))) return rc;
-    // ---- windows: [history ; new].  Net position p uses the features of hop p + L, so the hops of this call are the positions
-    // a0 - L .. a0 + n - 1 - L; positions < 0 do not exist: their features are zero for the taps of later positions (the causal
-    // padding of pad_feat, deepfilternet3.py:357-361) and they are not computed.
-    const int64_t a0 = S->frames, T = H + n;
-    const int64_t skip = a0 < L ? ((L - a0) < n ? (L - a0) : n) : 0;
-    // streams that started over on their own (dfx_stream_reset_streams): mixed — one of them is still younger than the window, the pass takes
-    // t_zero per stream; warm — one of them is younger than the lookahead (the caller passes one hop at a time then): dfx_k_stream_warm
-    // (pausable handles: decided per pass from the ages of the streams that take part — stream_process_impl)
-    const bool mixed = skip < n && (S->pausable ? S->p_mixed : a0 < S->mixed_until), warm = mixed && (S->pausable ? S->p_warm : a0 < S->warm_until);
-    if (warm && n != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "warm-up hops of a reset stream are passed one at a time");
-    float *work_fe = fp(S->work_fe), *work_fs = fp(S->work_fs), *work_spec = fp(S->work_spec);
-    struct Ring { size_t *hist; float *nw, *work; int64_t h, row; bool zero_skipped; } rings[2] = {
-        {S->hist_fe, new_fe, work_fe, H, E, true}, {S->hist_fs, new_fs, work_fs, H, Fd * 2, true}};
-    const float *spec_win = work_spec;
-    int64_t spec_win_T = Hs + n;
-    auto ring_step = [&](const Ring &r, hipStream_t on) -> int {  // window = [history ; new], next call's history = its last h frames
-        DfxKScope ks(DFX_K_COPY_ROWS, on);
-        dfx_launch(dfx_k_ring_step, dim3((unsigned)nn_grid(dfx_ceil_div(B * (r.h + n) * r.row, 256), 16)), dim3(256), 0, on,
-                   (const float *)fp(r.hist[S->flip]), (const float *)r.nw, r.work, fp(r.hist[S->flip ^ 1]), B, r.h, n, r.row,
-                   r.zero_skipped ? skip : (int64_t)0);
+
+    // ---- the three windows' enqueue steps.  What only the DF branch needs (the DF feature window) is enqueued on that branch's stream
+    // (DfxStreamCtx::df_pre), what only the final deep filter or the NEXT call needs (the spectrum window, the analysis memory) behind df_convp
+    // on its stream (DfxStreamCtx::df_post) — in front of the encoder these four small launches were 40 us of a 520 us hop at 4096 streams.
+    // A pass that runs no network (warm-up hops, the pass-through) enqueues them itself.
+    int hold(float *win, int64_t cap, int64_t row, int64_t h, hipStream_t on) {   // frozen streams keep their history (dfx_k_gate_hold)
+        dfx_launch(dfx_k_gate_hold, dim3((unsigned)B, (unsigned)(row > 1024 ? 4 : 1)), dim3(256), 0, on, (const unsigned char *)gflags, win, cap, row, lin_pos0, h, B);
         DFX_LAUNCH_CHECK();
         return DFX_OK;
-    };
-    // settle the three windows (host side), then enqueue their copies / ring steps: on s, or — side — on the streams that need them
-    if ((rc = spec_window(new_spec, &spec_win, &spec_win_T))) return rc;
-    const bool flin = feat_lin_ok && skip == 0;   // (warm-up hops zero their features: the ring step does that)
-    const float *fe_win = work_fe, *fs_win = work_fs;
-    int64_t feat_T = 0;
-    float *norm_fe = new_fe, *norm_fs = new_fs;   // where the normalised features of the new hops go
-    int64_t norm_fe_cs = 0, norm_fs_cs = 0;
-    if (flin) {
-        float *Lfe = fp(S->fe_lin), *Lfs = fp(S->fs_lin);
-        if (!S->feat_owns) {   // the ring form's history becomes the windows' first H frames
-            cp_fe.add(fp(S->hist_fe[S->flip]), H * E1, H * E1, 0, Lfe + S->lin_pos * E1, capf * E1, H * E1);
-            cp_fs.add(fp(S->hist_fs[S->flip]), H * D2, H * D2, 0, Lfs + S->lin_pos * D2, capf * D2, H * D2);
-            S->feat_owns = true;
-        }
-        fe_win = Lfe + S->lin_pos * E1, fs_win = Lfs + S->lin_pos * D2;
-        feat_T = capf;
-        if (n < 16) {   // the norms write the new frames straight into the windows (no append copies)
-            norm_fe = Lfe + (S->lin_pos + H) * E1, norm_fs = Lfs + (S->lin_pos + H) * D2;
-            norm_fe_cs = capf * E1, norm_fs_cs = capf * D2;
-        } else {
-            cp_fe.add(new_fe, n * E1, n * E1, 0, Lfe + (S->lin_pos + H) * E1, capf * E1, n * E1);
-            cp_fs.add(new_fs, n * D2, n * D2, 0, Lfs + (S->lin_pos + H) * D2, capf * D2, n * D2);
-        }
-    } else if (S->feat_owns) {
-        feat_to_ring();
     }
-    // features of the new hops (state: the running means)
-    if ((rc = dfx_launch_norm_scan(new_fe, norm_fe, (int)E, new_spec, Fp, norm_fs, (int)Fd, B, n, c.norm_alpha, fp(S->erb_state), fp(S->unit_state), s,
-                                   norm_fe_cs, norm_fs_cs)))
-        return rc;
-    const int64_t lin_pos0 = S->lin_pos;
-    if (lin) S->lin_pos += n;   // (advanced here: this form is never replayed from a graph nor walked hop by hop by the caller)
-    bool side_done = false, erb_done = false;
-    std::function<int(hipStream_t)> side_pre, side_post, erb_ring;
-    erb_ring = [&](hipStream_t on) -> int {
+    int feat_window(DfxCopyList &cp, const size_t *hist, const float *nw, float *work, float *lin_buf, int64_t row, hipStream_t on) {
+        if (int r = cp.emit(B, on)) return r;
+        if (bypass) return DFX_OK;
+        if (!flin) return stream_ring_step(S, hist, nw, work, H, n, row, skip, on);
+        return gated ? hold(lin_buf, capf, row, H, on) : DFX_OK;
+    }
+    int erb_window(hipStream_t on) {
         erb_done = true;
-        if (int r = emit(cp_fe, on)) return r;
-        if (!flin) return ring_step(rings[0], on);
-        return gated ? hold(fp(S->fe_lin), capf, E1, lin_pos0, H, on) : DFX_OK;
-    };
-    side_pre = [&](hipStream_t on) -> int {
-        if (int r = emit(cp_fs, on)) return r;
-        if (!flin) return ring_step(rings[1], on);
-        return gated ? hold(fp(S->fs_lin), capf, D2, lin_pos0, H, on) : DFX_OK;
-    };
-    side_post = [&](hipStream_t on) -> int {
+        return feat_window(cp_fe, S->hist_fe, new_fe, work_fe, fp(S->fe_lin), E, on);
+    }
+    int df_window(hipStream_t on) { return feat_window(cp_fs, S->hist_fs, new_fs, work_fs, fp(S->fs_lin), D2, on); }
+    int spec_window(hipStream_t on) {
         side_done = true;
-        if (int r = emit(cp_spec, on)) return r;
-        if (int r = spec_ring(on)) return r;
+        if (int r = cp_spec.emit(B, on)) return r;
+        if (!lin)
+            if (int r = stream_ring_step(S, S->hist_spec, new_spec, work_spec, Hs, n, F2, 0, on)) return r;
         if (gated && lin)
-            if (int r = hold(fp(S->spec_lin), S->lin_cap, F2, lin_pos0, Hs, on)) return r;
-        return side ? dfx_launch_analysis_mem(st, x, B, n * hop, xs, am_in, am_out, on) : DFX_OK;
-    };
-    if (!side && ((rc = side_post(s)) || (rc = erb_ring(s)) || (rc = side_pre(s)))) return rc;
-    float *out_spec = fp(S->out_spec);
-    if (skip > 0) DFX_HIP(hipMemsetAsync(out_spec, 0, (size_t)B * n * Fp * 8, s));  // warm-up hops: zero spectra (tract.rs rolling buffers)
-    bool stepped = false;
-    if (skip < n) {
+            if (int r = hold(fp(S->spec_lin), S->lin_cap, F2, Hs, on)) return r;
+        return bypass ? DFX_OK : dfx_launch_analysis_mem(st, x, B, n * hop, xs, am_in, am_out, on);   // (the pass-through's analysis wrote am_out)
+    }
+
+    int network() {
         DfxStreamCtx sc;
         sc.H = H + skip;
         const int64_t pos0 = Hs - a0;  // local index of net position 0
@@ -994,17 +1055,18 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         sc.spec_T = spec_win_T;
         sc.spec_stride = Fp;
         sc.feat_T = feat_T;
-        sc.h_state = fp(S->hflip ? S->h_state2 : S->h_state);
-        const bool step = step_all;
-        sc.h_next = step ? fp(S->hflip ? S->h_state : S->h_state2) : nullptr;
-        stepped = step;
-        if (step && !gated && S->c0ring_bytes) {   // df_convp from its pending sums (dfx_k_df_convp_step; a gated handle keeps its per-stream delay line)
+        sc.h_state = stream_h(S);
+        sc.h_next = step_all ? stream_h(S, true) : nullptr;
+        stepped = step_all;
+        if (step_all && !gated && S->c0ring_bytes) {   // df_convp from its pending sums (dfx_k_df_convp_step; a gated handle keeps its per-stream delay line)
             const int ns = c.df_pathway_kernel_size_t - 1;
             sc.c0ring = S->buf + S->c0ring;
             sc.c0slot = (int)((((a0 + skip - L) % ns) + ns) % ns);
             sc.c0rebuild = !S->c0ring_ok;
         }
-        if (side) sc.erb_pre = erb_ring, sc.df_pre = side_pre, sc.df_post = side_post;
+        sc.erb_pre = [this](hipStream_t on) { return erb_window(on); };
+        sc.df_pre = [this](hipStream_t on) { return df_window(on); };
+        sc.df_post = [this](hipStream_t on) { return spec_window(on); };
         sc.pf_beta = S->pf_beta;
         if (S->lim_rows) sc.lim_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_lim);     // per-stream settings: the finishing kernel
         if (S->beta_rows) sc.beta_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_beta);  //   takes each row's own values
@@ -1015,107 +1077,83 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
         sc.reduce_mask = S->reduce_mask;
         DfxGate gate;
         if (gated) {
-            gate.channels = S->channels;
-            gate.flags = gflags;
-            gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
-            if (!silence) gate.thr[0] = -INFINITY, gate.thr[1] = gate.thr[2] = INFINITY;   // pausable, not gated: every stage runs on every hop
-            else if (S->thr_rows) gate.thr_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_thr), gate.thr[0] = gate.thr[1] = gate.thr[2] = 0.f;
-            gate.c0_win = gp(S->g_c0_win);
-            if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
+            stream_fill_gate(S, silence, gate);
             sc.gate = &gate;
         }
         float *ws = reinterpret_cast<float *>(((uintptr_t)(S->buf + S->model_ws) + 255) & ~(uintptr_t)255);
-        const DfxLane *ln = &m->lanes[0];
-        if ((rc = forward_conv_ch(c.conv_ch, m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, ln, false, nullptr, &sc))) return rc;
+        if (int rc = forward_conv_ch(c.conv_ch, m, st->bands, spec_win, fe_win, fs_win, B, T, S->lim, nullptr, nullptr, fp(S->lsnr), nullptr, ws, s, &m->lanes[0], false, nullptr, &sc))
+            return rc;
         if (stepped) S->hflip ^= 1;   // (like lin_pos: this form is neither replayed from a graph nor walked hop by hop by the caller)
         S->c0ring_ok = sc.c0ring_used;   // any pass that did not go through the step kernel (several hops, gated, run_df off) leaves the sums behind
-        if (gated && c.df_pathway_kernel_size_t > 1) {  // the DF decoder's delay line moves where that decoder ran
-            if (S->g_pend2_ok) {
-                dfx_launch(dfx_k_gate_pend_commit, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const unsigned char *)gflags,
-                           S->gate_buf + S->g_par, reinterpret_cast<int *>(S->gate_buf + S->g_cnt), B);
-            } else {
-                const int64_t frame = (int64_t)Fd * c.conv_ch;
-                dfx_launch(dfx_k_gate_c0_shift, dim3((unsigned)B, 4), dim3(256), 0, s, (const unsigned char *)gflags, gp(S->g_c0_win), B, T,
-                           c.df_pathway_kernel_size_t, frame);
-            }
-            DFX_LAUNCH_CHECK();
-        }
-        if (warm) {   // the streams of this pass that have no net position yet: zero features, network state and enhanced spectrum
-            DfxRowClear R;
-            R.n = 0;
-            bool ok = true;
-            auto add = [&](void *ptr, int64_t stride, int64_t bytes, int reps = 1, int64_t rep_stride = 0) { ok = R.add(ptr, stride, bytes, reps, rep_stride) && ok; };
-            add(out_spec, Fp * 8, Fp * 8);
-            if (flin) {
-                add(fp(S->fe_lin) + (lin_pos0 + H) * E1, capf * E1 * 4, E1 * 4);
-                add(fp(S->fs_lin) + (lin_pos0 + H) * D2, capf * D2 * 4, D2 * 4);
-            } else {
-                add(fp(S->hist_fe[S->flip ^ 1]) + (H - 1) * E1, H * E1 * 4, E1 * 4);
-                add(fp(S->hist_fs[S->flip ^ 1]) + (H - 1) * D2, H * D2 * 4, D2 * 4);
-            }
-            add(fp(S->hflip ? S->h_state2 : S->h_state), 1024, 1024, S->layers, B * 1024);   // (the buffer that holds the states after this pass)
-            if (S->c0ring_bytes) add(S->buf + S->c0ring, (int64_t)(S->c0ring_bytes / (size_t)B), (int64_t)(S->c0ring_bytes / (size_t)B));
-            if (gated) {
-                const int kt = c.df_pathway_kernel_size_t;
-                add(gflags, 1, 1);
-                if (S->g_pend2_ok) {
-                    const int64_t pb = (int64_t)2 * (kt - 1) * ((Fd + 15) / 16) * 64 * 16;
-                    add(S->gate_buf + S->g_pend2, pb, pb);
-                    add(S->gate_buf + S->g_par, 1, 1);
-                    add(S->gate_buf + S->g_cnt, 4, 4);
-                } else if (kt > 1) {
-                    add(gp(S->g_c0_win), T * Fd * c.conv_ch * 4, T * Fd * c.conv_ch * 4);
-                }
-            }
-            if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream warm-up: more state arrays than DFX_ROWS_MAX_ENTRIES");
-            if (S->pausable)
-                dfx_launch(dfx_k_stream_warm_active, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount,
-                           (const unsigned char *)gflags, B);
-            else
-                dfx_launch(dfx_k_stream_warm, dim3((unsigned)B, 2), dim3(256), 0, s, R, (const int *)reinterpret_cast<int *>(S->buf + S->tz_rows), (int)H, gcount, B);
-            DFX_LAUNCH_CHECK();
-        }
+        return gated ? stream_commit_delay_line(S, T, s) : DFX_OK;
     }
-    if (side && !erb_done && (rc = erb_ring(s))) return rc;                              // (no forward pass ran: warm-up hops)
-    if (side && !side_done && ((rc = side_pre(s)) || (rc = side_post(s)))) return rc;
-    // ---- ISTFT of the n enhanced hops (state: overlap-add memory)
-    if ((rc = dfx_launch_synthesis(st, out_spec, B, n, sm_in, sm_out, y, ys, 0, n * hop, s, 0, -1, Fp))) return rc;
-    if (lsnr_out) {  // the window's lsnr is [B, T]: take the n new frames (the entries of warm-up hops are not meaningful)
-        if ((rc = stream_copy_rows(fp(S->lsnr), T, T, H, lsnr_out, ls, n, B, s))) return rc;
+
+    // the streams of this pass that have no net position yet: zero features, network state and enhanced spectrum
+    int warm_rows() {
+        DfxRowClear R;
+        R.n = 0;
+        bool ok = R.add(out_spec, Fp * 8, Fp * 8);
+        if (flin) {
+            ok = R.add(fp(S->fe_lin) + (lin_pos0 + H) * E, capf * E * 4, E * 4) && ok;
+            ok = R.add(fp(S->fs_lin) + (lin_pos0 + H) * D2, capf * D2 * 4, D2 * 4) && ok;
+        } else {
+            ok = R.add(fp(S->hist_fe[S->flip ^ 1]) + (H - 1) * E, H * E * 4, E * 4) && ok;
+            ok = R.add(fp(S->hist_fs[S->flip ^ 1]) + (H - 1) * D2, H * D2 * 4, D2 * 4) && ok;
+        }
+        ok = R.add(stream_h(S), 1024, 1024, S->layers, B * 1024) && ok;   // (the buffer that holds the states after this pass)
+        if (gated) ok = R.add(gflags, 1, 1) && ok;
+        ok = stream_convp_rows(S, gated, R) && ok;
+        if (!ok) DFX_FAIL(DFX_ERR_UNSUPPORTED, "stream warm-up: more state arrays than DFX_ROWS_MAX_ENTRIES");
+        const int *tz = reinterpret_cast<int *>(S->buf + S->tz_rows);
+        if (S->pausable) dfx_launch(dfx_k_stream_warm_active, dim3((unsigned)B, 2), dim3(256), 0, s, R, tz, (int)H, gcount, (const unsigned char *)gflags, B);
+        else dfx_launch(dfx_k_stream_warm, dim3((unsigned)B, 2), dim3(256), 0, s, R, tz, (int)H, gcount, B);
+        DFX_LAUNCH_CHECK();
+        return DFX_OK;
     }
-    if (gated) {
-        // ---- who keeps which state (dfx_k_gate_commit), then the frozen streams' answer and the skip counters
+
+    int finish() {
+        int rc;
+        if (!erb_done && (rc = erb_window(s))) return rc;                              // (no forward pass ran: warm-up hops)
+        if (!side_done && ((rc = df_window(s)) || (rc = spec_window(s)))) return rc;
+        // ---- ISTFT of the n enhanced hops (state: overlap-add memory)
+        if ((rc = dfx_launch_synthesis(st, out_spec, B, n, sm_in, sm_out, y, ys, 0, n * hop, s, 0, -1, Fp))) return rc;
+        if (lsnr_out) {  // the window's lsnr is [B, T]: take the n new frames (the entries of warm-up hops are not meaningful)
+            if ((rc = stream_copy_rows(fp(S->lsnr), T, T, H, lsnr_out, ls, n, B, s))) return rc;
+        }
+        if (!gated) return DFX_OK;
         DfxGateTable G;
         G.n = 0;
-        auto entry = [&](float *dst, const float *src, int64_t row, unsigned char mask, unsigned char want) {
-            G.dst[G.n] = dst, G.src[G.n] = src, G.row[G.n] = row, G.mask[G.n] = mask, G.want[G.n] = want;
-            ++G.n;
-        };
         const unsigned char FZ = DFX_GATE_FROZEN;
-        entry(am_out, am_in, ML, FZ, FZ);
-        entry(sm_out, sm_in, ML, FZ, FZ);
+        G.add(am_out, am_in, ML, FZ, FZ);
+        G.add(sm_out, sm_in, ML, FZ, FZ);
         if (!flin) {   // (linear windows: dfx_k_gate_hold)
-            entry(fp(S->hist_fe[S->flip ^ 1]), fp(S->hist_fe[S->flip]), H * E, FZ, FZ);
-            entry(fp(S->hist_fs[S->flip ^ 1]), fp(S->hist_fs[S->flip]), H * Fd * 2, FZ, FZ);
+            G.add(fp(S->hist_fe[S->flip ^ 1]), fp(S->hist_fe[S->flip]), H * E, FZ, FZ);
+            G.add(fp(S->hist_fs[S->flip ^ 1]), fp(S->hist_fs[S->flip]), H * D2, FZ, FZ);
         }
-        if (!lin) entry(fp(S->hist_spec[S->flip ^ 1]), fp(S->hist_spec[S->flip]), Hs * F2, FZ, FZ);
-        entry(fp(S->erb_state), gp(S->g_sh_erb), E, FZ, FZ);
-        entry(fp(S->unit_state), gp(S->g_sh_unit), Fd, FZ, FZ);
+        if (!lin) G.add(fp(S->hist_spec[S->flip ^ 1]), fp(S->hist_spec[S->flip]), Hs * F2, FZ, FZ);
+        G.add(fp(S->erb_state), gp(S->g_sh_erb), E, FZ, FZ);
+        G.add(fp(S->unit_state), gp(S->g_sh_unit), Fd, FZ, FZ);
         const int nenc = (int)m->enc_gru.size(), ndec = (int)m->dec_gru.size();
         for (int l = 0; l < S->layers; ++l) {
-            float *h = fp(S->hflip ? S->h_state2 : S->h_state) + (int64_t)l * B * 256;
-            const float *hs = (stepped ? fp(S->hflip ? S->h_state : S->h_state2) : gp(S->g_sh_h)) + (int64_t)l * B * 256;   // the states before this pass
-            if (l < nenc) entry(h, hs, 256, FZ, FZ);
-            else if (l < nenc + ndec) entry(h, hs, 256, DFX_GATE_GAINS, 0);   // stage 1 did not run (frozen streams included)
-            else entry(h, hs, 256, DFX_GATE_DF, 0);                           // stage 2 did not run
+            float *h = stream_h(S) + (int64_t)l * B * 256;
+            const float *hs = (stepped ? stream_h(S, true) : gp(S->g_sh_h)) + (int64_t)l * B * 256;   // the states before this pass
+            if (l < nenc) G.add(h, hs, 256, FZ, FZ);
+            else if (l < nenc + ndec) G.add(h, hs, 256, DFX_GATE_GAINS, 0);   // stage 1 did not run (frozen streams included)
+            else G.add(h, hs, 256, DFX_GATE_DF, 0);                           // stage 2 did not run
         }
-        dfx_launch(dfx_k_gate_commit, dim3((unsigned)B), dim3(128), 0, s, G, (const unsigned char *)gflags, B);
-        DFX_LAUNCH_CHECK();
-        dfx_launch(dfx_k_gate_finish, dim3((unsigned)B), dim3(128), 0, s, (const unsigned char *)gflags, gcount, y, ys, (int)hop, lsnr_out,
-                   ls, B, (int)(skip >= n));
-        DFX_LAUNCH_CHECK();
+        return close_gate(G, skip >= n);
     }
-    return DFX_OK;
+};
+
+static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s, int64_t xs, int64_t ys, int64_t ls,
+                       bool p_mixed, bool p_warm) {
+    DfxStreamPass p{S, x, n, y, lsnr_out, s, xs, ys, ls, p_mixed, p_warm, S->m->cfg};
+    int rc;
+    if ((rc = p.plan()) || (rc = p.open_gate())) return rc;
+    if (p.bypass) return p.pass_through();
+    if ((rc = p.features())) return rc;
+    if (p.skip < n && ((rc = p.network()) || (p.warm && (rc = p.warm_rows())))) return rc;
+    return p.finish();
 }
 
 // Faults raised by kernels (dfx_model::h_err): a call reports what earlier passes on the model raised before it starts its own, and — with
@@ -1150,58 +1188,38 @@ extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, in
 extern "C" int dfx_stream_process(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, void *stream) {
     return dfx_stream_process_active(S, x, n, y, lsnr_out, nullptr, stream);
 }
+// A call of n hops as passes.  A hop is passed on its own while the handle keeps per-stream forms (gated, pausable: the stage decisions of
+// hop i shape the state hop i+1 starts from) or sits inside the warm-up of a stream that started over on its own
+// (dfx_stream_reset_streams); otherwise the rest of the call is one pass.
 static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s) {
     const bool advances = S->lim != 1.f;  // the pass-through case (tract.rs:540-543) moves the STFT memory and the rolling spectra only
-    const int64_t hop = S->st->hop;
-    if (S->pausable && S->gate_buf) {
-        // one hop per pass, like a gated handle.  Whether a pass takes the per-row t_zero (a stream younger than the window and than the
-        // handle) and the warm-up (younger than the lookahead) follows the ages of the streams that take part: a young stream that sits out
-        // keeps nobody in those forms.  After the pass the paused streams' births follow the handle's count (dfx_k_stream_pause did the same).
-        const int ch = S->channels;
-        const int64_t ns = S->B / ch, Hs = S->H + S->L;
-        for (int64_t i = 0; i < n; ++i) {
-            S->p_mixed = S->p_warm = false;
-            for (int64_t k = 0; k < ns; ++k) {
-                const int64_t born = S->birth[(size_t)(k * ch)], age = S->frames - born;
-                if (S->paused[(size_t)k] || born == 0 || age >= Hs) continue;
-                S->p_mixed = true;
-                if (age < S->L) S->p_warm = true;
+    const bool per_stream = (S->gated || S->pausable) && S->gate_buf;
+    const int ch = S->channels;
+    const int64_t hop = S->st->hop, ns = S->B / ch, Hs = S->H + S->L;
+    for (int64_t done = 0, k; done < n; done += k) {
+        k = per_stream || (advances && S->frames < S->warm_until) ? 1 : n - done;
+        bool mixed = S->frames < S->mixed_until, warm = S->frames < S->warm_until;
+        if (S->pausable) {
+            // Whether a pass takes the per-row t_zero (a stream younger than the window and than the handle) and the warm-up (younger than the
+            // lookahead) follows the ages of the streams that take part: a young stream that sits out keeps nobody in those forms.
+            mixed = warm = false;
+            for (int64_t i = 0; i < ns; ++i) {
+                const int64_t born = S->birth[(size_t)(i * ch)], age = S->frames - born;
+                if (S->paused[(size_t)i] || born == 0 || age >= Hs) continue;
+                mixed = true;
+                if (age < S->L) warm = true;
             }
-            if (int rc = stream_body(S, x + i * hop, 1, y + i * hop, lsnr_out ? lsnr_out + i : nullptr, s, n * hop, n * hop, n)) return rc;
-            if (advances) {
-                S->frames += 1;
-                if (S->any_paused)
-                    for (int64_t k = 0; k < ns; ++k)
-                        if (S->paused[(size_t)k])
-                            for (int c = 0; c < ch; ++c) S->birth[(size_t)(k * ch + c)] += 1;
-            }
-            S->flip ^= 1;
         }
-        return DFX_OK;
-    }
-    if (S->gated && S->gate_buf) {  // one hop per pass: the stage decisions of hop i shape the state hop i+1 starts from
-        for (int64_t i = 0; i < n; ++i) {
-            if (int rc = stream_body(S, x + i * hop, 1, y + i * hop, lsnr_out ? lsnr_out + i : nullptr, s, n * hop, n * hop, n)) return rc;
-            if (advances) S->frames += 1;
-            S->flip ^= 1;
+        if (int rc = stream_body(S, x + done * hop, k, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n, mixed, warm)) return rc;
+        if (advances) {
+            S->frames += k;
+            // after the pass the paused streams' births follow the handle's count (dfx_k_stream_pause did the same)
+            for (int64_t i = 0; S->any_paused && i < ns; ++i)
+                if (S->paused[(size_t)i])
+                    for (int j = 0; j < ch; ++j) S->birth[(size_t)(i * ch + j)] += k;
         }
-        return DFX_OK;
-    }
-    // hops inside the warm-up of a stream that started over on its own (dfx_stream_reset_streams) are passed one at a time, the rest as one pass
-    int64_t done = 0;
-    for (; advances && done < n && S->frames < S->warm_until; ++done) {
-        if (int rc = stream_body(S, x + done * hop, 1, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n)) return rc;
-        S->frames += 1;
         S->flip ^= 1;
     }
-    if (done == n) return DFX_OK;
-    if (done > 0) {
-        if (int rc = stream_body(S, x + done * hop, n - done, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n)) return rc;
-    } else if (int rc = stream_body(S, x, n, y, lsnr_out, s)) {
-        return rc;
-    }
-    if (advances) S->frames += n - done;
-    S->flip ^= 1;
     return DFX_OK;
 }
 
@@ -1230,51 +1248,30 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
     const dfx_model *m = S->m;
     const dfx_state *st = S->st;
     const dfx_model_cfg &c = m->cfg;
-    const int64_t B = S->B, H = S->H, L = S->L, Hs = H + L, F = st->N / 2 + 1, E = c.nb_erb, Fd = c.nb_df, hop = st->hop, ML = st->N - hop;
+    const int64_t B = S->B, H = S->H, L = S->L, Hs = H + L, F = st->N / 2 + 1, E = c.nb_erb, Fd = c.nb_df;
     const int64_t n = 1, T = H + n, a0 = S->frames;
     const int O = c.df_order;
-    auto fp = [&](size_t o) { return reinterpret_cast<float *>(S->buf + o); };
-    auto gp = [&](size_t o) { return reinterpret_cast<float *>(S->gate_buf + o); };
     unsigned char *gflags = S->gate_buf + S->g_flags;
     int rc;
     // this path keeps the windows in ring form: if an earlier call on the handle left them in the linear buffers, their last frames
-    // become the ring form's history first (as stream_body does when it changes form)
-    if (S->feat_owns) {
-        const int64_t capf = S->feat_cap, D2 = Fd * 2;
-        if ((rc = stream_copy_rows(fp(S->fe_lin), capf * E, capf * E, S->lin_pos * E, fp(S->hist_fe[S->flip]), H * E, H * E, B, s)) ||
-            (rc = stream_copy_rows(fp(S->fs_lin), capf * D2, capf * D2, S->lin_pos * D2, fp(S->hist_fs[S->flip]), H * D2, H * D2, B, s)))
-            return rc;
-        S->feat_owns = false;
-    }
-    if (S->lin_owns) {
-        const int64_t F2 = S->Fp * 2;
-        if ((rc = stream_copy_rows(fp(S->spec_lin), S->lin_cap * F2, S->lin_cap * F2, S->lin_pos * F2, fp(S->hist_spec[S->flip]), Hs * F2, Hs * F2, B, s))) return rc;
-        S->lin_owns = false;
-    }
+    // become the ring form's history first
+    DfxCopyList cp_spec, cp_fe, cp_fs;
+    stream_to_ring(S, true, cp_spec, cp_fe, cp_fs);
+    if ((rc = cp_fe.emit(B, s)) || (rc = cp_fs.emit(B, s)) || (rc = cp_spec.emit(B, s))) return rc;
     DFX_HIP(hipMemsetAsync(gflags, 0, (size_t)B, s));  // no silent-input test on this path (tract.rs:441: process_raw starts at the features)
-    DFX_HIP(hipMemcpyAsync(gp(S->g_sh_erb), fp(S->erb_state), (size_t)B * E * 4, hipMemcpyDeviceToDevice, s));
-    DFX_HIP(hipMemcpyAsync(gp(S->g_sh_unit), fp(S->unit_state), (size_t)B * Fd * 4, hipMemcpyDeviceToDevice, s));
-    DFX_HIP(hipMemcpyAsync(gp(S->g_sh_h), fp(S->hflip ? S->h_state2 : S->h_state), (size_t)S->layers * B * 256 * 4, hipMemcpyDeviceToDevice, s));
+    if ((rc = stream_shadow_state(S, true, s))) return rc;
     // features of the given spectra (state: the running means): erb (dB) -> mean norm, low bins -> unit norm (lib.rs:206-217)
-    float *new_fe = fp(S->new_fe), *new_fs = fp(S->new_fs);   // (the caller's dense [B, F] spectra are read in place)
+    float *new_fe = stream_fp(S, S->new_fe), *new_fs = stream_fp(S, S->new_fs);   // (the caller's dense [B, F] spectra are read in place)
     if ((rc = dfx_erb(st->bands, spec, B, 1, new_fe, s))) return rc;
-    if ((rc = dfx_launch_norm_scan(new_fe, new_fe, (int)E, spec, F, new_fs, (int)Fd, B, n, c.norm_alpha, fp(S->erb_state),
-                                   fp(S->unit_state), s)))
+    if ((rc = dfx_launch_norm_scan(new_fe, new_fe, (int)E, spec, F, new_fs, (int)Fd, B, n, c.norm_alpha, stream_fp(S, S->erb_state),
+                                   stream_fp(S, S->unit_state), s)))
         return rc;
     const int64_t skip = a0 < L ? 1 : 0;
-    float *work_fe = fp(S->work_fe), *work_fs = fp(S->work_fs);
-    struct Ring { size_t *hist; float *nw, *work; int64_t h, row; } rings[2] = {{S->hist_fe, new_fe, work_fe, H, E}, {S->hist_fs, new_fs, work_fs, H, Fd * 2}};
-    for (const Ring &r : rings) {
-        DfxKScope ks(DFX_K_COPY_ROWS, s);
-        dfx_launch(dfx_k_ring_step, dim3((unsigned)nn_grid(dfx_ceil_div(B * (r.h + n) * r.row, 256), 16)), dim3(256), 0, s,
-                   (const float *)fp(r.hist[S->flip]), (const float *)r.nw, r.work, fp(r.hist[S->flip ^ 1]), B, r.h, n, r.row, skip);
-        DFX_LAUNCH_CHECK();
-    }
-    // the buffers this path does not use keep their contents across the parity flip
-    DFX_HIP(hipMemcpyAsync(fp(S->ana_mem[S->flip ^ 1]), fp(S->ana_mem[S->flip]), (size_t)B * ML * 4, hipMemcpyDeviceToDevice, s));
-    DFX_HIP(hipMemcpyAsync(fp(S->syn_mem[S->flip ^ 1]), fp(S->syn_mem[S->flip]), (size_t)B * ML * 4, hipMemcpyDeviceToDevice, s));
-    DFX_HIP(hipMemcpyAsync(fp(S->hist_spec[S->flip ^ 1]), fp(S->hist_spec[S->flip]), (size_t)B * Hs * S->Fp * 8, hipMemcpyDeviceToDevice, s));
-    float *mask = gp(S->g_mask), *cbuf = gp(S->g_coefs);
+    float *work_fe = stream_fp(S, S->work_fe), *work_fs = stream_fp(S, S->work_fs);
+    if ((rc = stream_ring_step(S, S->hist_fe, new_fe, work_fe, H, n, E, skip, s)) || (rc = stream_ring_step(S, S->hist_fs, new_fs, work_fs, H, n, Fd * 2, skip, s)))
+        return rc;
+    if ((rc = stream_carry_parity(S, true, true, false, true, s))) return rc;
+    float *mask = stream_gp(S, S->g_mask), *cbuf = stream_gp(S, S->g_coefs);
     if (!skip) {
         DfxStreamCtx sc;
         sc.H = H;
@@ -1282,46 +1279,30 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
         sc.t_zero = pos0 > 0 ? pos0 : 0;
         sc.spec_T = Hs + n;
         sc.spec_stride = S->Fp;
-        sc.h_state = fp(S->hflip ? S->h_state2 : S->h_state);
+        sc.h_state = stream_h(S);
         sc.pf_beta = 0.f;
-        sc.out = fp(S->out_spec);  // the deep-filter kernel still runs (on whatever the spectrum window holds); its output is not used
+        sc.out = stream_fp(S, S->out_spec);  // the deep-filter kernel still runs (on whatever the spectrum window holds); its output is not used
         sc.out_T = n;
         sc.out_toff = H;
         sc.channels = S->channels;
         sc.reduce_mask = S->reduce_mask;
         DfxGate gate;
-        gate.channels = S->channels;
-        gate.flags = gflags;
-        gate.thr[0] = S->thr[0], gate.thr[1] = S->thr[1], gate.thr[2] = S->thr[2];
-        if (S->thr_rows) gate.thr_rows = reinterpret_cast<const float *>(S->set_buf + S->sb_thr), gate.thr[0] = gate.thr[1] = gate.thr[2] = 0.f;
-        gate.c0_win = gp(S->g_c0_win);
-        if (S->g_pend2_ok) gate.pend2 = S->gate_buf + S->g_pend2, gate.par = S->gate_buf + S->g_par, gate.cnt = reinterpret_cast<int *>(S->gate_buf + S->g_cnt);
+        stream_fill_gate(S, true, gate);
         sc.gate = &gate;
         float *ws = reinterpret_cast<float *>(((uintptr_t)(S->buf + S->model_ws) + 255) & ~(uintptr_t)255);
-        const DfxLane *ln = &m->lanes[0];
-        if ((rc = forward_conv_ch(c.conv_ch, m, st->bands, fp(S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, fp(S->lsnr), cbuf, ws, s, ln, false, nullptr, &sc))) return rc;
-        if (c.df_pathway_kernel_size_t > 1) {
-            if (S->g_pend2_ok)
-                dfx_launch(dfx_k_gate_pend_commit, dim3((unsigned)dfx_ceil_div(B, 256)), dim3(256), 0, s, (const unsigned char *)gflags,
-                           S->gate_buf + S->g_par, reinterpret_cast<int *>(S->gate_buf + S->g_cnt), B);
-            else
-                dfx_launch(dfx_k_gate_c0_shift, dim3((unsigned)B, 4), dim3(256), 0, s, (const unsigned char *)gflags, gp(S->g_c0_win), B, T,
-                           c.df_pathway_kernel_size_t, (int64_t)Fd * c.conv_ch);
-            DFX_LAUNCH_CHECK();
-        }
+        if ((rc = forward_conv_ch(c.conv_ch, m, st->bands, stream_fp(S, S->work_spec), work_fe, work_fs, B, T, 0.f, nullptr, mask, stream_fp(S, S->lsnr), cbuf, ws, s, &m->lanes[0], false, nullptr, &sc)))
+            return rc;
+        if ((rc = stream_commit_delay_line(S, T, s))) return rc;
         // the newest frame's mask row and coefficient rows (coefficients are [B, O, T, F'][2]: one strided row per (stream, tap))
         if ((rc = stream_copy_rows(mask, T * E, T * E, (T - 1) * E, gains, E, E, B, s))) return rc;
         if ((rc = stream_copy_rows(cbuf, T * Fd * 2, T * Fd * 2, (T - 1) * Fd * 2, coefs, Fd * 2, Fd * 2, B * O, s))) return rc;
-        if (lsnr_out && (rc = stream_copy_rows(fp(S->lsnr), T, T, H, lsnr_out, 1, 1, B, s))) return rc;
+        if (lsnr_out && (rc = stream_copy_rows(stream_fp(S, S->lsnr), T, T, H, lsnr_out, 1, 1, B, s))) return rc;
         // decoder states of the stages that did not run go back to what they were
         DfxGateTable G;
         G.n = 0;
         const int nenc = (int)m->enc_gru.size(), ndec = (int)m->dec_gru.size();
-        for (int l = nenc; l < S->layers; ++l) {
-            G.dst[G.n] = fp(S->hflip ? S->h_state2 : S->h_state) + (int64_t)l * B * 256, G.src[G.n] = gp(S->g_sh_h) + (int64_t)l * B * 256, G.row[G.n] = 256;
-            G.mask[G.n] = l < nenc + ndec ? DFX_GATE_GAINS : DFX_GATE_DF, G.want[G.n] = 0;
-            ++G.n;
-        }
+        for (int l = nenc; l < S->layers; ++l)
+            G.add(stream_h(S) + (int64_t)l * B * 256, stream_gp(S, S->g_sh_h) + (int64_t)l * B * 256, 256, l < nenc + ndec ? DFX_GATE_GAINS : DFX_GATE_DF, 0);
         dfx_launch(dfx_k_gate_commit, dim3((unsigned)B), dim3(128), 0, s, G, (const unsigned char *)gflags, B);
         DFX_LAUNCH_CHECK();
     } else if (lsnr_out) {

@@ -163,6 +163,52 @@ def test_linear_rolling_spectra_equal_the_ring_form(backend, monkeypatch):
             assert torch.equal(run(env, toggle), ref), (env, toggle)
 
 
+def test_process_raw_takes_over_linear_windows(backend, monkeypatch):
+    """dfx_stream_process_raw keeps every window in ring form.  On a handle whose earlier process() calls left the rolling spectra and
+    the feature windows in the linear buffers (DFX_STREAM_LINEAR=6), its first call hands their last frames over to the ring form first —
+    more window-copy launches than its second call — and everything the handle returns, before, during and after the raw calls, has the
+    bits of the handle that was in ring form all along (DFX_STREAM_LINEAR=0)."""
+    from deepfilternet_amd import _lib
+    from deepfilternet_amd.enhance import init_df
+    from deepfilternet_amd.streaming import DfStream
+
+    p = named_params("pf32")
+    model, df_state, _, _ = init_df(params=p, epoch="none", seed=9)
+    hop, N = p.hop_size, p.fft_size
+    L = p.df_lookahead
+    T = L + 4 + 3 + 2
+    x = torch.from_numpy((0.1 * np.random.default_rng(6).standard_normal((2, hop * T))).astype(np.float32))
+    # spectra of the hops that go through process_raw: windowed frames [previous hop ; hop]
+    xp = torch.cat([torch.zeros(2, N - hop), x], dim=1)
+    spec = torch.fft.rfft(xp.unfold(1, N, hop) * torch.hann_window(N), dim=2).to(torch.complex64)   # [2, T, F]
+
+    def run(env):
+        monkeypatch.setenv("DFX_STREAM_LINEAR", env)
+        rt = DfStream(model, df_state, streams=2, max_frames=1, gating=True, thresholds=(-1e9, 1e9, 1e9))   # every stage runs
+        out, copies = [], []
+        _lib.prof_enable(["dfx_k_copy_rows"])
+        try:
+            for t in range(T):
+                if L + 4 <= t < L + 7:
+                    _lib.prof_reset()
+                    out += list(rt.process_raw(spec[:, t].contiguous()))   # lsnr, gains, coefs, stages
+                    copies.append(_lib.prof_read().get("dfx_k_copy_rows", (0.0, 0))[1])
+                else:
+                    out += list(rt.process(x[:, t * hop:(t + 1) * hop], return_lsnr=True))
+        finally:
+            _lib.prof_enable(None)
+        return out, copies
+
+    ring, ring_copies = run("0")
+    linear, linear_copies = run("6")
+    print(f"window-copy launches of the three process_raw calls: ring form {ring_copies}, after linear windows {linear_copies}")
+    assert linear_copies[0] > linear_copies[1], linear_copies   # the hand-over ran, once
+    assert len(ring) == len(linear) == (T - 3) * 2 + 3 * 4
+    for i, (a, b) in enumerate(zip(ring, linear)):
+        assert torch.equal(a, b), i
+    assert all(bool(torch.isfinite(torch.view_as_real(a) if a.is_complex() else a.float()).all()) for a in ring)
+
+
 @pytest.mark.gpu
 def test_one_hop_kernels_agree_with_the_general_path(hip_backend):
     """A call of ONE hop takes kernels of its own (dfx_k_gru_step_h3, dfx_k_df_convp_step with its pending sums, window updates on the DF
