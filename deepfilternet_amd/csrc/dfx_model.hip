@@ -500,6 +500,7 @@ struct dfx_model {
     unsigned int *d_psync = nullptr;    // pair form of the persistent GRU phase: [DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX / 2][48] words
     mutable unsigned int seq_pbase = 0;       // step counter base of the follower hand-overs (yprog / giprog), monotonic like seq_base
     mutable int64_t passes_ps = 0;   // batch passes whose c0 kernels read the pre-split copy of feat_spec (DFX_Q_PASSES_C0_PRESPLIT)
+    mutable int64_t last_plan = 0;   // DFX_PLAN_* bits of the last pass (DFX_Q_LAST_PLAN): written by DfxPass::plan() / df_out_rows() / finish()
     mutable int64_t passes_seq = 0, passes_ev = 0;   // passes that ran the persistent phase / that gave it up because another process held the device's ticket (DFX_Q_TICKET_*)
     mutable unsigned int seq_base = 0;  // flag value of "nothing of the current forward pass yet"
     unsigned long long *d_trace = nullptr;   // dev aid (DFX_SEQ_TRACE=1): chunk timestamps of the last persistent GRU launch
@@ -1378,6 +1379,7 @@ extern "C" int dfx_model_query(const dfx_model *m, int what, int64_t *value) {
         case DFX_Q_PASSES_TICKET_BUSY: *value = m->passes_ev; return DFX_OK;
         case DFX_Q_SPIN_LIMIT: *value = m->spin_limit; return DFX_OK;
         case DFX_Q_PASSES_C0_PRESPLIT: *value = m->passes_ps; return DFX_OK;
+        case DFX_Q_LAST_PLAN: *value = m->last_plan; return DFX_OK;
     }
     DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_query: unknown item %d", what);
 }
@@ -1406,6 +1408,12 @@ static inline bool dfx_c0_presplit(const dfx_model *m, bool streaming) {
 static inline bool dfx_enc_fan_ok(const dfx_model *m) {
     const dfx_model_cfg &c = m->cfg;
     return m->efan_groups > 0 && !c.enc_concat && (int64_t)c.conv_ch * c.nb_erb / 4 == 16 * (int64_t)m->efan_groups;
+}
+// Does the ERB encoder's head run frame-resident (dfx_k_erb_enc: a frame's zero-bordered feature rows within the kernel's 192 staging lanes, two
+// workgroups' rows within the LDS)?  One rule for DfxPass::plan() and for dfx_stream_create, whose passes have no other form of the head.
+static inline bool dfx_erb_enc_fused_ok(const dfx_model_cfg &c) {
+    const int C = c.conv_ch, E = c.nb_erb;
+    return E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
 }
 // Does the DF branch of the encoder run as the one kernel dfx_k_df_enc_h3 on the fp16-split path (forward_impl: `dfenc` = fuse_h3 && this)?
 // feat_T: frames per clip of the feature arrays (0: T).  The limits are the kernel's 32-bit element offsets; beyond them the two kernels run.

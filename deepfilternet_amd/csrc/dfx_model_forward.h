@@ -114,7 +114,7 @@ struct DfxPass {
         // frame-resident ERB encoder head / decoder tail (dfx_k_erb_enc, dfx_k_erb_dec10 / dfx_k_erb_tail) where a frame fits the LDS; else layer by layer
         fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
         fuse_tail = fuse_dec && erb_tail_ok<C>(m, E);
-        fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
+        fuse_enc = dfx_erb_enc_fused_ok(c);
         no_e0 = fuse_tail && fuse_enc;   // e0 never exists in HBM
         // batch passes on the fp16-split path: the four ERB convolutions as one launch (dfx_k_erb_enc4); streaming passes (frame ranges, gating,
         // row maps), exact mode and other shapes keep dfx_k_erb_enc + dfx_k_pwconv_f x 2 (DFX_ERB_ENC_SPLIT=1: batch passes too — test hook)
@@ -170,8 +170,15 @@ struct DfxPass {
         // (the event-synchronised form: m->tchunks chunks of at least tchunk_min frames, as decided above)
         if (pipe)
             for (int i = 0; i <= K; ++i) cb[i] = (int)(T * i / K);
+        // what this pass decided (DFX_Q_LAST_PLAN); df_out_rows() / df_tail_identity() and finish() add the forms they take
+        m->last_plan = (fan ? DFX_PLAN_FAN : 0) | (fan_skp ? DFX_PLAN_FAN_SKP : 0) | (fuse_h3 ? DFX_PLAN_FUSE_H3 : 0) |
+                       (c0_fused && fps ? DFX_PLAN_PRESPLIT : 0) | (fuse_tail ? DFX_PLAN_FUSE_TAIL : 0) | (fuse_enc ? DFX_PLAN_FUSE_ENC : 0) |
+                       (fuse_enc4 ? DFX_PLAN_FUSE_ENC4 : 0) | (enc_fan ? DFX_PLAN_ENC_FAN : 0) | (dfenc ? DFX_PLAN_DFENC : 0) |
+                       (c0_fused ? DFX_PLAN_C0_FUSED : 0) | (pipe ? DFX_PLAN_PIPE : 0) | (use_seq ? DFX_PLAN_USE_SEQ : 0) |
+                       (fuse_dec ? DFX_PLAN_FUSE_DEC : 0);
         return DFX_OK;
     }
+    void note_df_out(int form) const { m->last_plan = (m->last_plan & ~(int64_t)DFX_PLAN_DF_OUT_MASK) | ((int64_t)form << DFX_PLAN_DF_OUT_SHIFT); }
     // ---- time chunk k of the layer-pipelined forms: first frame, row map, rows; chunks [k0, k] as one range
     int64_t tb(int k) const { return cb[k]; }
     DfxRowMap rmk(int k0, int k) const { return DfxRowMap{T, tb(k + 1) - tb(k0), tb(k0)}; }
@@ -236,6 +243,7 @@ struct DfxPass {
             DfxKScope ks(DFX_K_GGEMM, st);
             // (weight fragments resident in registers when a wave's share fits: <= 16 groups of <= 4 tiles — every shipped shape)
             const bool resident = m->dfo_nu == 4 && A.G <= 16 && (int64_t)(NO / 2) * 16 * (Fd / 2) <= (int64_t)DFX_DFO_NPT * DFX_DFO_THREADS;
+            note_df_out(resident ? DFX_PLAN_DF_OUT_RESIDENT : DFX_PLAN_DF_OUT_STREAMING);
             if (resident) {
                 DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_df_out_h3r<4>, smem));
                 dfx_launch(dfx_k_df_out_h3r<4>, dim3((unsigned)nn_grid(dfx_ceil_div(M, 16), 2)), dim3(DFX_DFO_THREADS), smem, st, A);
@@ -246,6 +254,7 @@ struct DfxPass {
             DFX_LAUNCH_CHECK();
             return DFX_OK;
         }
+        note_df_out(DFX_PLAN_DF_OUT_GGEMM);
         return launch_ggemm(cfeat, m->df_out.G * m->df_out.Kg, m->p(m->df_out.w), m->df_out.G, m->df_out.Kg, m->df_out.Ng, nullptr, DFX_ACT_TANH,
                             c0p, coefs, m->df_out.G * m->df_out.Ng, M, st, NO, Fd, T, rm, cfeat2);
     }
@@ -296,6 +305,7 @@ struct DfxPass {
     // the identity-skip DF tail of the chunked forms is not chunked: one add + df_out (always the grouped GEMM) over all frames once the last chunk exists
     int df_tail_identity(const float *y, hipStream_t st) {
         if (int r = df_skip_identity(y, st)) return r;
+        note_df_out(DFX_PLAN_DF_OUT_GGEMM);
         return launch_ggemm(xdf, m->df_out.G * m->df_out.Kg, m->p(m->df_out.w), m->df_out.G, m->df_out.Kg, m->df_out.Ng, nullptr, DFX_ACT_TANH,
                             c0p, coefs, m->df_out.G * m->df_out.Ng, R, st, NO, Fd, T);
     }
@@ -921,6 +931,7 @@ struct DfxPass {
         // Where the transform cannot take them (dfx_synthesis_rows_ok) and without a transform: dfx_k_df_apply_rows -> spec_e -> dfx_k_synthesis (the
         // stand-alone deep-filter kernel stays the API of dfx_model_forward / dfx_df_apply and the roofline kernel of bench.py)
         if (fin && dfx_synthesis_rows_ok(fin->st, true, O, run_df ? Fd : 0, E) && bands == fin->st->bands && sstride % 2 == 0 && sstride > 0) {
+            m->last_plan |= DFX_PLAN_ROWS_FINISH;
             if ((rc = dfx_launch_synthesis_rows(fin->st, spec, sstride, run_df ? coefs : nullptr, run_df ? Fd : 0, O, c.df_lookahead, mask,
                                                 c.mask_pf ? c.pf_beta : 0.f, atten_lim, B, T, fin->y, fin->out_stride, fin->out_skip, fin->out_len, fin_s, fin->out_i16, m->d_err, m->d_sync ? m->d_sync + 14 : nullptr)))   // (d_sync[14]: a spare word of the flag block)
                 return rc;

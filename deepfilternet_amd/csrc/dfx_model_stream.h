@@ -278,6 +278,8 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     // every model without fp16-split fragments — and its GRU layers step on dfx_k_gru_step_x32 / dfx_k_gru_rec_x32)
     if (!m->fuse_c0)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
+    if (!dfx_erb_enc_fused_ok(c))   // (what DfxPass::plan() would refuse on the first hop)
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
     if (int rc = dfx_require_device()) return rc;
     dfx_stream_state *s = new dfx_stream_state();
     s->m = m;

@@ -138,6 +138,19 @@ class DfNet:
 
     Q_GRU_PERSISTENT, Q_HWQ_PROBE, Q_EXACT_FP32, Q_SPIN_LIMIT, Q_PASSES_PERSISTENT, Q_PASSES_TICKET_BUSY = 1, 2, 3, 4, 5, 6
     Q_PASSES_C0_PRESPLIT = 7
+    Q_LAST_PLAN = 8
+    # bits of query(Q_LAST_PLAN) (include/dfx.h DFX_PLAN_*): what the last pass decided; PLAN_DF_OUT is a two-bit field
+    PLAN_BITS = {"fan": 1 << 0, "fan_skp": 1 << 1, "fuse_h3": 1 << 2, "presplit": 1 << 3, "fuse_tail": 1 << 4, "fuse_enc": 1 << 5,
+                 "fuse_enc4": 1 << 6, "enc_fan": 1 << 7, "dfenc": 1 << 8, "c0_fused": 1 << 9, "pipe": 1 << 10, "use_seq": 1 << 11,
+                 "rows_finish": 1 << 14, "fuse_dec": 1 << 15}
+    PLAN_DF_OUT_SHIFT, PLAN_DF_OUT_FORMS = 12, {0: "none", 1: "resident", 2: "streaming", 3: "ggemm"}
+
+    def last_plan(self) -> Dict[str, object]:
+        """query(Q_LAST_PLAN) by name: every PLAN_BITS key as a bool, and ``df_out`` as the form's name."""
+        v = self.query(self.Q_LAST_PLAN)
+        d: Dict[str, object] = {k: bool(v & b) for k, b in self.PLAN_BITS.items()}
+        d["df_out"] = self.PLAN_DF_OUT_FORMS[(v >> self.PLAN_DF_OUT_SHIFT) & 3]
+        return d
 
     def query(self, what: int) -> int:
         """dfx_model_query (include/dfx.h DFX_Q_*)."""

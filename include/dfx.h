@@ -229,6 +229,29 @@ int dfx_model_check(const dfx_model *m);
 #define DFX_Q_PASSES_TICKET_BUSY 6  /* big passes that took the event-synchronised form because another PROCESS held the device's ticket for its own
                                        persistent phase (/dev/shm/dfx_persistent_<PCI bus id>.lock, DFX_DEVICE_TICKET=0: no ticket) */
 #define DFX_Q_PASSES_C0_PRESPLIT 7  /* batch passes whose fused DF-encoder kernels read the pre-split copy of feat_spec (default; DFX_C0_PRESPLIT=0: none) */
+#define DFX_Q_LAST_PLAN 8           /* what the last pass of this handle (batch or streaming) decided: a mask of DFX_PLAN_* bits, 0 before the first pass */
+/* DFX_Q_LAST_PLAN: which fused kernels the pass ran and which form its GRU phase took (decided by the model's shape, the arithmetic mode and the
+ * size of the pass; the names are those of DfxPass::plan() in csrc/dfx_model_forward.h).  Diagnostic: the tests use it to see that their shapes
+ * reach every form. */
+#define DFX_PLAN_FAN (1 << 0)         /* emb and its consumers in one kernel behind the encoder GRU (dfx_k_emb_fan) */
+#define DFX_PLAN_FAN_SKP (1 << 1)     /* ... which also writes df_skip(emb) */
+#define DFX_PLAN_FUSE_H3 (1 << 2)     /* fp16-split fused DF-encoder kernels (c0 recomputed on the matrix core) */
+#define DFX_PLAN_PRESPLIT (1 << 3)    /* ... reading the pre-split copy of feat_spec (counted by DFX_Q_PASSES_C0_PRESPLIT) */
+#define DFX_PLAN_FUSE_TAIL (1 << 4)   /* ERB decoder convolutions as one launch (dfx_k_erb_tail) */
+#define DFX_PLAN_FUSE_ENC (1 << 5)    /* frame-resident ERB encoder head (dfx_k_erb_enc) */
+#define DFX_PLAN_FUSE_ENC4 (1 << 6)   /* the four ERB encoder convolutions as one launch (dfx_k_erb_enc4) */
+#define DFX_PLAN_ENC_FAN (1 << 7)     /* df_fc_emb + linear_in as the fan-out kernel (dfx_k_enc_fan) */
+#define DFX_PLAN_DFENC (1 << 8)       /* the DF branch of the encoder as one kernel (dfx_k_df_enc_h3) */
+#define DFX_PLAN_C0_FUSED (1 << 9)    /* c0 = df_conv0(feat_spec) never stored */
+#define DFX_PLAN_PIPE (1 << 10)       /* layer-pipelined GRU phase (time chunks) */
+#define DFX_PLAN_USE_SEQ (1 << 11)    /* ... in its persistent form (counted by DFX_Q_PASSES_PERSISTENT) */
+#define DFX_PLAN_DF_OUT_SHIFT 12      /* two bits: the form df_out took, DFX_PLAN_DF_OUT_* (0: df_out did not run) */
+#define DFX_PLAN_DF_OUT_MASK (3 << DFX_PLAN_DF_OUT_SHIFT)
+#define DFX_PLAN_DF_OUT_RESIDENT 1    /* dfx_k_df_out_h3r: weight fragments in registers */
+#define DFX_PLAN_DF_OUT_STREAMING 2   /* dfx_k_df_out_h3 */
+#define DFX_PLAN_DF_OUT_GGEMM 3       /* the grouped GEMM */
+#define DFX_PLAN_ROWS_FINISH (1 << 14) /* deep filter + gains inside the inverse transform (dfx_k_synthesis_rows) */
+#define DFX_PLAN_FUSE_DEC (1 << 15)   /* frame-resident last two ERB decoder layers (dfx_k_erb_dec10 / inside dfx_k_erb_tail) */
 int dfx_model_query(const dfx_model *m, int what, int64_t *value);
 
 /* Scratch memory the caller must provide (device bytes) for a [B, T-frames] batch. */

@@ -27,6 +27,54 @@ def named_params(name: str) -> ModelParams:
 GOLDEN_SEEDS = {"defaults": 0, "df3": 1, "pf32": 2}
 
 
+def _shape(base: str = "df3", **kw) -> ModelParams:
+    p = named_params(base)
+    for k, v in kw.items():
+        assert hasattr(p, k), k
+        setattr(p, k, v)
+    return p
+
+
+def _look(n: int) -> dict:
+    return {"conv_lookahead": n, "df_lookahead": n}
+
+
+# Model shapes off the grid of the four named configurations (tests/test_model_shapes.py): each an offset from DeepFilterNet3 ("df3") unless it
+# says "defaults", with the decisions of a pass (DfNet.last_plan(), DfxPass::plan()) it flips against df3.  df3 itself decides: fan, fan_skp,
+# fuse_h3, presplit, fuse_tail, fuse_enc, fuse_enc4, enc_fan, dfenc, c0_fused, df_out resident, rows_finish; GRU layers 1 + 2 + 2.
+SHAPES = {
+    "e24_f64": _shape(nb_erb=24, nb_df=64),              # emb = 384; tile counts of df_enc / df_out
+    "e16": _shape(nb_erb=16),                            # emb = 256
+    "e64": _shape(nb_erb=64),                            # fuse_enc false (3 * (64 + 2) > 192: layer-by-layer head), so fuse_enc4 false; streaming refused
+    "f128": _shape(nb_df=128),                           # widest fused finishing (rows_finish takes nb_df <= 128)
+    "f32": _shape(nb_df=32),
+    "kt2_o3": _shape(df_pathway_kernel_size_t=2, df_order=3, **_look(1)),   # rows_finish false (order != 5)
+    "kt4_o8": _shape(df_pathway_kernel_size_t=4, df_order=8),               # fuse_c0 boundary 2 * O = 16: still c0_fused; rows_finish false
+    "kt7": _shape(df_pathway_kernel_size_t=7),           # c0_fused false by kt (so fuse_h3, presplit, dfenc false: c0 stored, tiled df_convp); streaming refused
+    "o1": _shape(df_order=1, **_look(0)),                # rows_finish false; df_out streaming (one 16-column tile per group)
+    "l4_d1": _shape(emb_num_layers=4, df_num_layers=1),  # GRU layers 1 + 3 + 1
+    "l4_d3": _shape(emb_num_layers=4, df_num_layers=3),  # 1 + 3 + 3 = 7 layers: projection followers without the emb follower
+    "l5_d3": _shape(emb_num_layers=5, df_num_layers=3),  # 1 + 4 + 3 = 8 layers = DFX_MAX_GRU_LAYERS: persistent phase without followers
+    "l2_d1": _shape(emb_num_layers=2, df_num_layers=1),  # 3 layers
+    "lg8": _shape(lin_groups=8),                         # fan_kind fails: fan / fan_skp false (separate grouped linears); df_out streaming (8 tiles per group)
+    "lg4_elg16": _shape(lin_groups=4, enc_lin_groups=16),  # fan false, enc_fan / dfenc false (fc groups of 32 outputs); df_out ggemm (Kg = 64)
+    "look31": _shape(conv_lookahead=3, df_lookahead=1),  # streaming refused (conv_lookahead != df_lookahead)
+    "c32_e64": _shape("defaults", conv_ch=32, nb_erb=64),   # fuse_enc false at conv_ch 32
+    "c32_e8_f16": _shape("defaults", conv_ch=32, nb_erb=8, nb_df=16, enc_lin_groups=8),   # smallest of everything
+    "c16_e16_f32_o6": _shape("defaults", nb_erb=16, nb_df=32, df_order=6, **_look(2)),    # conv_ch 16: no fp16-split front (fuse_h3 / presplit / fuse_tail / fuse_enc4 false)
+    "fft512": _shape(fft_size=512, hop_size=256, nb_erb=24, nb_df=64),   # general analysis / synthesis; rows_finish false
+    "hop240": _shape(hop_size=240),                      # quarter hop; rows_finish false
+}
+NAMED = ("defaults", "df3", "pf32", "df3_o10")
+
+
+def shape_params(name: str) -> ModelParams:
+    """A fresh copy of a SHAPES entry or of one of the four named configurations."""
+    import copy
+
+    return copy.deepcopy(SHAPES[name]) if name in SHAPES else named_params(name)
+
+
 def widths_for(p: ModelParams) -> np.ndarray:
     return L.erb_fb_widths(p.sr, p.fft_size, p.nb_erb, p.min_nb_freqs)
 
