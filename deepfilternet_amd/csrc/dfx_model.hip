@@ -79,7 +79,8 @@ extern "C" int dfx_model_blob_floats(const dfx_model_cfg *cfg, int64_t *n) {
 struct PwW {   // separable conv block: depthwise + pointwise(+BN) [+ pathway skip scalars]
     size_t dw = 0, wt = 0, bias = 0, sk_a = 0, sk_b = 0;
     bool has_skip = false;
-    size_t wt_h3 = 0;       // pointwise weights as pre-scaled f16 hi/lo MFMA fragments (dfx_chain_stage_h3), 0 = none (C % 32 != 0)
+    size_t wt_h3 = 0;       // pointwise weights as pre-scaled f16 hi/lo MFMA fragments (dfx_chain_stage_h3) ...
+    bool has_h3 = false;    // ... which pack_pw_h3 made for this block (the six ERB blocks where C % 32 == 0; df_conv1 has its own order: dfc1_h3)
     float unscale = 1.f;
 };
 struct GruW {
@@ -421,6 +422,56 @@ __global__ void dfx_k_gate_finish(const unsigned char *flags, int *skip_counter,
 
 enum { EV_START = 0, EV_C0, EV_C1, EV_C0P, EV_EMB, EV_COEFS, EV_FRONT, EV_DONE, EV_XA, EV_MASK, EV_FIN, EV_TICKET };
 
+// What this model can run: decided once at the end of dfx_model_create (model_capabilities: the ONLY place these rules are written) from cfg,
+// from what the optional packers packed and from the arithmetic mode.  A pass combines them with what depends on the pass (streaming window,
+// B and T against the 32-bit limits, the sw test hooks, run_df, the lane, the ticket): DfxPass::plan() / DfxStreamPass::plan().
+struct DfxCan {
+    // df_conv0's output c0 is recomputed by its consumers instead of being stored when the pathway conv has the sliding-window kernel
+    // (kt <= 5, df_order <= 8); otherwise c0 is materialised (dfx_k_conv_in_df -> dfx_k_pwconv / dfx_k_df_convp2 / dfx_k_df_convp).
+    bool fuse_c0 = false;
+    // Exact mode, batch passes: c0 is written once and read by its two consumers instead of being recomputed by both — on fp32 matrix ops a c0
+    // tile is 20 ops of 32 cycles (3 of 16 on the fp16-split path), and the two recomputing kernels side by side are the exact front's 10 ms:
+    // 28.65 vs 29.45 ms per step (the frame-by-frame runtime always uses the recomputing forms)
+    bool c0_batch_unfused = false;
+    bool c0_h3 = false;        // the fused c0 kernels on fp16-split fragments (dfx_k_df_conv01_h3, dfx_k_df_convp_h3, dfx_k_df_convp_step): fuse_c0, not exact, conv_ch % 32 == 0
+    bool c0_presplit = false;  // batch passes of such a model read the pre-split copy of feat_spec (Ws::fps; DFX_C0_PRESPLIT=0: they do not)
+    bool pw_h3 = false;        // the ERB blocks' pointwise contractions on fp16-split fragments (PwW::wt_h3 of the blocks that have them)
+    // dfx_k_emb_fan (one pass over the encoder GRU's output for emb and its consumers) where the grouped linears nest the way pack_fan needs,
+    // else the separate grouped GEMMs; fan_skp: df_skip is a grouped linear and one of the kernel's consumers (a pass: && run_df)
+    bool fan = false, fan_skp = false;
+    bool enc_fan = false;      // dfx_k_enc_fan: df_fc_emb + the encoder GRU's linear_in in one pass over c1 (pack_encfan's nesting, no enc_concat)
+    bool dfenc = false;        // dfx_k_df_enc_h3: the DF branch of the encoder as one kernel, c1 never stored (else dfx_k_df_conv01_h3 + dfx_k_enc_fan)
+    // frame-resident ERB encoder head (dfx_k_erb_enc: a frame's zero-bordered feature rows within the kernel's 192 staging lanes, two workgroups' rows
+    // within the LDS; streaming has no other form of the head) / decoder end (dfx_k_erb_dec10: convt1 + conv0_out)
+    bool fuse_enc = false, fuse_dec = false;
+    // The ERB decoder's convolutions as ONE launch (dfx_k_erb_tail: d3 / d2 / d1 stay in LDS, -12 KB per frame beside the GRU chain); otherwise
+    // three launches (convt3, convt2, convt1 + conv0_out).  Measured at config 2 (profiles/r03_fusion_ab.log): the first version (8 waves per
+    // CU) 2.19 ms alone against 1.5 ms for the three launches and +0.37 ms per step; the second (12 waves per CU, 8.5 KB of strips per wave,
+    // fragments read from LDS per k-chunk) 1.32 ms alone and -0.25 ... -0.45 ms per step.
+    // e0 = erb_conv0's output (8 KB per frame) is then not stored: the fused decoder tail recomputes it from the three feature rows it depends on
+    // (rejected: written by dfx_k_erb_enc, read back by dfx_k_erb_tail)
+    bool erb_tail = false;
+    bool erb_enc4 = false;     // the four ERB encoder convolutions as one launch (dfx_k_erb_enc4; batch passes only)
+    int df_out = DFX_PLAN_DF_OUT_GGEMM;   // df_out + tanh + c0p: DFX_PLAN_DF_OUT_RESIDENT / _STREAMING (dfx_k_df_out_h3r / _h3, a pass: while 32-bit offsets reach) or the grouped GEMM
+};
+
+// The flag block d_sync of the persistent GRU phase (dfx_k_gru_seq), word offsets.  All words are monotonic over the model's life or zeroed by
+// their users; LG = one word per (layer, 16-clip group).
+struct DfxSyncLayout {
+    static constexpr size_t LG = (size_t)DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
+    static constexpr size_t ready = 0;             // [8] per layer: gi chunks ready
+    static constexpr size_t emb = 8;               // emb chunks ready
+    static constexpr size_t probe = 13;            // the handshake's meeting counter (hwq_probe_run)
+    static constexpr size_t poison = 14;           // "a kernel of this pass raised a fault", for the synthesis (dfx_k_fault_mirror)
+    static constexpr size_t done = 16;             // [LG] chunks done per (layer, group)
+    static constexpr size_t pcnt = done + LG;      // [16] producers' completion counters (DfxPublish), one per producing stream (layer), [8] = emb
+    static constexpr size_t yprog = pcnt + 16;     // [LG] steps of y per (layer, group): the followers' hand-overs
+    static constexpr size_t giprog = yprog + LG;   // [LG] steps of gi
+    static constexpr size_t xtab = giprog + LG;    // [3 kinds][LG] XCD registrations (DfxXcd)
+    static constexpr size_t xstat = xtab + 3 * LG; // [64]: [0] light hand-overs counted (dev aid), [8..48) the followers' claim counters
+    static constexpr size_t total = xstat + 64;
+};
+
 struct dfx_model {
     dfx_model_cfg cfg{};
     float *d_w = nullptr;  // all prepared weights, one device allocation
@@ -436,34 +487,24 @@ struct dfx_model {
     std::vector<GruW> enc_gru, dec_gru, df_gru;
     size_t lsnr_w = 0;
     float lsnr_b = 0.f;
-    // dfx_k_emb_fan (one pass over the encoder GRU's output for emb and its consumers): fragments [chunks][8][64] float4, 0 chunks = the
-    // grouped linears of this model do not nest the way the kernel needs (then the separate grouped GEMMs run)
+    // The fragment sets below are optional: a packer whose shape condition fails leaves its offsets alone, and whether a kernel that reads
+    // them may run is `can`'s answer, never "is this offset non-zero".
+    // dfx_k_emb_fan: fragments [chunks][8][64] float4, fan_chunks super-chunks of 32 hidden columns (can.fan)
     size_t fan_w = 0;
-    int fan_chunks = 0;            // super-chunks of 32 hidden columns (0: not available)
-    int fan_kind[3] = {0, 0, 0};   // per consumer (dec_in, dfg_in, df_skip): 0 absent, 1 narrow (32 -> 16 groups), 2 wide (64 -> 32 groups)
-    // dfx_k_enc_fan (df_fc_emb + the encoder GRU's linear_in in one pass over c1): fragment offsets, 0 groups = shapes do not nest
+    int fan_chunks = 0;
+    // dfx_k_enc_fan: fragments of df_fc_emb (efan_groups groups) and of the encoder GRU's linear_in (can.enc_fan)
     size_t efan_w1 = 0, efan_w2 = 0;
     int efan_groups = 0;
-    // dfx_k_df_enc_h3 (df_conv0 -> df_conv1 -> df_fc_emb -> linear_in in one kernel, c1 never stored): fc / linear_in fragments; 0 chunks = the
-    // shapes do not fit (then dfx_k_df_conv01_h3 + dfx_k_enc_fan run)
+    // dfx_k_df_enc_h3 (df_conv0 -> df_conv1 -> df_fc_emb -> linear_in in one kernel): fc / linear_in fragments (can.dfenc)
     size_t dfenc_fc = 0, dfenc_in = 0;
-    int dfenc_chunks = 0;
     float dfenc_fc_unscale = 1.f, dfenc_in_unscale = 1.f;
-    // dfx_k_df_out_h3 (df_out + tanh + c0p as a row-streaming kernel of its own): fragments [G][ceil(Ng / 16)]; 0 = shapes do not fit
-    // (dfx_k_ggemm then)
+    // dfx_k_df_out_h3 / _h3r (df_out + tanh + c0p as a row-streaming kernel of its own): fragments [G][ceil(Ng / 16)] (can.df_out)
     size_t dfo_h3 = 0;
-    int dfo_nu = 0;
     float dfo_unscale = 1.f;
-    // The ERB decoder's convolutions as ONE launch (dfx_k_erb_tail: d3 / d2 / d1 stay in LDS, -12 KB per frame beside the GRU chain) where
-    // erb_tail_ok() holds; otherwise three launches (convt3, convt2, convt1 + conv0_out).  Measured at config 2 (profiles/r03_fusion_ab.log): the
-    // first version (8 waves per CU) 2.19 ms alone against 1.5 ms for the three launches and +0.37 ms per step; the second (12 waves per CU, 8.5 KB
-    // of strips per wave, fragments read from LDS per k-chunk) 1.32 ms alone and -0.25 ... -0.45 ms per step.
-    // e0 = erb_conv0's output (8 KB per frame) is then not stored: the fused decoder tail recomputes it from the three feature rows it depends on
-    // (rejected: written by dfx_k_erb_enc, read back by dfx_k_erb_tail)
     size_t cp_w1 = 0, cp_w2 = 0, cp_b = 0;   // df_convp, tiled form (kt > 5)
     size_t cp_weff = 0, cp_b16 = 0;          // df_convp, folded sliding-window form (kt <= 5)
     size_t cin_weff = 0, cin_b = 0;          // enc.df_conv0 folded into a dense 3x3 conv 2 -> C
-    // fp16-split MFMA fragments of the fused DF-encoder kernels (conv_ch % 32 == 0, kt <= 5): df_conv0, df_conv1 pointwise, df_convp
+    // fp16-split MFMA fragments of the fused DF-encoder kernels (can.c0_h3): df_conv0, df_conv1 pointwise, df_convp
     size_t c0_h3 = 0, dfc1_h3 = 0, cp_h3 = 0;
     float c0_unscale = 1.f, dfc1_unscale = 1.f, cp_unscale = 1.f;
     int cp_G = 0, cp_NO = 0;
@@ -491,12 +532,8 @@ struct dfx_model {
     int tchunk_min = 32;      // shortest chunk worth a launch (frames)
     bool run_df = true;       // DfNet(run_df=False): mask only (dfx_model_set_run_df)
     bool exact_fp32 = false;  // DFX_EXACT_FP32=1: keep the dense contractions on the exact fp32 MFMA path
-    // df_conv0's output c0 is recomputed by its consumers instead of being stored when the pathway conv has the sliding-window kernel
-    // (kt <= 5, df_order <= 8); otherwise c0 is materialised (dfx_k_conv_in_df -> dfx_k_pwconv / dfx_k_df_convp2 / dfx_k_df_convp).
-    bool fuse_c0 = true;
-    bool c0_batch_unfused = false;   // exact mode: batch passes materialise c0 (below)
-    // persistent GRU phase (dfx_k_gru_seq): flag words [ready: 8][emb: 1][pad][done: 8 * DFX_SEQ_GMAX], monotonic over the model's life
-    unsigned int *d_sync = nullptr;
+    DfxCan can;               // which kernels this model's shape, fragments and arithmetic allow (model_capabilities)
+    unsigned int *d_sync = nullptr;     // persistent GRU phase (dfx_k_gru_seq): its flag words (DfxSyncLayout)
     unsigned int *d_psync = nullptr;    // pair form of the persistent GRU phase: [DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX / 2][48] words
     mutable unsigned int seq_pbase = 0;       // step counter base of the follower hand-overs (yprog / giprog), monotonic like seq_base
     mutable int64_t passes_ps = 0;   // batch passes whose c0 kernels read the pre-split copy of feat_spec (DFX_Q_PASSES_C0_PRESPLIT)
@@ -518,6 +555,8 @@ struct dfx_model {
         bool tail_split = true;         // the ERB decoder's linear_out on a stream of its own beside the decoder tail (round 6; DFX_TAIL_SPLIT=0 in -DDFX_DEV builds)
         int64_t convp_elems = (int64_t)1 << 29;   // DFX_CONVP_ELEMS (test hook)
         bool c0_presplit = true;        // DFX_C0_PRESPLIT=0 (test hook): batch passes run the unsplit instances of dfx_k_df_enc_h3 / dfx_k_df_convp_h3 on the fp32 feat_spec
+        bool seq_trace = false;         // DFX_SEQ_TRACE=1 (dev aid): d_trace below
+        char hwq_probe_mode = 0;        // DFX_HWQ_PROBE: '0' no handshake, 'f' ("fail") a failed one, 0 the handshake before the first pass that needs it
         bool erb_enc_split = false;     // DFX_ERB_ENC_SPLIT=1 (test hook): batch passes run the ERB encoder as three launches (dfx_k_erb_enc, dfx_k_pwconv_f x 2) instead of dfx_k_erb_enc4
     } sw;
     // Error words, written by kernels, read by the host (page-locked host memory the device can store to: dfx_env_err_words_alloc):
@@ -541,6 +580,10 @@ struct Prep {
     std::vector<float> out;
     std::string err;
     bool exact_fp32 = false;   // the model is created under DFX_EXACT_FP32=1: weights that only the exact kernels read are packed
+    struct Packed {            // which optional fragment sets the packers made (each states its shape condition at its head); model_capabilities reads it
+        bool pw = false, tail = false, c0 = false, fan = false, fan_skp = false, encfan = false, dfenc = false;
+        int dfo_tiles = 0;     // 16-column tiles per group of df_out's fragments (0: not packed)
+    } packed;
     const float *get(const std::string &name, const DfxTensor **tt = nullptr) {
         const DfxTensor *t = man.find(name);
         if (!t) {
@@ -600,17 +643,23 @@ bool prep_path(Prep &P, const std::string &name, int C, size_t &a_off, size_t &b
 }
 // fp16-split MFMA A fragments: nfrag fragments of [hi, lo][64 lanes][8 halves]; val(frag, lane, i) is the fp32 weight of that slot.
 // All values are scaled by one power of two so that the largest is just below 2^14 (lo parts stay normal f16); *unscale undoes it.
+// val may read P.out: the values are taken first, the fragments carved afterwards (alloc may move P.out).
 template <typename F>
 size_t pack_h3(Prep &P, int nfrag, F val, float *unscale) {
+    std::vector<float> v((size_t)nfrag * 64 * 8);
     float mx = 0.f;
     for (int fr = 0; fr < nfrag; ++fr)
         for (int l = 0; l < 64; ++l)
-            for (int i = 0; i < 8; ++i) mx = fmaxf(mx, fabsf(val(fr, l, i)));
+            for (int i = 0; i < 8; ++i) {
+                const float w = val(fr, l, i);
+                v[((size_t)fr * 64 + l) * 8 + i] = w;
+                mx = fmaxf(mx, fabsf(w));
+            }
     int e = 0;
     if (mx > 0.f) {
         int ex;
-        frexpf(mx, &ex);
-        e = 14 - ex;
+        frexpf(mx, &ex);          // mx = f * 2^ex, f in [0.5, 1)
+        e = 14 - ex;              // scaled magnitude < 2^14
         if (e > 24) e = 24;
         if (e < -14) e = -14;
     }
@@ -621,7 +670,7 @@ size_t pack_h3(Prep &P, int nfrag, F val, float *unscale) {
     for (int fr = 0; fr < nfrag; ++fr)
         for (int l = 0; l < 64; ++l)
             for (int i = 0; i < 8; ++i) {
-                const float w = val(fr, l, i) * sc;
+                const float w = v[((size_t)fr * 64 + l) * 8 + i] * sc;
                 const uint16_t hb = dfx_f32_to_f16_bits(w);
                 const uint16_t lb = dfx_f32_to_f16_bits(w - dfx_f16_bits_to_f32(hb));
                 dst[(((size_t)fr * 2 + 0) * 64 + l) * 8 + i] = hb;
@@ -629,16 +678,37 @@ size_t pack_h3(Prep &P, int nfrag, F val, float *unscale) {
             }
     return off;
 }
+// The fp32 twin for the GRU weights w [3 H][H] (H = 256), in dfx_k_gru_rec_h3's fragment order: [16-unit tile][k-chunk][gate][half][lane][4],
+// half h = weights 32 kc + 8 q + 4 h + 0..3 of the lane's unit
+size_t pack_x32(Prep &P, const float *w) {
+    const int H = 256;
+    const size_t off = P.alloc((size_t)3 * H * H);
+    float *dst = &P.out[off];
+    for (int ut = 0; ut < 16; ++ut)
+        for (int kc = 0; kc < 8; ++kc)
+            for (int gate = 0; gate < 3; ++gate)
+                for (int half = 0; half < 2; ++half)
+                    for (int l = 0; l < 64; ++l)
+                        for (int i = 0; i < 4; ++i) {
+                            const int unit = 16 * ut + (l & 15), k = 32 * kc + 8 * (l >> 4) + 4 * half + i;
+                            const size_t frag = (((size_t)ut * 8 + kc) * 3 + gate) * 2 + half;
+                            dst[(frag * 64 + l) * 4 + i] = w[(size_t)(gate * H + unit) * H + k];
+                        }
+    return off;
+}
 // pointwise weights of a separable block as dfx_chain_stage_h3's A fragments: fragment (nt, kc), lane l, element i = the weight of output
 // channel 16 nt + (l & 15) for input channel (C/4) (l >> 4) + 8 kc + i (lane (pos, q) owns the C/4 consecutive channels from (C/4) q)
-void pack_pw_h3(Prep &P, int C, PwW &w) {
+void pack_pw_h3(Prep &P, dfx_model *m) {   // the six ERB blocks (df_conv1 has its own order: dfc1_h3)
+    const int C = m->cfg.conv_ch, KC = C / 32;
     if (C % 32 != 0) return;
-    const int KC = C / 32;
-    const std::vector<float> src(P.out.begin() + (long)w.wt, P.out.begin() + (long)w.wt + (size_t)C * C);   // pack_h3 may reallocate P.out
-    w.wt_h3 = pack_h3(P, (C / 16) * KC, [&](int fr, int l, int i) {
-        const int nt = fr / KC, kc = fr % KC;
-        return src[(size_t)((C / 4) * (l >> 4) + 8 * kc + i) * C + 16 * nt + (l & 15)];
-    }, &w.unscale);
+    for (PwW *w : {&m->erb1, &m->erb2, &m->erb3, &m->ct3, &m->ct2, &m->ct1}) {
+        w->wt_h3 = pack_h3(P, (C / 16) * KC, [&](int fr, int l, int i) {
+            const int nt = fr / KC, kc = fr % KC;
+            return P.out[w->wt + (size_t)((C / 4) * (l >> 4) + 8 * kc + i) * C + 16 * nt + (l & 15)];
+        }, &w->unscale);
+        w->has_h3 = true;
+    }
+    P.packed.pw = true;
 }
 bool prep_glin(Prep &P, const std::string &name, GlinW &g) {
     const DfxTensor *t = nullptr;
@@ -660,20 +730,21 @@ bool prep_glin(Prep &P, const std::string &name, GlinW &g) {
 //     i = 4 + 8 c + 2 u + t   narrow consumer c, output column 16 u + m: W_c[2J + u][16 t + 4 kq + s][m]
 //     i = 4 + 8 c + 4 u + tt  wide consumer c, output column 16 u + m:   W_c[J][16 tt + 4 kq + s][16 u + m]
 void pack_fan(Prep &P, dfx_model *m) {
+    int kind[DFX_FAN_NC];   // per consumer (dec_in, dfg_in, df_skip): 0 absent, 1 narrow (32 -> 16 groups), 2 wide (64 -> 32 groups)
     const GlinW &o = m->enc_out;
     const GlinW *cons[DFX_FAN_NC] = {&m->dec_in, &m->dfg_in, m->cfg.df_gru_skip == DFX_SKIP_GROUPEDLINEAR ? &m->df_skip : nullptr};
     if (o.Kg != 16 || o.Ng != 32 || o.G % 2 != 0) return;
     const int nj = o.G / 2;
     for (int c = 0; c < DFX_FAN_NC; ++c) {
         const GlinW *g = cons[c];
-        m->fan_kind[c] = 0;
+        kind[c] = 0;
         if (!g) continue;
-        if (g->G == 2 * nj && g->Kg == 32 && g->Ng == 16) m->fan_kind[c] = 1;
-        else if (g->G == nj && g->Kg == 64 && g->Ng == 32) m->fan_kind[c] = 2;
+        if (g->G == 2 * nj && g->Kg == 32 && g->Ng == 16) kind[c] = 1;
+        else if (g->G == nj && g->Kg == 64 && g->Ng == 32) kind[c] = 2;
         else return;
     }
     // the instantiated combinations (launch_emb_fan)
-    if (m->fan_kind[0] != 1 || m->fan_kind[1] != 2 || (m->fan_kind[2] != 1 && m->fan_kind[2] != 0)) return;
+    if (kind[0] != 1 || kind[1] != 2 || (kind[2] != 1 && kind[2] != 0)) return;
     const size_t off = P.alloc((size_t)nj * DFX_FAN_WPJ * 64 * 4);   // (may reallocate P.out: offsets only below)
     auto frag = [&](int J, int i, int l, int sidx) -> float & { return P.out[off + (((size_t)J * DFX_FAN_WPJ + i) * 64 + l) * 4 + sidx]; };
     for (int J = 0; J < nj; ++J)
@@ -683,11 +754,11 @@ void pack_fan(Prep &P, dfx_model *m) {
                 for (int ch = 0; ch < 2; ++ch)
                     for (int t = 0; t < 2; ++t) frag(J, 2 * ch + t, l, sidx) = P.out[o.w + ((size_t)(2 * J + ch) * 16 + 4 * kq + sidx) * 32 + 16 * t + mm];
                 for (int c = 0; c < DFX_FAN_NC; ++c) {
-                    if (m->fan_kind[c] == 1) {
+                    if (kind[c] == 1) {
                         for (int u = 0; u < 2; ++u)
                             for (int t = 0; t < 2; ++t)
                                 frag(J, 4 + 8 * c + 2 * u + t, l, sidx) = P.out[cons[c]->w + ((size_t)(2 * J + u) * 32 + 16 * t + 4 * kq + sidx) * 16 + mm];
-                    } else if (m->fan_kind[c] == 2) {
+                    } else if (kind[c] == 2) {
                         for (int u = 0; u < 2; ++u)
                             for (int tt = 0; tt < 4; ++tt)
                                 frag(J, 4 + 8 * c + 4 * u + tt, l, sidx) = P.out[cons[c]->w + ((size_t)J * 64 + 16 * tt + 4 * kq + sidx) * 32 + 16 * u + mm];
@@ -697,6 +768,7 @@ void pack_fan(Prep &P, dfx_model *m) {
         }
     m->fan_w = off;
     m->fan_chunks = nj;
+    P.packed.fan = true, P.packed.fan_skp = kind[2] == 1;
 }
 // Fragments of dfx_k_enc_fan: df_fc_emb in groups of 96 -> 16 (enc_lin_groups = 32 over 3072 -> 512) feeding linear_in of the encoder GRU in
 // groups of 32 -> 16 (lin_groups = 16 over 512 -> 256), i.e. two groups of the first per group of the second.
@@ -717,6 +789,7 @@ void pack_encfan(Prep &P, dfx_model *m) {
     }
     m->efan_w1 = o1, m->efan_w2 = o2;
     m->efan_groups = a.G;
+    P.packed.encfan = true;
 }
 bool prep_gru(Prep &P, const std::string &name, int layers, std::vector<GruW> &out) {
     const int H = 256;
@@ -740,101 +813,23 @@ bool prep_gru(Prep &P, const std::string &name, int layers, std::vector<GruW> &o
                     for (int e = 0; e < 4; ++e)
                         P.out[g.whh4 + ((((size_t)k4 * 3 + gate) * H + j) * 4 + e)] = whh[(size_t)(gate * H + j) * H + 4 * k4 + e];
         for (int j = 0; j < H; ++j) P.out[g.bhn + j] = bhh[2 * H + j];
-        {   // fp16-split fragments of W[k][n] = wih[n][k]: [n/64][kc][ct][hi,lo][lane][8], scaled by 2^e so that lo is a normal f16
-            float mx = 0.f;
-            for (size_t i = 0; i < (size_t)3 * H * H; ++i) mx = fmaxf(mx, fabsf(wih[i]));
-            int e = 0;
-            if (mx > 0.f) {
-                int ex;
-                frexpf(mx, &ex);          // mx = f * 2^ex, f in [0.5, 1)
-                e = 14 - ex;              // scaled magnitude < 2^14
-                if (e > 24) e = 24;
-                if (e < -14) e = -14;
-            }
-            const float sc = ldexpf(1.f, e);
-            g.wih_unscale = ldexpf(1.f, -e);
-            const size_t nh = (size_t)3 * H * H * 2;  // halves
-            g.wih_h3 = P.alloc(nh / 2);
-            uint16_t *dst = reinterpret_cast<uint16_t *>(&P.out[g.wih_h3]);
-            for (int ch = 0; ch < 3 * H / 64; ++ch)
-                for (int kc = 0; kc < 8; ++kc)
-                    for (int ct = 0; ct < 4; ++ct)
-                        for (int l = 0; l < 64; ++l)
-                            for (int i = 0; i < 8; ++i) {
-                                const int n = ch * 64 + ct * 16 + (l & 15), k = 32 * kc + 8 * (l >> 4) + i;
-                                const float w = wih[(size_t)n * H + k] * sc;
-                                const uint16_t hb = dfx_f32_to_f16_bits(w);
-                                const uint16_t lb = dfx_f32_to_f16_bits(w - dfx_f16_bits_to_f32(hb));
-                                const size_t frag = (((size_t)ch * 8 + kc) * 4 + ct) * 2;
-                                dst[((frag + 0) * 64 + l) * 8 + i] = hb;
-                                dst[((frag + 1) * 64 + l) * 8 + i] = lb;
-                            }
-        }
-        auto pack_whh_pj = [&](float sc) {   // W_hh in the same fragment order (dfx_k_gru_step_h3)
-            g.whh_pj = P.alloc((size_t)3 * H * H);
-            uint16_t *dst = reinterpret_cast<uint16_t *>(&P.out[g.whh_pj]);
-            for (int ch = 0; ch < 3 * H / 64; ++ch)
-                for (int kc = 0; kc < 8; ++kc)
-                    for (int ct = 0; ct < 4; ++ct)
-                        for (int l = 0; l < 64; ++l)
-                            for (int i = 0; i < 8; ++i) {
-                                const int n = ch * 64 + ct * 16 + (l & 15), k = 32 * kc + 8 * (l >> 4) + i;
-                                const float w = whh[(size_t)n * H + k] * sc;
-                                const uint16_t hb = dfx_f32_to_f16_bits(w);
-                                const uint16_t lb = dfx_f32_to_f16_bits(w - dfx_f16_bits_to_f32(hb));
-                                const size_t frag = (((size_t)ch * 8 + kc) * 4 + ct) * 2;
-                                dst[((frag + 0) * 64 + l) * 8 + i] = hb;
-                                dst[((frag + 1) * 64 + l) * 8 + i] = lb;
-                            }
+        // fp16-split fragments [n/64][kc][ct] of W[k][n] = w[n][k] (dfx_k_proj256_h3; W_hh in the same order: dfx_k_gru_step_h3) ...
+        auto proj_order = [&](const float *w) {
+            return [w](int fr, int l, int i) {
+                const int ch = fr / 32, kc = fr / 4 % 8, ct = fr % 4;
+                return w[(size_t)(ch * 64 + ct * 16 + (l & 15)) * H + 32 * kc + 8 * (l >> 4) + i];
+            };
         };
-        {   // W_hh fragments for dfx_k_gru_rec_h3: [16-unit tile][k-chunk][gate][hi,lo][lane][8]
-            float mx = 0.f;
-            for (size_t i = 0; i < (size_t)3 * H * H; ++i) mx = fmaxf(mx, fabsf(whh[i]));
-            int e = 0;
-            if (mx > 0.f) {
-                int ex;
-                frexpf(mx, &ex);
-                e = 14 - ex;
-                if (e > 24) e = 24;
-                if (e < -14) e = -14;
-            }
-            const float sc = ldexpf(1.f, e);
-            g.whh_unscale = ldexpf(1.f, -e);
-            pack_whh_pj(sc);
-            g.whh_h3 = P.alloc((size_t)3 * H * H);  // 2 halves per weight
-            uint16_t *dst = reinterpret_cast<uint16_t *>(&P.out[g.whh_h3]);
-            for (int ut = 0; ut < 16; ++ut)          // 16-unit tile
-                for (int kc = 0; kc < 8; ++kc)
-                    for (int gate = 0; gate < 3; ++gate)
-                        for (int l = 0; l < 64; ++l)
-                            for (int i = 0; i < 8; ++i) {
-                                const int unit = 16 * ut + (l & 15), k = 32 * kc + 8 * (l >> 4) + i;
-                                const float v = whh[(size_t)(gate * H + unit) * H + k] * sc;
-                                const uint16_t hb = dfx_f32_to_f16_bits(v);
-                                const uint16_t lb = dfx_f32_to_f16_bits(v - dfx_f16_bits_to_f32(hb));
-                                const size_t frag = (((size_t)ut * 8 + kc) * 3 + gate) * 2;
-                                dst[((frag + 0) * 64 + l) * 8 + i] = hb;
-                                dst[((frag + 1) * 64 + l) * 8 + i] = lb;
-                            }
-        }
-        // the same fragment order in fp32: [16-unit tile][k-chunk][gate][half][lane][4], half h = weights 32 kc + 8 q + 4 h + 0..3 of the lane's unit
-        auto pack_x32 = [&](const float *w) {
-            const size_t off = P.alloc((size_t)3 * H * H);
-            float *dst = &P.out[off];
-            for (int ut = 0; ut < 16; ++ut)
-                for (int kc = 0; kc < 8; ++kc)
-                    for (int gate = 0; gate < 3; ++gate)
-                        for (int half = 0; half < 2; ++half)
-                            for (int l = 0; l < 64; ++l)
-                                for (int i = 0; i < 4; ++i) {
-                                    const int unit = 16 * ut + (l & 15), k = 32 * kc + 8 * (l >> 4) + 4 * half + i;
-                                    const size_t frag = (((size_t)ut * 8 + kc) * 3 + gate) * 2 + half;
-                                    dst[(frag * 64 + l) * 4 + i] = w[(size_t)(gate * H + unit) * H + k];
-                                }
-            return off;
+        // ... and [16-unit tile][k-chunk][gate] of W_hh (dfx_k_gru_rec_h3); both forms of W_hh carry the one scale that max |W_hh| gives
+        auto rec_order = [whh](int fr, int l, int i) {
+            const int ut = fr / 24, kc = fr / 3 % 8, gate = fr % 3;
+            return whh[(size_t)(gate * H + 16 * ut + (l & 15)) * H + 32 * kc + 8 * (l >> 4) + i];
         };
-        g.whh_x32 = pack_x32(whh);
-        if (P.exact_fp32) g.wih_x32 = pack_x32(wih), g.has_wih_x32 = true;   // (fp16-split models do not carry it)
+        g.wih_h3 = pack_h3(P, 3 * H / 64 * 8 * 4, proj_order(wih), &g.wih_unscale);
+        g.whh_pj = pack_h3(P, 3 * H / 64 * 8 * 4, proj_order(whh), &g.whh_unscale);
+        g.whh_h3 = pack_h3(P, 16 * 8 * 3, rec_order, &g.whh_unscale);
+        g.whh_x32 = pack_x32(P, whh);
+        if (P.exact_fp32) g.wih_x32 = pack_x32(P, wih), g.has_wih_x32 = true;   // (fp16-split models do not carry it)
         out.push_back(g);
     }
     return true;
@@ -967,7 +962,7 @@ static void hwq_probe_run(dfx_model *m) {
         if (ln.ps[i]) ss.push_back(ln.ps[i]);
     for (int i = 0; i < 2; ++i)
         if (ln.ts[i]) ss.push_back(ln.ts[i]);
-    unsigned int *cnt = m->d_sync + 13;   // (a spare word of the flag block: ready 0-7 | emb 8 | probe 13 | done 16-)
+    unsigned int *cnt = m->d_sync + DfxSyncLayout::probe;
     // warm-up: the kernel's code object is loaded and every stream's queue exists before the bounded handshake starts (a slow first
     // launch must not look like a shared queue); a failed handshake is tried once more with a longer bound before it counts
     for (hipStream_t st : ss) dfx_launch(dfx_k_probe_meet, dim3(1), dim3(64), 0, st, cnt, 0u, 1, m->d_err + 9);
@@ -988,212 +983,336 @@ static void hwq_probe_run(dfx_model *m) {
     if (m->hwq_probe == 0) hwq_probe_fallback(m);
 }
 
+// ------------------------------------------------------------------------------------------------ model creation
+// Weight preparation: BatchNorm folded into the layer in front of it, every array re-laid-out the way its kernel reads it, carved from P.out
+// in the order of the steps below (prepare_weights).  A step returns false where a tensor is missing (P.err names it).
+namespace {
+// enc.erb_conv0: pad(.0) conv(.1) bn(.2)
+bool prep_erb_conv0(Prep &P, dfx_model *m) {
+    const int C = m->cfg.conv_ch;
+    const float *w = P.get("enc.erb_conv0.1.weight");
+    std::vector<float> sc, sh;
+    if (!w || !P.bn("enc.erb_conv0.2", C, sc, sh)) return false;
+    m->erb0_w = P.alloc(9 * C);
+    m->erb0_b = P.alloc(C);
+    for (int ch = 0; ch < C; ++ch) {
+        for (int k = 0; k < 9; ++k) P.out[m->erb0_w + k * C + ch] = w[ch * 9 + k] * sc[ch];
+        P.out[m->erb0_b + ch] = sh[ch];
+    }
+    return true;
+}
+// enc.df_conv0: pad(.0) conv groups=2 (.1) pointwise(.2) bn(.3), folded into one dense conv (K = 18 -> 20)
+bool prep_df_conv0(Prep &P, dfx_model *m) {
+    const int C = m->cfg.conv_ch;
+    const float *w = P.get("enc.df_conv0.1.weight"), *pw = P.get("enc.df_conv0.2.weight");
+    std::vector<float> sc, sh;
+    if (!w || !pw || !P.bn("enc.df_conv0.3", C, sc, sh)) return false;
+    m->cin_weff = P.alloc((size_t)20 * C);
+    m->cin_b = P.alloc(C);
+    for (int n = 0; n < C; ++n) {
+        for (int tap = 0; tap < 9; ++tap)
+            for (int ch = 0; ch < 2; ++ch) {
+                double acc = 0.0;  // groups=2: output channel c of the 3x3 conv sees input ch = c / (C/2)
+                for (int c = ch * (C / 2); c < (ch + 1) * (C / 2); ++c) acc += (double)pw[(size_t)n * C + c] * (double)w[c * 9 + tap];
+                P.out[m->cin_weff + (size_t)(tap * 2 + ch) * C + n] = (float)(acc * (double)sc[n]);
+            }
+        P.out[m->cin_b + n] = sh[n];
+    }
+    return true;
+}
+bool prep_lsnr(Prep &P, dfx_model *m) {
+    const float *w = P.get("enc.lsnr_fc.0.weight"), *b = P.get("enc.lsnr_fc.0.bias");
+    if (!w || !b) return false;
+    const int emb = m->cfg.conv_ch * m->cfg.nb_erb / 4;
+    m->lsnr_w = P.alloc(emb);
+    memcpy(&P.out[m->lsnr_w], w, sizeof(float) * emb);
+    m->lsnr_b = b[0];
+    return true;
+}
+// erb_dec.conv0_out: conv [1,C,1,3] (.0) bn(1) (.1)
+bool prep_conv0_out(Prep &P, dfx_model *m) {
+    const int C = m->cfg.conv_ch;
+    const float *w = P.get("erb_dec.conv0_out.0.weight");
+    std::vector<float> sc, sh;
+    if (!w || !P.bn("erb_dec.conv0_out.1", 1, sc, sh)) return false;
+    m->co_w = P.alloc(3 * C);
+    for (int ch = 0; ch < C; ++ch)
+        for (int j = 0; j < 3; ++j) P.out[m->co_w + j * C + ch] = w[ch * 3 + j] * sc[0];
+    m->co_bias = sh[0];
+    return true;
+}
+// matrix-op forms of the two small contractions inside dfx_k_erb_tail (round 5)
+void pack_tail_h3(Prep &P, dfx_model *m) {
+    const int C = m->cfg.conv_ch;
+    if (C % 32 != 0) return;
+    const int KC = C / 32;
+    const size_t w0 = m->erb0_w, b0 = m->erb0_b, wo = m->co_w;
+    // erb_conv0 as [C x 32] fragments per 16 channels: k-slot 8 (l >> 4) + i = tap 3 kt + kf for k < 9, the bias (against a constant 1) at k = 9
+    m->tail_w0h3 = pack_h3(P, C / 16, [&](int nt, int l, int i) {
+        const int k = 8 * (l >> 4) + i, ch = 16 * nt + (l & 15);
+        return k < 9 ? P.out[w0 + (size_t)k * C + ch] : (k == 9 ? P.out[b0 + ch] : 0.f);
+    }, &m->tail_w0_unscale);
+    // conv0_out's three taps as the rows 0..2 of one 16-row tile; the contraction index is enumerated the way a D fragment leaves it (lane
+    // (position, q): element 8 kc + i <-> channel 16 ((8 kc + i) >> 2) + 4 q + ((8 kc + i) & 3))
+    m->tail_woh3 = pack_h3(P, KC, [&](int kc, int l, int i) {
+        const int j = l & 15, e = 8 * kc + i, ch = 16 * (e >> 2) + 4 * (l >> 4) + (e & 3);
+        return j < 3 ? P.out[wo + (size_t)j * C + ch] : 0.f;
+    }, &m->tail_wo_unscale);
+    P.packed.tail = true;
+}
+// df_dec.df_convp: the tiled form (dfx_k_df_convp on a materialised c0) and, where 2 * df_order <= 16, the folded sliding-window form
+bool prep_df_convp(Prep &P, dfx_model *m) {
+    const dfx_model_cfg &c = m->cfg;
+    const int C = c.conv_ch, kt = c.df_pathway_kernel_size_t, NO = 2 * c.df_order, G = dfx_gcd(C, NO), CG = C / G, OG = NO / G;
+    const int idx = kt > 1 ? 1 : 0;
+    const bool has_pw = kt > 1;  // separable only if groups > 1 and max(kernel) > 1; groups > 1 always holds (2 | C, 2O)
+    const float *w = P.get("df_dec.df_convp." + std::to_string(idx) + ".weight");
+    const float *pw = has_pw ? P.get("df_dec.df_convp." + std::to_string(idx + 1) + ".weight") : nullptr;
+    std::vector<float> sc, sh;
+    if (!w || (has_pw && !pw) || !P.bn("df_dec.df_convp." + std::to_string(idx + (has_pw ? 2 : 1)), NO, sc, sh)) return false;
+    m->cp_G = G;
+    m->cp_NO = NO;
+    m->cp_w1 = P.alloc((size_t)G * kt * CG * 16);
+    m->cp_w2 = P.alloc((size_t)NO * NO);
+    m->cp_b = P.alloc(NO);
+    for (int g = 0; g < G; ++g)
+        for (int k = 0; k < kt; ++k)
+            for (int ci = 0; ci < CG; ++ci)
+                for (int o = 0; o < OG; ++o) {
+                    // weight [NO, CG, kt, 1]
+                    float v = w[(((size_t)(g * OG + o) * CG + ci) * kt + k)];
+                    if (!has_pw) v *= sc[g * OG + o];
+                    P.out[m->cp_w1 + ((((size_t)g * kt + k) * CG + ci) * 16 + o)] = v;
+                }
+    for (int n = 0; n < NO; ++n) {
+        for (int o = 0; o < NO; ++o) P.out[m->cp_w2 + (size_t)n * NO + o] = has_pw ? pw[(size_t)n * NO + o] * sc[n] : (n == o ? 1.f : 0.f);
+        P.out[m->cp_b + n] = sh[n];
+    }
+    // folded form: W_eff[k][c][n] = scale[n] * sum_o PW[n][o] * W1[o][c - group(o)*CG][k]   (PW = identity if absent).
+    // One 16-wide MFMA tile of outputs: 2 * df_order <= 16; longer filters (BASELINE.json configs[4]: df_order = 10) take the
+    // tiled kernel dfx_k_df_convp on a materialised c0.
+    const bool folded = NO <= 16;
+    m->cp_weff = P.alloc(folded ? (size_t)kt * C * 16 : 0);
+    m->cp_b16 = P.alloc(16);
+    for (int k = 0; folded && k < kt; ++k)
+        for (int ch = 0; ch < C; ++ch) {
+            const int g = ch / CG, ci = ch - g * CG;
+            for (int n = 0; n < NO; ++n) {
+                double acc = 0.0;
+                for (int o = g * OG; o < (g + 1) * OG; ++o) {
+                    const double p2 = has_pw ? (double)pw[(size_t)n * NO + o] : (n == o ? 1.0 : 0.0);
+                    acc += p2 * (double)w[((size_t)o * CG + ci) * kt + k];
+                }
+                P.out[m->cp_weff + ((size_t)k * C + ch) * 16 + n] = (float)(acc * (double)sc[n]);
+            }
+        }
+    for (int n = 0; folded && n < NO; ++n) P.out[m->cp_b16 + n] = sh[n];
+    return true;
+}
+// fragments of the fused fp16-split DF-encoder kernels (dfx_k_df_conv01_h3, dfx_k_df_convp_h3): df_conv0, df_conv1's pointwise, folded df_convp
+void pack_c0_h3(Prep &P, dfx_model *m) {
+    const dfx_model_cfg &c = m->cfg;
+    const int C = c.conv_ch, kt = c.df_pathway_kernel_size_t;
+    if (C % 32 != 0 || 2 * c.df_order > 16) return;   // (df_convp has its folded form)
+    const int KC = C / 32;
+    // channel a lane (q = l>>4) feeds as element i of k-chunk kc after dfx_c0_tile
+    auto chan = [](int kc, int l, int i) { const int e = 8 * kc + i; return 16 * (e >> 2) + 4 * (l >> 4) + (e & 3); };
+    const size_t cin = m->cin_weff, wt1 = m->dfc1.wt, cpw = m->cp_weff;
+    m->c0_h3 = pack_h3(P, C / 16, [&](int nt, int l, int i) {
+        const int k = 8 * (l >> 4) + i;
+        return k < 18 ? P.out[cin + (size_t)k * C + 16 * nt + (l & 15)] : 0.f;
+    }, &m->c0_unscale);
+    m->dfc1_h3 = pack_h3(P, (C / 16) * KC, [&](int fr, int l, int i) {
+        const int nt = fr / KC, kc = fr % KC;
+        return P.out[wt1 + (size_t)chan(kc, l, i) * C + 16 * nt + (l & 15)];
+    }, &m->dfc1_unscale);
+    m->cp_h3 = pack_h3(P, kt * KC, [&](int fr, int l, int i) {
+        const int k = fr / KC, kc = fr % KC;
+        return P.out[cpw + ((size_t)k * C + chan(kc, l, i)) * 16 + (l & 15)];
+    }, &m->cp_unscale);
+    P.packed.c0 = true;
+}
+// fragments of dfx_k_df_out_h3: [G][ceil(Ng / 16)] tiles of 32 x 16
+void pack_dfo_h3(Prep &P, dfx_model *m) {
+    const GlinW a = m->df_out;
+    const int NO = 2 * m->cfg.df_order, Fd = m->cfg.nb_df;
+    if (!(a.Kg <= 32 && a.Kg % 8 == 0 && a.Ng % 2 == 0 && NO % 2 == 0 && Fd % 2 == 0 && (int64_t)a.G * a.Ng == (int64_t)NO * Fd &&
+          DFX_DFO_SMEM(NO, Fd) <= (size_t)64 * 1024))
+        return;
+    const int NU = (a.Ng + 15) / 16;
+    m->dfo_h3 = pack_h3(P, a.G * NU, [&](int fr, int l, int i) {
+        const int g = fr / NU, u = fr % NU, o = 16 * u + (l & 15), k = 8 * (l >> 4) + i;
+        return o < a.Ng && k < a.Kg ? P.out[a.w + ((size_t)g * a.Kg + k) * a.Ng + o] : 0.f;
+    }, &m->dfo_unscale);
+    P.packed.dfo_tiles = NU;
+}
+// fragments of the fused DF branch of the encoder (dfx_k_df_enc_h3): df_fc_emb in groups of 32 n -> 16 feeding linear_in in groups of 32 -> 16,
+// behind the c0 fragments
+void pack_dfenc_h3(Prep &P, dfx_model *m) {
+    const GlinW a = m->fc_emb, b = m->enc_in;
+    const int C = m->cfg.conv_ch, Fout = m->cfg.nb_df / 2, KC = C / 32;
+    if (!P.packed.c0) return;
+    if (!(a.Kg % 32 == 0 && a.Ng == 16 && b.Kg == 32 && b.Ng == 16 && b.G * 2 == a.G && (int64_t)a.G * a.Kg == (int64_t)Fout * C)) return;
+    // chunk ci = fo * KC + kc; lane (o = l & 15, q = l >> 4), element i <-> channel 16 ((8 kc + i) >> 2) + 4 q + (i & 3) of bin fo (the order
+    // in which dfx_k_df_conv01_h3's D fragments hold df_conv1's output)
+    m->dfenc_fc = pack_h3(P, Fout * KC, [&](int ci, int l, int i) {
+        const int fo = ci / KC, kc = ci % KC, ch = 16 * ((8 * kc + i) >> 2) + 4 * (l >> 4) + (i & 3);
+        const int idx = fo * C + ch, g = idx / a.Kg, kin = idx % a.Kg;
+        return P.out[a.w + ((size_t)g * a.Kg + kin) * 16 + (l & 15)];
+    }, &m->dfenc_fc_unscale);
+    // linear_in group j: element i <-> feature 16 (i >> 2) + 4 q + (i & 3) of its 32 inputs (two finished fc groups)
+    m->dfenc_in = pack_h3(P, b.G, [&](int j, int l, int i) {
+        return P.out[b.w + ((size_t)j * 32 + 16 * (i >> 2) + 4 * (l >> 4) + (i & 3)) * 16 + (l & 15)];
+    }, &m->dfenc_in_unscale);
+    P.packed.dfenc = true;
+}
+
+// All of it, in the order of the packed array.  The optional packers (pack_*: void) state their own shape conditions and note in P.packed
+// what they made.
+bool prepare_weights(Prep &P, dfx_model *m) {
+    const dfx_model_cfg &c = m->cfg;
+    const int C = c.conv_ch;
+    const bool skip_enc = c.emb_gru_skip_enc == DFX_SKIP_GROUPEDLINEAR, skip_dec = c.emb_gru_skip == DFX_SKIP_GROUPEDLINEAR;
+    // encoder convolutions
+    if (!prep_erb_conv0(P, m)) return false;
+    if (!prep_sep(P, "enc.erb_conv1", C, m->erb1) || !prep_sep(P, "enc.erb_conv2", C, m->erb2) || !prep_sep(P, "enc.erb_conv3", C, m->erb3) ||
+        !prep_sep(P, "enc.df_conv1", C, m->dfc1))
+        return false;
+    if (!prep_df_conv0(P, m)) return false;
+    // encoder GRU, lsnr, ERB decoder GRU stack
+    if (!prep_glin(P, "enc.df_fc_emb.0.weight", m->fc_emb) || !prep_glin(P, "enc.emb_gru.linear_in.0.weight", m->enc_in) ||
+        !prep_gru(P, "enc.emb_gru.gru", 1, m->enc_gru) || !prep_glin(P, "enc.emb_gru.linear_out.0.weight", m->enc_out))
+        return false;
+    if (skip_enc && !prep_glin(P, "enc.emb_gru.gru_skip.weight", m->enc_skip)) return false;
+    if (skip_dec && !prep_glin(P, "erb_dec.emb_gru.gru_skip.weight", m->dec_skip)) return false;
+    if (!prep_lsnr(P, m)) return false;
+    if (!prep_glin(P, "erb_dec.emb_gru.linear_in.0.weight", m->dec_in) || !prep_gru(P, "erb_dec.emb_gru.gru", c.emb_num_layers - 1, m->dec_gru) ||
+        !prep_glin(P, "erb_dec.emb_gru.linear_out.0.weight", m->dec_out))
+        return false;
+    // ERB decoder blocks with their pathway scalars, the pointwise fragments of the six ERB blocks, conv0_out, the tail's two small sets
+    if (!prep_sep(P, "erb_dec.convt3", C, m->ct3) || !prep_path(P, "erb_dec.conv3p", C, m->ct3.sk_a, m->ct3.sk_b) ||
+        !prep_sep(P, "erb_dec.convt2", C, m->ct2) || !prep_path(P, "erb_dec.conv2p", C, m->ct2.sk_a, m->ct2.sk_b) ||
+        !prep_sep(P, "erb_dec.convt1", C, m->ct1) || !prep_path(P, "erb_dec.conv1p", C, m->ct1.sk_a, m->ct1.sk_b) ||
+        !prep_path(P, "erb_dec.conv0p", C, m->co_ska, m->co_skb))
+        return false;
+    m->ct3.has_skip = m->ct2.has_skip = m->ct1.has_skip = true;
+    pack_pw_h3(P, m);
+    if (!prep_conv0_out(P, m)) return false;
+    pack_tail_h3(P, m);
+    // DF decoder: df_convp (tiled, folded, fragments), GRU stack, df_out
+    if (!prep_df_convp(P, m)) return false;
+    pack_c0_h3(P, m);
+    if (!prep_glin(P, "df_dec.df_gru.linear_in.0.weight", m->dfg_in) || !prep_gru(P, "df_dec.df_gru.gru", c.df_num_layers, m->df_gru)) return false;
+    if (c.df_gru_skip == DFX_SKIP_GROUPEDLINEAR && !prep_glin(P, "df_dec.df_skip.weight", m->df_skip)) return false;
+    if (!prep_glin(P, "df_dec.df_out.0.weight", m->df_out)) return false;
+    // fragment sets of the fan-out kernels
+    pack_fan(P, m);
+    pack_encfan(P, m);
+    pack_dfo_h3(P, m);
+    pack_dfenc_h3(P, m);
+    return true;
+}
+}  // namespace
+
+// Every variable dfx_model_create reads, each with its own parse rule: "off only when 0", "on only when 1", a number.
+// First in creation: exact_fp32 steers the packing.
+static void read_switches(dfx_model *m) {
+    auto is = [](const char *name, char ch) {   // the variable's first character
+        const char *v = getenv(name);
+        return v && v[0] == ch;
+    };
+    auto at_least = [](const char *name, int least, int *out) {   // a number >= least, else *out stays
+        const char *v = getenv(name);
+        if (v && atoi(v) >= least) *out = atoi(v);
+    };
+    m->exact_fp32 = is("DFX_EXACT_FP32", '1');
+    m->concurrent = !is("DFX_STREAMS", '0');   // independent branches of the forward pass run on two auxiliary streams (0: everything serial)
+    m->gru_seq = !is("DFX_GRU_SEQ", '0') && !dfx_env_is_emulator();
+    if (getenv("DFX_GRU_PAIR")) m->sw.gru_pair = !is("DFX_GRU_PAIR", '0');
+    m->sw.gru_pair_far = is("DFX_GRU_PAIR_FAR", '1');
+    m->check_every_pass = is("DFX_CHECK_EVERY_PASS", '1');
+    at_least("DFX_SYNC_SPIN_LIMIT", 1, &m->spin_limit);
+    if (const char *v = getenv("DFX_CONVP_ELEMS"))          // test hook: the 32-bit-offset split of df_convp at small sizes
+        if (atoll(v) > 0) m->sw.convp_elems = atoll(v);
+    m->sw.erb_enc_split = is("DFX_ERB_ENC_SPLIT", '1');   // test hook: the three-launch form of the ERB encoder in batch passes
+    m->sw.c0_presplit = !is("DFX_C0_PRESPLIT", '0');      // test hook: the c0 kernels of batch passes split their feat_spec patches themselves
+#ifdef DFX_DEV
+    // dev A/Bs of the phase's side work (product builds have no such switches)
+    if (getenv("DFX_TAIL_SPLIT")) m->sw.tail_split = !is("DFX_TAIL_SPLIT", '0');
+    at_least("DFX_SEQ_P0_AHEAD", 1, &m->sw.p0_ahead);
+    at_least("DFX_SEQ_DFTAIL_EVERY", 1, &m->sw.dftail_every);
+    at_least("DFX_SEQ_TAIL_EVERY", 1, &m->sw.tail_every);
+    at_least("DFX_SEQ_CHUNKS", 1, &m->sw.chunks);
+    at_least("DFX_CONVP_LATE", 0, &m->sw.convp_late);
+#endif
+    m->sw.seq_trace = is("DFX_SEQ_TRACE", '1');
+    int tc = 0;
+    at_least("DFX_TCHUNKS", 1, &tc);
+    if (tc) m->tchunks = tc < DFX_MAX_TCHUNKS ? tc : DFX_MAX_TCHUNKS;
+    m->enqueue_ahead = is("DFX_ENQUEUE_AHEAD", '1');
+    m->sw.hwq_probe_mode = is("DFX_HWQ_PROBE", '0') ? '0' : is("DFX_HWQ_PROBE", 'f') ? 'f' : 0;   // "0": no handshake (trust the environment); "fail": dev / test hook
+}
+
+// dfx_model::can, from cfg, from what the packers made and from the arithmetic mode (the forms that rounds 2-5 could select by environment were
+// measured and lost; tools/dev/patches/ keeps the experiments).  The rules are written here and nowhere else.
+static void model_capabilities(dfx_model *m, const Prep::Packed &k) {
+    const dfx_model_cfg &c = m->cfg;
+    const int C = c.conv_ch, E = c.nb_erb, Fd = c.nb_df, NO = 2 * c.df_order, emb = C * E / 4;
+    const bool split = !m->exact_fp32;   // fp16-split matrix ops (default)
+    DfxCan &can = m->can;
+    can.fuse_c0 = c.df_pathway_kernel_size_t <= 5 && NO <= 16;
+    can.c0_batch_unfused = m->exact_fp32 && can.fuse_c0;
+    can.c0_h3 = can.fuse_c0 && split && k.c0;
+    can.c0_presplit = m->sw.c0_presplit && can.c0_h3;
+    can.pw_h3 = split && k.pw;
+    can.fan = k.fan && !c.enc_concat && emb == 64 * m->fan_chunks;   // (exact fp32 matrix ops: also with DFX_EXACT_FP32=1)
+    can.fan_skp = can.fan && c.df_gru_skip == DFX_SKIP_GROUPEDLINEAR && k.fan_skp;
+    can.enc_fan = k.encfan && !c.enc_concat && emb == 16 * m->efan_groups;
+    can.dfenc = can.c0_h3 && can.enc_fan && k.dfenc;
+    can.fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
+    can.fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
+    can.erb_tail = can.fuse_dec && can.pw_h3 && k.tail && dfx_tail_ok(C, E);
+    // (dfx_k_erb_enc4's strips assume what DeepFilterNet3's encoder is: erb_conv1..3 of kernel 1 x 3 over frequency, strides 2 / 2 / 1 — the only
+    // form prep_sep packs for these layers)
+    can.erb_enc4 = can.fuse_enc && can.pw_h3 && dfx_enc4_ok(C, E);
+    // df_out's fragments resident in registers when a wave's share fits: <= 16 groups of <= 4 tiles — every shipped shape
+    const bool resident = k.dfo_tiles == 4 && m->df_out.G <= 16 && (int64_t)(NO / 2) * 16 * (Fd / 2) <= (int64_t)DFX_DFO_NPT * DFX_DFO_THREADS;
+    can.df_out = !(split && k.dfo_tiles > 0) ? DFX_PLAN_DF_OUT_GGEMM : resident ? DFX_PLAN_DF_OUT_RESIDENT : DFX_PLAN_DF_OUT_STREAMING;
+}
+
+// Sync words, error words, events and the streams of lane 0.
+static int create_device_objects(dfx_model *m) {
+    if (m->sw.seq_trace) (void)hipMalloc(reinterpret_cast<void **>(&m->d_trace), (size_t)DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX * DFX_GS_MAX_CHUNKS * 3 * 8);
+    const size_t sync_bytes = DfxSyncLayout::total * sizeof(unsigned int);
+    const size_t psync_bytes = (size_t)DFX_MAX_GRU_LAYERS * (DFX_SEQ_GMAX / 2) * 48 * sizeof(unsigned int);
+    if (hipMalloc(reinterpret_cast<void **>(&m->d_psync), psync_bytes) != hipSuccess || hipMemset(m->d_psync, 0, psync_bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void **>(&m->d_sync), sync_bytes) != hipSuccess || hipMemset(m->d_sync, 0, sync_bytes) != hipSuccess ||
+        dfx_env_err_words_alloc(&m->h_err, &m->d_err, 256) != hipSuccess)
+        DFX_FAIL(DFX_ERR_ALLOC, "dfx_model_create: device allocation failed");
+    // Streams are created sparingly: ROCm multiplexes them onto GPU_MAX_HW_QUEUES hardware queues and two live streams
+    // that share a queue serialise each other.  Lane 0 gets exactly the streams its model needs; lanes 1.. (batch-chunk
+    // pipelining, off by default) are created on demand by dfx_model_set_pipeline.
+    bool good = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess;
+    good = good && hipEventCreateWithFlags(&m->ev_pass, hipEventDisableTiming) == hipSuccess;
+    good = good && hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming) == hipSuccess;
+    good = good && dfx_create_lane(m, 0);
+    for (int l = 1; l < m->max_chunks && good; ++l) good = dfx_create_lane(m, l);
+    if (!good) DFX_FAIL(DFX_ERR_HIP, "dfx_model_create: could not create the auxiliary streams/events");
+    return DFX_OK;
+}
+
+// create = check, switches, weights, upload, capabilities, device-side objects, handshake arming
 extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx_model **out) {
     if (int rc = check_cfg(cfg)) return rc;
     if (!blob || !out) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_create: null");
     if (int rc = dfx_require_device()) return rc;
-    const dfx_model_cfg &c = *cfg;
-    const DfxManifest man = dfx_build_manifest(c);
-    Prep P{blob, man, {}, {}};
-    {   // (read here as well as below: the weights that only the exact kernels read are packed for exact models alone)
-        const char *x = getenv("DFX_EXACT_FP32");
-        P.exact_fp32 = x && x[0] == '1';
-    }
     dfx_model *m = new dfx_model();
-    m->cfg = c;
-    const int C = c.conv_ch, O = c.df_order;
-    bool ok = true;
-    {   // enc.erb_conv0: pad(.0) conv(.1) bn(.2)
-        const float *w = P.get("enc.erb_conv0.1.weight");
-        std::vector<float> sc, sh;
-        ok = ok && w && P.bn("enc.erb_conv0.2", C, sc, sh);
-        if (ok) {
-            m->erb0_w = P.alloc(9 * C);
-            m->erb0_b = P.alloc(C);
-            for (int ch = 0; ch < C; ++ch) {
-                for (int k = 0; k < 9; ++k) P.out[m->erb0_w + k * C + ch] = w[ch * 9 + k] * sc[ch];
-                P.out[m->erb0_b + ch] = sh[ch];
-            }
-        }
-    }
-    ok = ok && prep_sep(P, "enc.erb_conv1", C, m->erb1) && prep_sep(P, "enc.erb_conv2", C, m->erb2) &&
-         prep_sep(P, "enc.erb_conv3", C, m->erb3) && prep_sep(P, "enc.df_conv1", C, m->dfc1);
-    if (ok) {   // enc.df_conv0: pad(.0) conv groups=2 (.1) pointwise(.2) bn(.3), folded into one dense conv (K = 18 -> 20)
-        const float *w = P.get("enc.df_conv0.1.weight"), *pw = P.get("enc.df_conv0.2.weight");
-        std::vector<float> sc, sh;
-        ok = w && pw && P.bn("enc.df_conv0.3", C, sc, sh);
-        if (ok) {
-            m->cin_weff = P.alloc((size_t)20 * C);
-            m->cin_b = P.alloc(C);
-            for (int n = 0; n < C; ++n) {
-                for (int tap = 0; tap < 9; ++tap)
-                    for (int ch = 0; ch < 2; ++ch) {
-                        double acc = 0.0;  // groups=2: output channel c of the 3x3 conv sees input ch = c / (C/2)
-                        for (int c = ch * (C / 2); c < (ch + 1) * (C / 2); ++c) acc += (double)pw[(size_t)n * C + c] * (double)w[c * 9 + tap];
-                        P.out[m->cin_weff + (size_t)(tap * 2 + ch) * C + n] = (float)(acc * (double)sc[n]);
-                    }
-                P.out[m->cin_b + n] = sh[n];
-            }
-        }
-    }
-    ok = ok && prep_glin(P, "enc.df_fc_emb.0.weight", m->fc_emb) && prep_glin(P, "enc.emb_gru.linear_in.0.weight", m->enc_in) &&
-         prep_gru(P, "enc.emb_gru.gru", 1, m->enc_gru) && prep_glin(P, "enc.emb_gru.linear_out.0.weight", m->enc_out);
-    if (ok && c.emb_gru_skip_enc == DFX_SKIP_GROUPEDLINEAR) ok = prep_glin(P, "enc.emb_gru.gru_skip.weight", m->enc_skip);
-    if (ok && c.emb_gru_skip == DFX_SKIP_GROUPEDLINEAR) ok = prep_glin(P, "erb_dec.emb_gru.gru_skip.weight", m->dec_skip);
-    if (ok) {
-        const float *w = P.get("enc.lsnr_fc.0.weight"), *b = P.get("enc.lsnr_fc.0.bias");
-        ok = w && b;
-        if (ok) {
-            const int emb = C * c.nb_erb / 4;
-            m->lsnr_w = P.alloc(emb);
-            memcpy(&P.out[m->lsnr_w], w, sizeof(float) * emb);
-            m->lsnr_b = b[0];
-        }
-    }
-    ok = ok && prep_glin(P, "erb_dec.emb_gru.linear_in.0.weight", m->dec_in) &&
-         prep_gru(P, "erb_dec.emb_gru.gru", c.emb_num_layers - 1, m->dec_gru) &&
-         prep_glin(P, "erb_dec.emb_gru.linear_out.0.weight", m->dec_out);
-    ok = ok && prep_sep(P, "erb_dec.convt3", C, m->ct3) && prep_path(P, "erb_dec.conv3p", C, m->ct3.sk_a, m->ct3.sk_b) &&
-         prep_sep(P, "erb_dec.convt2", C, m->ct2) && prep_path(P, "erb_dec.conv2p", C, m->ct2.sk_a, m->ct2.sk_b) &&
-         prep_sep(P, "erb_dec.convt1", C, m->ct1) && prep_path(P, "erb_dec.conv1p", C, m->ct1.sk_a, m->ct1.sk_b) &&
-         prep_path(P, "erb_dec.conv0p", C, m->co_ska, m->co_skb);
-    m->ct3.has_skip = m->ct2.has_skip = m->ct1.has_skip = true;
-    if (ok)
-        for (PwW *w : {&m->erb1, &m->erb2, &m->erb3, &m->ct3, &m->ct2, &m->ct1}) pack_pw_h3(P, C, *w);
-    if (ok) {   // erb_dec.conv0_out: conv [1,C,1,3] (.0) bn(1) (.1)
-        const float *w = P.get("erb_dec.conv0_out.0.weight");
-        std::vector<float> sc, sh;
-        ok = w && P.bn("erb_dec.conv0_out.1", 1, sc, sh);
-        if (ok) {
-            m->co_w = P.alloc(3 * C);
-            for (int ch = 0; ch < C; ++ch)
-                for (int j = 0; j < 3; ++j) P.out[m->co_w + j * C + ch] = w[ch * 3 + j] * sc[0];
-            m->co_bias = sh[0];
-        }
-    }
-    if (ok && C % 32 == 0) {   // matrix-op forms of the two small contractions inside dfx_k_erb_tail (round 5)
-        const int KC = C / 32;
-        const std::vector<float> src(P.out.begin(), P.out.end());   // pack_h3 may reallocate P.out
-        const size_t w0 = m->erb0_w, b0 = m->erb0_b, wo = m->co_w;
-        // erb_conv0 as [C x 32] fragments per 16 channels: k-slot 8 (l >> 4) + i = tap 3 kt + kf for k < 9, the bias (against a constant 1) at k = 9
-        m->tail_w0h3 = pack_h3(P, C / 16, [&](int nt, int l, int i) {
-            const int k = 8 * (l >> 4) + i, ch = 16 * nt + (l & 15);
-            return k < 9 ? src[w0 + (size_t)k * C + ch] : (k == 9 ? src[b0 + ch] : 0.f);
-        }, &m->tail_w0_unscale);
-        // conv0_out's three taps as the rows 0..2 of one 16-row tile; the contraction index is enumerated the way a D fragment leaves it (lane
-        // (position, q): element 8 kc + i <-> channel 16 ((8 kc + i) >> 2) + 4 q + ((8 kc + i) & 3))
-        m->tail_woh3 = pack_h3(P, KC, [&](int kc, int l, int i) {
-            const int j = l & 15, e = 8 * kc + i, ch = 16 * (e >> 2) + 4 * (l >> 4) + (e & 3);
-            return j < 3 ? src[wo + (size_t)j * C + ch] : 0.f;
-        }, &m->tail_wo_unscale);
-    }
-    if (ok) {   // df_dec.df_convp
-        const int kt = c.df_pathway_kernel_size_t, NO = 2 * O, G = dfx_gcd(C, NO), CG = C / G, OG = NO / G;
-        const int idx = kt > 1 ? 1 : 0;
-        const bool has_pw = kt > 1;  // separable only if groups > 1 and max(kernel) > 1; groups > 1 always holds (2 | C, 2O)
-        const float *w = P.get("df_dec.df_convp." + std::to_string(idx) + ".weight");
-        const float *pw = has_pw ? P.get("df_dec.df_convp." + std::to_string(idx + 1) + ".weight") : nullptr;
-        std::vector<float> sc, sh;
-        ok = w && (!has_pw || pw) && P.bn("df_dec.df_convp." + std::to_string(idx + (has_pw ? 2 : 1)), NO, sc, sh);
-        if (ok) {
-            m->cp_G = G;
-            m->cp_NO = NO;
-            m->cp_w1 = P.alloc((size_t)G * kt * CG * 16);
-            m->cp_w2 = P.alloc((size_t)NO * NO);
-            m->cp_b = P.alloc(NO);
-            for (int g = 0; g < G; ++g)
-                for (int k = 0; k < kt; ++k)
-                    for (int ci = 0; ci < CG; ++ci)
-                        for (int o = 0; o < OG; ++o) {
-                            // weight [NO, CG, kt, 1]
-                            float v = w[(((size_t)(g * OG + o) * CG + ci) * kt + k)];
-                            if (!has_pw) v *= sc[g * OG + o];
-                            P.out[m->cp_w1 + ((((size_t)g * kt + k) * CG + ci) * 16 + o)] = v;
-                        }
-            for (int n = 0; n < NO; ++n) {
-                for (int o = 0; o < NO; ++o) P.out[m->cp_w2 + (size_t)n * NO + o] = has_pw ? pw[(size_t)n * NO + o] * sc[n] : (n == o ? 1.f : 0.f);
-                P.out[m->cp_b + n] = sh[n];
-            }
-            // folded form: W_eff[k][c][n] = scale[n] * sum_o PW[n][o] * W1[o][c - group(o)*CG][k]   (PW = identity if absent).
-            // One 16-wide MFMA tile of outputs: 2 * df_order <= 16; longer filters (BASELINE.json configs[4]: df_order = 10) take the
-            // tiled kernel dfx_k_df_convp on a materialised c0.
-            const bool folded = NO <= 16;
-            m->cp_weff = P.alloc(folded ? (size_t)kt * C * 16 : 0);
-            m->cp_b16 = P.alloc(16);
-            for (int k = 0; folded && k < kt; ++k)
-                for (int ch = 0; ch < C; ++ch) {
-                    const int g = ch / CG, ci = ch - g * CG;
-                    for (int n = 0; n < NO; ++n) {
-                        double acc = 0.0;
-                        for (int o = g * OG; o < (g + 1) * OG; ++o) {
-                            const double p2 = has_pw ? (double)pw[(size_t)n * NO + o] : (n == o ? 1.0 : 0.0);
-                            acc += p2 * (double)w[((size_t)o * CG + ci) * kt + k];
-                        }
-                        P.out[m->cp_weff + ((size_t)k * C + ch) * 16 + n] = (float)(acc * (double)sc[n]);
-                    }
-                }
-            for (int n = 0; folded && n < NO; ++n) P.out[m->cp_b16 + n] = sh[n];
-            if (C % 32 == 0 && folded) {  // fragments of the fused fp16-split DF-encoder kernels (dfx_k_df_conv01_h3, dfx_k_df_convp_h3)
-                const int KC = C / 32;
-                // channel a lane (q = l>>4) feeds as element i of k-chunk kc after dfx_c0_tile
-                auto chan = [](int kc, int l, int i) { const int e = 8 * kc + i; return 16 * (e >> 2) + 4 * (l >> 4) + (e & 3); };
-                const size_t cin = m->cin_weff, wt1 = m->dfc1.wt, cpw = m->cp_weff;
-                // P.out may reallocate inside pack_h3 (alloc): read through offsets, never through cached pointers
-                std::vector<float> src(P.out.begin(), P.out.end());
-                m->c0_h3 = pack_h3(P, C / 16, [&](int nt, int l, int i) {
-                    const int k = 8 * (l >> 4) + i;
-                    return k < 18 ? src[cin + (size_t)k * C + 16 * nt + (l & 15)] : 0.f;
-                }, &m->c0_unscale);
-                m->dfc1_h3 = pack_h3(P, (C / 16) * KC, [&](int fr, int l, int i) {
-                    const int nt = fr / KC, kc = fr % KC;
-                    return src[wt1 + (size_t)chan(kc, l, i) * C + 16 * nt + (l & 15)];
-                }, &m->dfc1_unscale);
-                m->cp_h3 = pack_h3(P, kt * KC, [&](int fr, int l, int i) {
-                    const int k = fr / KC, kc = fr % KC;
-                    return src[cpw + ((size_t)k * C + chan(kc, l, i)) * 16 + (l & 15)];
-                }, &m->cp_unscale);
-            }
-        }
-    }
-    ok = ok && prep_glin(P, "df_dec.df_gru.linear_in.0.weight", m->dfg_in) && prep_gru(P, "df_dec.df_gru.gru", c.df_num_layers, m->df_gru);
-    if (ok && c.df_gru_skip == DFX_SKIP_GROUPEDLINEAR) ok = prep_glin(P, "df_dec.df_skip.weight", m->df_skip);
-    ok = ok && prep_glin(P, "df_dec.df_out.0.weight", m->df_out);
-    if (ok) pack_fan(P, m);
-    if (ok) pack_encfan(P, m);
-    if (ok) {   // fragments of dfx_k_df_out_h3
-        const GlinW a = m->df_out;
-        const int NO = 2 * O, Fd = c.nb_df;
-        if (a.Kg <= 32 && a.Kg % 8 == 0 && a.Ng % 2 == 0 && NO % 2 == 0 && Fd % 2 == 0 && (int64_t)a.G * a.Ng == (int64_t)NO * Fd &&
-            DFX_DFO_SMEM(NO, Fd) <= (size_t)64 * 1024) {
-            const std::vector<float> src(P.out.begin(), P.out.end());   // pack_h3 may reallocate P.out
-            const int NU = (a.Ng + 15) / 16;
-            m->dfo_h3 = pack_h3(P, a.G * NU, [&](int fr, int l, int i) {
-                const int g = fr / NU, u = fr % NU, o = 16 * u + (l & 15), k = 8 * (l >> 4) + i;
-                return o < a.Ng && k < a.Kg ? src[a.w + ((size_t)g * a.Kg + k) * a.Ng + o] : 0.f;
-            }, &m->dfo_unscale);
-            m->dfo_nu = NU;
-        }
-    }
-    if (ok && C % 32 == 0 && m->c0_h3 && m->dfc1_h3) {   // fragments of the fused DF branch of the encoder (dfx_k_df_enc_h3)
-        const GlinW a = m->fc_emb, b = m->enc_in;
-        const int Fout = c.nb_df / 2, KC = C / 32;
-        if (a.Kg % 32 == 0 && a.Ng == 16 && b.Kg == 32 && b.Ng == 16 && b.G * 2 == a.G && (int64_t)a.G * a.Kg == (int64_t)Fout * C) {
-            const std::vector<float> src(P.out.begin(), P.out.end());   // pack_h3 may reallocate P.out
-            // chunk ci = fo * KC + kc; lane (o = l & 15, q = l >> 4), element i <-> channel 16 ((8 kc + i) >> 2) + 4 q + (i & 3) of bin fo (the order
-            // in which dfx_k_df_conv01_h3's D fragments hold df_conv1's output)
-            m->dfenc_fc = pack_h3(P, Fout * KC, [&](int ci, int l, int i) {
-                const int fo = ci / KC, kc = ci % KC, ch = 16 * ((8 * kc + i) >> 2) + 4 * (l >> 4) + (i & 3);
-                const int idx = fo * C + ch, g = idx / a.Kg, kin = idx % a.Kg;
-                return src[a.w + ((size_t)g * a.Kg + kin) * 16 + (l & 15)];
-            }, &m->dfenc_fc_unscale);
-            // linear_in group j: element i <-> feature 16 (i >> 2) + 4 q + (i & 3) of its 32 inputs (two finished fc groups)
-            m->dfenc_in = pack_h3(P, b.G, [&](int j, int l, int i) {
-                return src[b.w + ((size_t)j * 32 + 16 * (i >> 2) + 4 * (l >> 4) + (i & 3)) * 16 + (l & 15)];
-            }, &m->dfenc_in_unscale);
-            m->dfenc_chunks = Fout * KC;
-        }
-    }
-    if (!ok) {
+    m->cfg = *cfg;
+    read_switches(m);
+    const DfxManifest man = dfx_build_manifest(m->cfg);
+    Prep P{blob, man};
+    P.exact_fp32 = m->exact_fp32;
+    if (!prepare_weights(P, m)) {
         delete m;
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_create: %s", P.err.empty() ? "weight preparation failed" : P.err.c_str());
     }
@@ -1206,94 +1325,21 @@ extern "C" int dfx_model_create(const dfx_model_cfg *cfg, const float *blob, dfx
         dfx_model_free(m);
         DFX_FAIL(DFX_ERR_HIP, "dfx_model_create: upload failed");
     }
-    {   // independent branches of the forward pass run on two auxiliary streams (DFX_STREAMS=0 keeps everything serial)
-        const char *e = getenv("DFX_STREAMS");
-        m->concurrent = !(e && e[0] == '0');
-        m->exact_fp32 = P.exact_fp32;   // DFX_EXACT_FP32=1
-        // (the forms that rounds 2-5 could select by environment were measured and lost; which kernel runs is decided by the model's shape and
-        // the arithmetic mode alone, and tools/dev/patches/ keeps the experiments)
-        m->fuse_c0 = m->cfg.df_pathway_kernel_size_t <= 5 && 2 * m->cfg.df_order <= 16;
-        // Exact mode, batch passes: c0 is written once and read by its two consumers instead of being recomputed by both — on fp32 matrix ops a c0
-        // tile is 20 ops of 32 cycles (3 of 16 on the fp16-split path), and the two recomputing kernels side by side are the exact front's 10 ms:
-        // 28.65 vs 29.45 ms per step (the frame-by-frame runtime always uses the recomputing forms)
-        m->c0_batch_unfused = m->exact_fp32 && m->fuse_c0;
-        const char *gq = getenv("DFX_GRU_SEQ");
-        {
-            const char *gp = getenv("DFX_GRU_PAIR");
-            if (gp) m->sw.gru_pair = gp[0] != '0';
-            const char *gf = getenv("DFX_GRU_PAIR_FAR");
-            m->sw.gru_pair_far = gf && gf[0] == '1';
-        }
-        m->gru_seq = !(gq && gq[0] == '0') && !dfx_env_is_emulator();
-        const char *cep = getenv("DFX_CHECK_EVERY_PASS"), *spl = getenv("DFX_SYNC_SPIN_LIMIT");
-        m->check_every_pass = cep && cep[0] == '1';
-        if (spl && atoi(spl) > 0) m->spin_limit = atoi(spl);
-        {
-            const char *cel = getenv("DFX_CONVP_ELEMS");   // test hook: the 32-bit-offset split of df_convp at small sizes
-            if (cel && atoll(cel) > 0) m->sw.convp_elems = atoll(cel);
-            const char *ees = getenv("DFX_ERB_ENC_SPLIT");   // test hook: the three-launch form of the ERB encoder in batch passes
-            m->sw.erb_enc_split = ees && ees[0] == '1';
-            const char *cps = getenv("DFX_C0_PRESPLIT");     // test hook: the c0 kernels of batch passes split their feat_spec patches themselves
-            m->sw.c0_presplit = !(cps && cps[0] == '0');
-        }
-#ifdef DFX_DEV
-        {   // dev A/Bs of the phase's side work (product builds have no such switches)
-            const char *v;
-            if ((v = getenv("DFX_TAIL_SPLIT"))) m->sw.tail_split = v[0] != '0';
-            if ((v = getenv("DFX_SEQ_P0_AHEAD")) && atoi(v) > 0) m->sw.p0_ahead = atoi(v);
-            if ((v = getenv("DFX_SEQ_DFTAIL_EVERY")) && atoi(v) > 0) m->sw.dftail_every = atoi(v);
-            if ((v = getenv("DFX_SEQ_TAIL_EVERY")) && atoi(v) > 0) m->sw.tail_every = atoi(v);
-            if ((v = getenv("DFX_SEQ_CHUNKS")) && atoi(v) > 0) m->sw.chunks = atoi(v);
-            if ((v = getenv("DFX_CONVP_LATE")) && atoi(v) >= 0) m->sw.convp_late = atoi(v);
-        }
-#endif
-        {
-            const char *tq = getenv("DFX_SEQ_TRACE");
-            if (tq && tq[0] == '1') (void)hipMalloc(reinterpret_cast<void **>(&m->d_trace), (size_t)DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX * DFX_GS_MAX_CHUNKS * 3 * 8);
-        }
-        // ready 0-7 | emb 8 | probe 13 | done 16- | producers' completion counters (DfxPublish): 9 words (16) | yprog, giprog: steps per (layer, group)
-        // | XCD registrations [3 kinds][layers][groups] (DfxXcd) | 64 words: [0] light hand-overs counted (dev aid), [8..48) the followers' claim counters
-        const size_t sync_bytes = (size_t)(16 + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX + 16 + 2 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX + 3 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX + 64) * sizeof(unsigned int);
-        const size_t psync_bytes = (size_t)DFX_MAX_GRU_LAYERS * (DFX_SEQ_GMAX / 2) * 48 * sizeof(unsigned int);
-        if (hipMalloc(reinterpret_cast<void **>(&m->d_psync), psync_bytes) != hipSuccess || hipMemset(m->d_psync, 0, psync_bytes) != hipSuccess ||
-            hipMalloc(reinterpret_cast<void **>(&m->d_sync), sync_bytes) != hipSuccess || hipMemset(m->d_sync, 0, sync_bytes) != hipSuccess ||
-            dfx_env_err_words_alloc(&m->h_err, &m->d_err, 256) != hipSuccess) {
-            dfx_model_free(m);
-            DFX_FAIL(DFX_ERR_ALLOC, "dfx_model_create: device allocation failed");
-        }
-        const char *tc = getenv("DFX_TCHUNKS");
-        if (tc && atoi(tc) >= 1) m->tchunks = atoi(tc) < DFX_MAX_TCHUNKS ? atoi(tc) : DFX_MAX_TCHUNKS;
-        {
-            // Streams are created sparingly: ROCm multiplexes them onto GPU_MAX_HW_QUEUES hardware queues and two live streams
-            // that share a queue serialise each other.  Lane 0 gets exactly the streams its model needs; lanes 1.. (batch-chunk
-            // pipelining, off by default) are created on demand by dfx_model_set_pipeline.
-            bool good = hipEventCreateWithFlags(&m->ev_fork, hipEventDisableTiming) == hipSuccess;
-            good = good && hipEventCreateWithFlags(&m->ev_pass, hipEventDisableTiming) == hipSuccess;
-            good = good && hipEventCreateWithFlags(&m->ev_gate, hipEventDisableTiming) == hipSuccess;
-            {
-                const char *ea = getenv("DFX_ENQUEUE_AHEAD");
-                m->enqueue_ahead = ea && ea[0] == '1';
-            }
-            good = good && dfx_create_lane(m, 0);
-            for (int l = 1; l < m->max_chunks && good; ++l) good = dfx_create_lane(m, l);
-            if (!good) {
-                dfx_model_free(m);
-                DFX_FAIL(DFX_ERR_HIP, "dfx_model_create: could not create the auxiliary streams/events");
-            }
-        }
-        // The persistent GRU phase synchronises through device flags and needs its streams to run concurrently: checked with a handshake
-        // (hwq_probe_run) — not here but before the first pass that would use the persistent form, or when DFX_Q_HWQ_PROBE /
-        // DFX_Q_GRU_PERSISTENT is asked for: a process that creates many handles it only streams through (df_create: one state per
-        // stream, never a persistent phase) pays nothing for it.
-        if (m->gru_seq && m->concurrent && !dfx_env_is_emulator()) {
-            const char *pe = getenv("DFX_HWQ_PROBE");   // "0": skip the probe (trust the environment); "fail": dev / test hook
-            if (pe && pe[0] == '0') {
-            } else if (pe && pe[0] == 'f') {
-                m->hwq_probe = 0;
-                hwq_probe_fallback(m);
-            } else {
-                m->hwq_probe_pending = true;
-            }
+    model_capabilities(m, P.packed);
+    if (int rc = create_device_objects(m)) {
+        dfx_model_free(m);
+        return rc;
+    }
+    // The persistent GRU phase synchronises through device flags and needs its streams to run concurrently: checked with a handshake
+    // (hwq_probe_run) — not here but before the first pass that would use the persistent form, or when DFX_Q_HWQ_PROBE /
+    // DFX_Q_GRU_PERSISTENT is asked for: a process that creates many handles it only streams through (df_create: one state per
+    // stream, never a persistent phase) pays nothing for it.  DFX_HWQ_PROBE=0: skip it (trust the environment); "fail": dev / test hook
+    if (m->gru_seq && m->concurrent && !dfx_env_is_emulator()) {
+        if (m->sw.hwq_probe_mode == 'f') {
+            m->hwq_probe = 0;
+            hwq_probe_fallback(m);
+        } else if (m->sw.hwq_probe_mode != '0') {
+            m->hwq_probe_pending = true;
         }
     }
     *out = m;
@@ -1310,8 +1356,7 @@ extern "C" void dfx_model_free(dfx_model *m) {
     dfx_env_err_words_free(m->h_err);
     if (m->d_sync && m->d_trace) {   // dev aid (DFX_SEQ_TRACE=1): how many block hand-overs of the followers took the same-XCD form
         unsigned int n = 0;
-        const size_t off = 16 + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX + 16 + 2 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX + 3 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
-        if (hipMemcpy(&n, m->d_sync + off, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "[dfx] same-XCD (light) block hand-overs over the model's life: %u\n", n);
+        if (hipMemcpy(&n, m->d_sync + DfxSyncLayout::xstat, sizeof(n), hipMemcpyDeviceToHost) == hipSuccess) fprintf(stderr, "[dfx] same-XCD (light) block hand-overs over the model's life: %u\n", n);
     }
     if (m->d_sync) (void)hipFree(m->d_sync);
     if (m->d_psync) (void)hipFree(m->d_psync);
@@ -1398,33 +1443,16 @@ extern "C" int dfx_model_cfg_get(const dfx_model *m, dfx_model_cfg *out) {
     return DFX_OK;
 }
 
-// Does a pass read the pre-split copy of feat_spec (Ws::fps)?  Batch passes on the fp16-split path whose shape takes the fused c0 kernels
-// (forward_impl: fuse_h3); never the streaming runtime.  One rule for forward_impl and for enhance(), which has the norm scan write the copy.
-static inline bool dfx_c0_presplit(const dfx_model *m, bool streaming) {
-    return !streaming && m->sw.c0_presplit && m->fuse_c0 && !m->c0_batch_unfused && !m->exact_fp32 && m->cfg.conv_ch % 32 == 0 && m->cp_h3;
-}
-
-// df_fc_emb + linear_in behind df_conv1 as the fan-out kernels (dfx_k_enc_fan, and inside dfx_k_df_enc_h3)?
-static inline bool dfx_enc_fan_ok(const dfx_model *m) {
-    const dfx_model_cfg &c = m->cfg;
-    return m->efan_groups > 0 && !c.enc_concat && (int64_t)c.conv_ch * c.nb_erb / 4 == 16 * (int64_t)m->efan_groups;
-}
-// Does the ERB encoder's head run frame-resident (dfx_k_erb_enc: a frame's zero-bordered feature rows within the kernel's 192 staging lanes, two
-// workgroups' rows within the LDS)?  One rule for DfxPass::plan() and for dfx_stream_create, whose passes have no other form of the head.
-static inline bool dfx_erb_enc_fused_ok(const dfx_model_cfg &c) {
-    const int C = c.conv_ch, E = c.nb_erb;
-    return E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
-}
-// Does the DF branch of the encoder run as the one kernel dfx_k_df_enc_h3 on the fp16-split path (forward_impl: `dfenc` = fuse_h3 && this)?
+// The pass-dependent half of "the DF branch of the encoder runs as the one kernel dfx_k_df_enc_h3" (DfxPass::plan(): dfenc = fuse_h3 && this).
 // feat_T: frames per clip of the feature arrays (0: T).  The limits are the kernel's 32-bit element offsets; beyond them the two kernels run.
 static inline bool dfx_dfenc_ok(const dfx_model *m, int64_t B, int64_t T, int64_t feat_T) {
     const dfx_model_cfg &c = m->cfg;
     const int64_t emb = (int64_t)c.conv_ch * c.nb_erb / 4;
-    return dfx_enc_fan_ok(m) && m->dfenc_chunks > 0 && B * T * emb < ((int64_t)1 << 31) && B * (feat_T > 0 ? feat_T : T) * c.nb_df < ((int64_t)1 << 29);
+    return m->can.dfenc && B * T * emb < ((int64_t)1 << 31) && B * (feat_T > 0 ? feat_T : T) * c.nb_df < ((int64_t)1 << 29);
 }
-// ... and is the copy ALL such a pass reads of feat_spec?  The front takes the fused DF encoder and df_convp its PS instance: enhance() then has
-// the norm scan store the copy INSTEAD of the fp32 values (the scan is bound by its stores).  forward_impl decides with the same two functions.
-static inline bool dfx_feat_spec_unread(const dfx_model *m, int64_t B, int64_t T) { return dfx_c0_presplit(m, false) && dfx_dfenc_ok(m, B, T, 0); }
+// Is the pre-split copy ALL a batch pass reads of feat_spec?  The front takes the fused DF encoder and df_convp its PS instance: enhance() then has
+// the norm scan store the copy INSTEAD of the fp32 values (the scan is bound by its stores).  DfxPass::plan() decides with the same two.
+static inline bool dfx_feat_spec_unread(const dfx_model *m, int64_t B, int64_t T) { return m->can.c0_presplit && dfx_dfenc_ok(m, B, T, 0); }
 // where model_forward_lane places the model's arrays inside the workspace it is given
 static inline float *dfx_ws_base(void *workspace) { return reinterpret_cast<float *>(((uintptr_t)workspace + 255) & ~(uintptr_t)255); }
 
@@ -1435,7 +1463,9 @@ struct Ws {
     size_t e0, e1, e2, e3, c0, c1, emb_in, emb, xa, xb, gi, xa2, xb2, gi2, demb, d3, d2, d1, mask, c0p, xdf, coefs, lsnr, skp_e, skp_d, fps, total;
     size_t pgi[DFX_MAX_GRU_LAYERS], py[DFX_MAX_GRU_LAYERS], ph[DFX_MAX_GRU_LAYERS];  // layer-pipelined GRU phase: gi, y, h state per layer
 };
-Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0, bool presplit = false) {   // presplit: dfx_c0_presplit (batch passes of the model)
+Ws plan_ws(const dfx_model *m, int64_t R, int64_t B) {
+    const dfx_model_cfg &c = m->cfg;
+    const bool c0_stored = !m->can.fuse_c0 || m->can.c0_batch_unfused, presplit = m->can.c0_presplit;
     Ws w{};
     size_t off = 0;
     auto take = [&](size_t n) {
@@ -1448,7 +1478,7 @@ Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0, bool 
     w.e1 = take(R * (E / 2) * C);
     w.e2 = take(R * (E / 4) * C);
     w.e3 = take(R * (E / 4) * C);
-    w.c0 = fuse_c0 ? 0 : take(R * Fd * C);  // only materialised by the unfused DF-encoder path
+    w.c0 = c0_stored ? take(R * Fd * C) : 0;  // only materialised by the unfused DF-encoder path
     w.c1 = take(R * (Fd / 2) * C);
     w.emb_in = take(R * emb * (c.enc_concat ? 2 : 1));
     w.emb = take(R * emb);
@@ -1484,7 +1514,7 @@ Ws plan_ws(const dfx_model_cfg &c, bool fuse_c0, int64_t R, int64_t B = 0, bool 
 
 extern "C" int dfx_model_workspace_bytes(const dfx_model *m, int64_t B, int64_t T, int64_t *bytes) {
     if (!m || !bytes || B < 0 || T < 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_workspace_bytes: bad arguments");
-    *bytes = (int64_t)(plan_ws(m->cfg, m->fuse_c0 && !m->c0_batch_unfused, B * T, B, dfx_c0_presplit(m, false)).total * sizeof(float)) + 256;
+    *bytes = (int64_t)(plan_ws(m, B * T, B).total * sizeof(float)) + 256;
     return DFX_OK;
 }
 

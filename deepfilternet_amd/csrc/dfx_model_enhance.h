@@ -101,10 +101,10 @@ static int enhance_chunk(const dfx_model *m, const dfx_state *st, const float *x
     float *fe = reinterpret_cast<float *>(base + w.feat_erb), *fs = reinterpret_cast<float *>(base + w.feat_spec);
     // F.pad(audio, (0, n_fft)) (enhance.py:230-233) is implicit: the analysis reads zeros past the T samples of a row
     const int64_t sstride = enh_spec_stride(st);
-    // the pre-split copy of feat_spec for the c0 kernels of the pass (dfx_c0_presplit) comes out of the norm scan, into its slot of the model workspace
+    // the pre-split copy of feat_spec for the c0 kernels of the pass (can.c0_presplit) comes out of the norm scan, into its slot of the model workspace
     int64_t mb = 0;
     dfx_model_workspace_bytes(m, B, Tf, &mb);
-    void *fps = dfx_c0_presplit(m, false) ? dfx_ws_base(base + w.model) + plan_ws(c, m->fuse_c0 && !m->c0_batch_unfused, B * Tf, B, true).fps : nullptr;
+    void *fps = m->can.c0_presplit ? dfx_ws_base(base + w.model) + plan_ws(m, B * Tf, B).fps : nullptr;
     const bool fs_unread = fps && Tf >= 16 && dfx_feat_spec_unread(m, B, Tf);   // (Tf < 16: the one-lane scan, the copy is made from its fp32 output)
     int rc = dfx_features_padded(st, x, B, Tp, T, x_stride, c.nb_df, c.norm_alpha, spec, fe, fs_unread ? nullptr : fs, (void *)s, sstride, pcm16, rows.len, fps,
                                  m->d_err);

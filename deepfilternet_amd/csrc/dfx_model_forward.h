@@ -76,7 +76,7 @@ struct DfxPass {
         Lk = sc ? 0 : c.conv_lookahead;
         t_zero = sc ? sc->t_zero : 0;
         tzr = sc ? sc->t_zero_rows : nullptr;   // per-stream t_zero (streams of the handle that started over at different hops)
-        w = plan_ws(c, m->fuse_c0 && !m->c0_batch_unfused, R, B, dfx_c0_presplit(m, false));
+        w = plan_ws(m, R, B);
         sstride = fin ? fin->spec_stride : 0;  // 0: dense rows of F bins
         fin_s = s;
         E = c.nb_erb, Fd = c.nb_df, O = c.df_order, NO = 2 * O, emb = C * E / 4, L = c.conv_lookahead;
@@ -93,8 +93,8 @@ struct DfxPass {
         // dfx_k_emb_fan: emb = enc_out_skip(y) and its consumers in one pass.  emb itself is only written when something outside the kernel
         // still reads it (the ERB decoder's skip connection, an identity skip around the DF GRU).  df_skip(emb) lands in xdf WITHOUT the
         // DF GRU's output (which does not exist yet): df_out then takes its operand as the sum y_df + xdf (DfxGgArgs::a2).
-        fan = m->fan_chunks > 0 && !c.enc_concat && emb == 64 * m->fan_chunks;   // (exact fp32 matrix ops: also with DFX_EXACT_FP32=1)
-        fan_skp = fan && run_df && c.df_gru_skip == DFX_SKIP_GROUPEDLINEAR && m->fan_kind[2] == 1;
+        fan = m->can.fan;
+        fan_skp = m->can.fan_skp && run_df;
         // Stream plan (s = caller's stream, x1/x2 = auxiliary; all joins are events, the host never blocks):
         //   s : e0..e3 ----------------(join c1)-- fc_emb, enc GRU, emb, lsnr --+-- ERB decoder: GRU stack, convt3..conv0_out --(join coefs)-- df_apply
         //   x1: c0 -+- c1 ------------------------------------------------------+-- DF decoder: GRU stack, skip, (join c0p) df_out -> coefs
@@ -103,29 +103,27 @@ struct DfxPass {
         x1 = par ? ln->aux[0] : s, x2 = par ? ln->aux[1] : s;
         // ---- Encoder, DF branch on x1 (deepfilternet3.py:176-179).  By default c0 = df_conv0(feat_spec) never exists in HBM: its two
         // consumers (df_conv1, df_convp) recompute the tiles they need from feat_spec on the matrix core.
-        c0_fused = m->fuse_c0 && !(m->c0_batch_unfused && !sc);   // this pass (m->fuse_c0: the model's shape allows it)
+        c0_fused = m->can.fuse_c0 && !(m->can.c0_batch_unfused && !sc);   // this pass (can.fuse_c0: the model's shape allows it)
         if (sc && !c0_fused) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
         cp_feat = c0_fused ? feat_spec : nullptr;
-        fuse_h3 = c0_fused && !m->exact_fp32 && C % 32 == 0 && m->cp_h3;  // fp16-split matrix ops (default)
+        fuse_h3 = c0_fused && m->can.c0_h3;  // fp16-split matrix ops (default)
         // batch passes on the fp16-split path: the two kernels that recompute c0 read the pre-split copy of feat_spec (PS instances; DFX_C0_PRESPLIT=0:
         // the unsplit ones — test hook).  enhance() has the norm scan write the copy; for a caller's own feat_spec (dfx_model_forward) front() makes it.
         // Streaming passes (feature windows, per-stream t_zero, dfx_k_df_convp_step), exact mode and other shapes keep the fp32 features.
-        fps = dfx_c0_presplit(m, sc != nullptr) ? reinterpret_cast<const uint2 *>(ws + w.fps) : nullptr;
+        fps = !sc && m->can.c0_presplit ? reinterpret_cast<const uint2 *>(ws + w.fps) : nullptr;
         // frame-resident ERB encoder head / decoder tail (dfx_k_erb_enc, dfx_k_erb_dec10 / dfx_k_erb_tail) where a frame fits the LDS; else layer by layer
-        fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
-        fuse_tail = fuse_dec && erb_tail_ok<C>(m, E);
-        fuse_enc = dfx_erb_enc_fused_ok(c);
+        fuse_dec = m->can.fuse_dec, fuse_tail = m->can.erb_tail, fuse_enc = m->can.fuse_enc;
         no_e0 = fuse_tail && fuse_enc;   // e0 never exists in HBM
         // batch passes on the fp16-split path: the four ERB convolutions as one launch (dfx_k_erb_enc4); streaming passes (frame ranges, gating,
         // row maps), exact mode and other shapes keep dfx_k_erb_enc + dfx_k_pwconv_f x 2 (DFX_ERB_ENC_SPLIT=1: batch passes too — test hook)
-        fuse_enc4 = fuse_enc && !sc && !m->sw.erb_enc_split && erb_enc4_ok<C>(m, E);
+        fuse_enc4 = m->can.erb_enc4 && !sc && !m->sw.erb_enc_split;
         e0r = no_e0 ? nullptr : e0;   // what the decoder tail is handed
         if (sc && !fuse_enc) DFX_FAIL(DFX_ERR_UNSUPPORTED, "streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
         gate = sc ? sc->gate : nullptr;
         if (gate && T - t_begin != 1) DFX_FAIL(DFX_ERR_INVALID_ARG, "gated streaming passes carry exactly one new frame");
         kt = c.df_pathway_kernel_size_t;
         convp_split = T;
-        enc_fan = dfx_enc_fan_ok(m);
+        enc_fan = m->can.enc_fan;
         // the DF branch of the encoder as one kernel behind the ERB convolutions (it adds e3), c1 never stored
         dfenc = fuse_h3 && dfx_dfenc_ok(m, B, T, featT);   // (32-bit element offsets inside the kernel; beyond: the two kernels)
         // ---- How the GRU phase will run — decided before the front, because its persistent form starts UNDER the front.
@@ -229,7 +227,7 @@ struct DfxPass {
     }
     // c = tanh(df_out(c)).view(b,t,F',2O) + c0p   (:329-330) of M rows; cfeat (+ cfeat2) is df_out's operand
     int df_out_rows(const float *cfeat, const float *cfeat2, int64_t M, hipStream_t st, DfxRowMap rm) {
-        if (m->dfo_nu > 0 && !m->exact_fp32 && M > 0 && R * (int64_t)NO * Fd < ((int64_t)1 << 31)) {   // row-streaming form (dfx_k_df_out_h3)
+        if (m->can.df_out != DFX_PLAN_DF_OUT_GGEMM && M > 0 && R * (int64_t)NO * Fd < ((int64_t)1 << 31)) {   // row-streaming form (dfx_k_df_out_h3)
             DfxDfOutArgs A;
             A.a = cfeat, A.a2 = cfeat2;
             A.wf = reinterpret_cast<const dfx_h8 *>(m->p(m->dfo_h3));
@@ -241,9 +239,8 @@ struct DfxPass {
             A.err = m->d_err;
             const size_t smem = DFX_DFO_SMEM(NO, Fd);
             DfxKScope ks(DFX_K_GGEMM, st);
-            // (weight fragments resident in registers when a wave's share fits: <= 16 groups of <= 4 tiles — every shipped shape)
-            const bool resident = m->dfo_nu == 4 && A.G <= 16 && (int64_t)(NO / 2) * 16 * (Fd / 2) <= (int64_t)DFX_DFO_NPT * DFX_DFO_THREADS;
-            note_df_out(resident ? DFX_PLAN_DF_OUT_RESIDENT : DFX_PLAN_DF_OUT_STREAMING);
+            const bool resident = m->can.df_out == DFX_PLAN_DF_OUT_RESIDENT;   // (weight fragments in registers)
+            note_df_out(m->can.df_out);
             if (resident) {
                 DFX_HIP(dfx_env_set_max_dyn_smem((const void *)dfx_k_df_out_h3r<4>, smem));
                 dfx_launch(dfx_k_df_out_h3r<4>, dim3((unsigned)nn_grid(dfx_ceil_div(M, 16), 2)), dim3(DFX_DFO_THREADS), smem, st, A);
@@ -617,17 +614,17 @@ struct DfxPass {
         int rc;
         const unsigned int base = m->seq_base;
         m->seq_base += (unsigned int)K + 1u;
-        unsigned int *ready = m->d_sync, *embf = m->d_sync + 8, *done = m->d_sync + 16;
-        unsigned int *pcnt = m->d_sync + 16 + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;   // one completion counter per producing stream (layer), [8] = emb
+        using SL = DfxSyncLayout;
+        unsigned int *ready = m->d_sync + SL::ready, *embf = m->d_sync + SL::emb, *done = m->d_sync + SL::done;
+        unsigned int *pcnt = m->d_sync + SL::pcnt;   // one completion counter per producing stream (layer), [8] = emb
         // Follower workgroups (dfx_k_proj_follow) feed the decoder layers in blocks of 16 steps instead of time chunks, all of them or none:
         // a follower of the encoder GRU, dfx_k_emb_follow, runs dfx_k_emb_fan's arithmetic per block of 8 steps and the stacks' first
         // layers' projection followers read what it wrote (since the same-XCD hand-over, measurements R5.12; rejected: followers for the
         // layers whose input is the output of the layer below only, for the first layers only, launches per chunk for all).
-        unsigned int *yprog = pcnt + 16, *giprog = yprog + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
+        unsigned int *yprog = m->d_sync + SL::yprog, *giprog = m->d_sync + SL::giprog;
         unsigned int *embprog = yprog + (size_t)(DFX_MAX_GRU_LAYERS - 1) * DFX_SEQ_GMAX;   // (the row of a layer that cannot exist: nl < 8 below)
         // same-XCD hand-overs (DfxXcd; rejected: every block hand-over with the agent-scope release / acquire)
-        unsigned int *xtab = giprog + DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
-        unsigned int *xstat = xtab + 3 * DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX;
+        unsigned int *xtab = m->d_sync + SL::xtab, *xstat = m->d_sync + SL::xstat;
         const unsigned int xtag = (m->seq_pbase & 0x0fffffffu) << 4;
         auto xword = [&](int kind, int layer) { return xtab + ((size_t)kind * DFX_MAX_GRU_LAYERS + layer) * DFX_SEQ_GMAX; };
         const unsigned int pbase = m->seq_pbase;
@@ -933,7 +930,7 @@ struct DfxPass {
         if (fin && dfx_synthesis_rows_ok(fin->st, true, O, run_df ? Fd : 0, E) && bands == fin->st->bands && sstride % 2 == 0 && sstride > 0) {
             m->last_plan |= DFX_PLAN_ROWS_FINISH;
             if ((rc = dfx_launch_synthesis_rows(fin->st, spec, sstride, run_df ? coefs : nullptr, run_df ? Fd : 0, O, c.df_lookahead, mask,
-                                                c.mask_pf ? c.pf_beta : 0.f, atten_lim, B, T, fin->y, fin->out_stride, fin->out_skip, fin->out_len, fin_s, fin->out_i16, m->d_err, m->d_sync ? m->d_sync + 14 : nullptr)))   // (d_sync[14]: a spare word of the flag block)
+                                                c.mask_pf ? c.pf_beta : 0.f, atten_lim, B, T, fin->y, fin->out_stride, fin->out_skip, fin->out_len, fin_s, fin->out_i16, m->d_err, m->d_sync ? m->d_sync + DfxSyncLayout::poison : nullptr)))
                 return rc;
         } else {
             if (dfx_dev_stage(10) && (rc = dfx_launch_df_apply(spec, coefs, DFX_COEF_BOTF, mask, bands, B, T, c.fft_size / 2 + 1, run_df ? Fd : 0, O, c.df_lookahead,

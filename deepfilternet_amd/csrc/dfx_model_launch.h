@@ -51,9 +51,9 @@ static int launch_pw(int mode, const dfx_model *m, const PwW &w, const float *x,
     if (dfx_pwf_ok(C, Fin, Fout)) {
         const size_t smem = dfx_pwf_smem(C, Fin, Fout);
         const int gridf = nn_grid(dfx_ceil_div(dfx_ceil_div(R, dfx_pwf_group(C, Fin, Fout)), 4), 2);
-        bool h3 = false;   // fp16-split pointwise contraction (default); without wt_h3 and in exact mode: the fp32 instances
+        bool h3 = false;   // fp16-split pointwise contraction (default); blocks without fragments and exact mode: the fp32 instances
         if constexpr (C % 32 == 0) {
-            if (!m->exact_fp32 && w.wt_h3) {
+            if (m->can.pw_h3 && w.has_h3) {
                 h3 = true;
                 A.wt_h3 = reinterpret_cast<const dfx_h8 *>(m->p(w.wt_h3));
                 A.unscale = w.unscale;
@@ -297,7 +297,7 @@ static int launch_erb_dec10(const dfx_model *m, const float *d2, const float *e1
         const size_t smemf = DFX_DEC10F_SMEM(C, E);
         bool h3 = false;
         if constexpr (C % 32 == 0) {
-            if (!m->exact_fp32 && m->ct1.wt_h3) {
+            if (m->can.pw_h3) {
                 h3 = true;
                 AA.wt_h3 = reinterpret_cast<const dfx_h8 *>(m->p(m->ct1.wt_h3));
                 AA.unscale = m->ct1.unscale;
@@ -320,11 +320,6 @@ static int launch_erb_dec10(const dfx_model *m, const float *d2, const float *e1
 }
 
 // erb_dec.convt3 -> convt2 -> convt1 -> conv0_out in one kernel (dfx_k_erb_tail): d3 / d2 / d1 never reach HBM
-template <int C>
-static bool erb_tail_ok(const dfx_model *m, int E) {
-    if constexpr (C % 32 != 0) return false;
-    return !m->exact_fp32 && m->ct3.wt_h3 && m->ct2.wt_h3 && m->ct1.wt_h3 && m->tail_w0h3 && m->tail_woh3 && dfx_tail_ok(C, E);
-}
 template <int C>
 // e0 == null: recomputed in the kernel from feat_erb (rows of T frames per clip, feat_T frames per clip in feat_erb, lookahead L)
 static int launch_erb_tail(const dfx_model *m, const float *demb, const float *e3, const float *e2, const float *e1, const float *e0,
@@ -395,7 +390,7 @@ static int launch_erb_enc(const dfx_model *m, const float *feat_erb, float *e0, 
     DfxKScope ks(DFX_K_ERB_ENC, s);
     const dim3 grid((unsigned)nn_grid(dfx_ceil_div(B * (t_end - t_begin), 4), 2));
     if constexpr (C % 32 == 0) {
-        if (!m->exact_fp32 && m->erb1.wt_h3) {   // erb_conv1's pointwise contraction on the fp16-split path
+        if (m->can.pw_h3) {   // erb_conv1's pointwise contraction on the fp16-split path
             A.wt_h3 = reinterpret_cast<const dfx_h8 *>(m->p(m->erb1.wt_h3));
             A.unscale = m->erb1.unscale;
             A.err = m->d_err;
@@ -412,14 +407,6 @@ static int launch_erb_enc(const dfx_model *m, const float *feat_erb, float *e0, 
 }
 
 // erb_conv0 -> erb_conv1 -> erb_conv2 -> erb_conv3 in one kernel (dfx_k_erb_enc4): e1 / e2 are written once and not read back by the encoder
-template <int C>
-static bool erb_enc4_ok(const dfx_model *m, int E) {
-    if constexpr (C % 32 != 0) return false;
-    const dfx_model_cfg &c = m->cfg;
-    // (the strips assume what DeepFilterNet3's encoder is: erb_conv1..3 of kernel 1 x 3 over frequency, strides 2 / 2 / 1 — the only form
-    // prep_sep packs for these layers — on E = nb_erb bins)
-    return !m->exact_fp32 && m->erb1.wt_h3 && m->erb2.wt_h3 && m->erb3.wt_h3 && E == c.nb_erb && dfx_enc4_ok(C, E);
-}
 template <int C>
 static int launch_erb_enc4(const dfx_model *m, const float *feat_erb, float *e0, float *e1, float *e2, float *e3, int64_t B, int64_t T,
                            hipStream_t s, int64_t t_begin = 0, int L = -1, int64_t t_end = -1, int64_t feat_T = 0) {

@@ -276,9 +276,9 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: conv_lookahead != df_lookahead is not supported by the streaming path");
     // (either arithmetic, DF stage on or off: an exact handle keeps its feature windows in ring form and a gated one its c0 window — the forms of
     // every model without fp16-split fragments — and its GRU layers step on dfx_k_gru_step_x32 / dfx_k_gru_rec_x32)
-    if (!m->fuse_c0)
+    if (!m->can.fuse_c0)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
-    if (!dfx_erb_enc_fused_ok(c))   // (what DfxPass::plan() would refuse on the first hop)
+    if (!m->can.fuse_enc)   // (what DfxPass::plan() would refuse on the first hop)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
     if (int rc = dfx_require_device()) return rc;
     dfx_stream_state *s = new dfx_stream_state();
@@ -544,7 +544,7 @@ static int stream_gate_alloc(dfx_stream_state *s, const char *who) {
         s->g_sh_h = take((size_t)s->layers * B * 256 * 4);
         {   // df_convp's state of a gated handle: pending sums (fp16-split models; 2 x what the ungated handle keeps) or the window of c0 frames
             const int kt = c.df_pathway_kernel_size_t;
-            s->g_pend2_ok = kt >= 2 && kt <= 5 && c.conv_ch % 32 == 0 && s->m->fuse_c0 && !s->m->exact_fp32 && s->m->cp_h3;
+            s->g_pend2_ok = kt >= 2 && s->m->can.c0_h3;
             if (s->g_pend2_ok) {
                 s->g_pend2 = take((size_t)B * stream_pend2_row_bytes(c));
                 s->g_par = take((size_t)B);
@@ -888,7 +888,7 @@ struct DfxStreamPass {
         // The feature windows of the encoder take the same form when the kernels that read them accept a clip stride (the fp16-split DF
         // encoder: DfxC01hArgs::feat_T): [B, feat_cap, E] and [B, feat_cap, Fd, 2] with the same slack as the spectra, so that all three
         // windows sit at lin_pos and go back to the front in the same call.  feat_owns: the linear form holds the feature history.
-        const bool feat_lin_ok = lin && capf > 0 && m->fuse_c0 && !m->exact_fp32 && c.conv_ch % 32 == 0 && m->cp_h3;
+        const bool feat_lin_ok = lin && capf > 0 && m->can.c0_h3;
         flin = feat_lin_ok && !bypass && skip == 0;   // (warm-up hops zero their features: the ring step does that)
         // (pass-through: the features do not advance, their history waits in the ring form)
         if (!flin) stream_to_ring(S, false, cp_spec, cp_fe, cp_fs);

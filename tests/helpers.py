@@ -56,7 +56,7 @@ SHAPES = {
     "l4_d3": _shape(emb_num_layers=4, df_num_layers=3),  # 1 + 3 + 3 = 7 layers: projection followers without the emb follower
     "l5_d3": _shape(emb_num_layers=5, df_num_layers=3),  # 1 + 4 + 3 = 8 layers = DFX_MAX_GRU_LAYERS: persistent phase without followers
     "l2_d1": _shape(emb_num_layers=2, df_num_layers=1),  # 3 layers
-    "lg8": _shape(lin_groups=8),                         # fan_kind fails: fan / fan_skp false (separate grouped linears); df_out streaming (8 tiles per group)
+    "lg8": _shape(lin_groups=8),                         # pack_fan refuses the nesting: fan / fan_skp false (separate grouped linears); df_out streaming (8 tiles per group)
     "lg4_elg16": _shape(lin_groups=4, enc_lin_groups=16),  # fan false, enc_fan / dfenc false (fc groups of 32 outputs); df_out ggemm (Kg = 64)
     "look31": _shape(conv_lookahead=3, df_lookahead=1),  # streaming refused (conv_lookahead != df_lookahead)
     "c32_e64": _shape("defaults", conv_ch=32, nb_erb=64),   # fuse_enc false at conv_ch 32
