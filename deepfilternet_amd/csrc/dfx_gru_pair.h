@@ -5,12 +5,18 @@
 // streamed from the L2 every step (432 KB per step and CU), and the step runs at the CU's L2 fill rate: 5.1 us alone, 7.3-8.2 under the side traffic
 // of the phase, against 1.9 us of matrix operations (docs/measurements.md R5.12, R6.2).  Here TWO workgroups of one XCD serve 32 clips together:
 // half p holds the rows of W_hh for the units [128 p, 128 p + 128) of all three gates — 48 fragment pairs per wave, 33 in registers and 15 in LDS,
-// nothing streamed —, computes those units for all 32 clips (two 16-column matrix-op tiles per fragment: 288 matrix operations per wave and step as
+// nothing streamed —, computes those units for all 32 clips (two 16-column matrix-op tiles: 288 matrix operations per wave and step as
 // before) and needs the partner's 128 x 32 new h values before the next step.  The exchange medium is y itself (each half stores its units of row t
 // anyway): store -> drain -> barrier -> step flag -> wait for the partner's step flag -> L1 invalidate -> load its half of row t, with R5.12's same-XCD
 // hand-over (no L2 write-back, no L2 invalidate) when both halves registered the same XCD and the agent-scope release / acquire pair otherwise
 // (blocks b and b + 8 of a launch sit on one XCD under the round-robin dispatch; placement = speed only).  CUs: a pair per 32 clips = the same 80
 // workgroups at 256 clips as one per 16.
+//
+// A step is two passes over the fragments, one per clip tile (docs/measurements.md, "The pair kernel's step in two passes"): the two tiles are independent,
+// so tile 0's gate math, y stores and f16 hi / lo conversion are issued between the matrix operations of tile 1 instead of behind the last of the 288;
+// the 15 LDS-resident pairs are read once per tile.  With one wave per SIMD that vector work is NOT free: pass B is longer than pass A by almost what
+// the work costs alone.  What the form buys (5.20 -> 4.89 us per step alone) are tighter passes (18.3 instead of 19.7 clocks per matrix op), gate math
+// of tile 1 that waits for no load, and tile 0's stores out of the way of the drain in front of barrier B.
 //
 // Bits: a lane's accumulators see the same products in the same order as in dfx_gru_h3_run (k-chunks ascending; lo*hi, hi*lo, hi*hi), the gate
 // math is the same code, the f16 hi / lo copies of h are made by the same conversion from the same fp32 values: y is bit-identical
@@ -31,6 +37,8 @@
 #ifndef DFX_GP_PIN
 #define DFX_GP_PIN 30                       /* of those, pinned in the accumulation half of the register file (256 registers = 32 pairs at most) */
 #endif
+#define DFX_GP_VALU_PER_MFMA 2              /* vector instructions asked for behind each matrix op of pass B; measured 1 / 2 / 3: 4.92 / 4.89 us per step and (an \
+                                               earlier form) 5.20 / 5.20 / 5.25 - flat, because an instruction issued between two matrix ops mostly delays the second */
 #ifndef DFX_GP_ABLATE
 #define DFX_GP_ABLATE 0   /* dev (tools/dev/gru_p2_bench.hip): 1 no partner wait / load, 2 no gate math, 4 no matrix ops, 8 no drain */
 #endif
@@ -264,103 +272,150 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
             for (int n = 0; n < 2; ++n)
 #pragma unroll
                 for (int i = 0; i < TILES; ++i) acc[n][i] = f32x4{0.f, 0.f, 0.f, 0.f};
-            dfx_h8 bh[2][2], bl[2][2];   // [k-chunk parity][clip tile]
-#pragma unroll
-            for (int n = 0; n < 2; ++n) {
-                bh[0][n] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n);
-                bl[0][n] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n + HB_LO);
-            }
-            dfx_h8 lhi[2][3], llo[2][3];   // LDS-resident fragments of the current / next group
-            dfx_static_for<0, 3>([&](auto ic) {
-                constexpr int i = decltype(ic)::value;
-                if constexpr (SC.cls[i] == 1) {
-                    lhi[0][i] = wl[((SC.idx[i] * NW + wave) * 2 + 0) * 64 + lane];
-                    llo[0][i] = wl[((SC.idx[i] * NW + wave) * 2 + 1) * 64 + lane];
-                }
-            });
-            // three fragments (three accumulator tiles of one k-chunk) x two clip tiles per group: 18 matrix ops, consecutive ones on different accumulators
-            dfx_static_for<0, NF / 3>([&](auto gc) {
-                constexpr int grp = decltype(gc)::value, f0 = 3 * grp;
-                constexpr int kc = DFX_GP_POS_KC(f0);
-                if constexpr (DFX_GP_POS_TILE(f0) == 0 && kc + 1 < 8) {   // next k-chunk of h, a chunk ahead
-                    constexpr int kn = kc + 1;
-#pragma unroll
-                    for (int n = 0; n < 2; ++n) {
-                        bh[kn & 1][n] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n + HB_KSTEP * kn);
-                        bl[kn & 1][n] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n + HB_LO + HB_KSTEP * kn);
+            // Two passes over the fragments, one per clip tile: tile 0's accumulators are complete after pass A, and its gate math, y stores and
+            // f16 hi / lo conversion are issued BETWEEN the matrix operations of pass B (pure vector work of the same wave while the matrix pipe
+            // works on tile 1; see the head of this file for what that buys), instead of behind the last of the 288.  Per accumulator nothing changes: k-chunks ascending, lo*hi, hi*lo, hi*hi.
+            dfx_h8 bh[2], bl[2];                   // h of the clip tile in flight, [k-chunk parity]
+            dfx_h8 lhi[2][TILES], llo[2][TILES];   // LDS-resident fragments of the current / next k-chunk
+            uint32_t c0hi[NS][2], c0lo[NS][2];     // tile 0's new h as packed f16 hi / lo (their LDS store stays behind barrier B)
+            float ga[NS][4], gb[NS][4];            // tile 0's gate math in flight (pass B)
+            // one group = the six accumulator tiles of one k-chunk of one clip tile; what group g needs from the LDS is requested in group g - 1
+            auto request = [&](auto gc) {
+                constexpr int g = decltype(gc)::value, n = g / 8, kc = g % 8;
+                bh[kc & 1] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n + HB_KSTEP * kc);
+                bl[kc & 1] = *reinterpret_cast<const dfx_h8 *>(hb + HB_N * n + HB_LO + HB_KSTEP * kc);
+                dfx_static_for<0, TILES>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value, f = kc * TILES + i;
+                    if constexpr (SC.cls[f] == 1) {
+                        lhi[kc & 1][i] = wl[((SC.idx[f] * NW + wave) * 2 + 0) * 64 + lane];
+                        llo[kc & 1][i] = wl[((SC.idx[f] * NW + wave) * 2 + 1) * 64 + lane];
                     }
+                });
+            };
+            // gate math of one value of clip tile n (dfx_gru_h3_run's gate_unit): what tile 1 runs behind pass B.  Tile 0 runs THE SAME EXPRESSIONS cut into
+            // slices inside pass B below (k-chunks 0-5): y is only bit-identical to the other forms while the two spell them alike — change both or neither
+            // (tests/test_gru_pair_step.py holds either tile against the one-CU and the launch forms)
+            auto gate = [&](int n, int s, int r) {
+                const float gr = r == 0 ? gv[n][0][s].x : r == 1 ? gv[n][0][s].y : r == 2 ? gv[n][0][s].z : gv[n][0][s].w;
+                const float gz = r == 0 ? gv[n][1][s].x : r == 1 ? gv[n][1][s].y : r == 2 ? gv[n][1][s].z : gv[n][1][s].w;
+                const float gn = r == 0 ? gv[n][2][s].x : r == 1 ? gv[n][2][s].y : r == 2 ? gv[n][2][s].z : gv[n][2][s].w;
+                const float bb = r == 0 ? bn[s].x : r == 1 ? bn[s].y : r == 2 ? bn[s].z : bn[s].w;
+                if (DFX_GP_ABLATE & 2) {
+                    hp[n][s][r] = 0.5f * hp[n][s][r] + 1e-3f * (gr + gz + gn + bb + acc[n][s][r] + acc[n][NS + s][r] + acc[n][2 * NS + s][r]);
+                    return;
                 }
-                // the LDS-resident fragments of the NEXT group are requested now (one group = 18 matrix ops ahead of their use)
-                if constexpr (grp + 1 < NF / 3) {
-                    dfx_static_for<0, 3>([&](auto ic) {
-                        constexpr int i = decltype(ic)::value, f = f0 + 3 + i;
-                        if constexpr (SC.cls[f] == 1) {
-                            lhi[(grp + 1) & 1][i] = wl[((SC.idx[f] * NW + wave) * 2 + 0) * 64 + lane];
-                            llo[(grp + 1) & 1][i] = wl[((SC.idx[f] * NW + wave) * 2 + 1) * 64 + lane];
-                        }
-                    });
-                }
-                dfx_h8 whi[3], wlo[3];
-                dfx_static_for<0, 3>([&](auto ic) {
-                    constexpr int i = decltype(ic)::value, f = f0 + i;
+                const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-(gr + acc[n][0 * NS + s][r] * A.unscale)));
+                const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-(gz + acc[n][1 * NS + s][r] * A.unscale)));
+                const float pre = gn + rg * (acc[n][2 * NS + s][r] * A.unscale + bb);
+                const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
+                hp[n][s][r] = (1.f - zg) * ng + zg * hp[n][s][r];
+            };
+            request(std::integral_constant<int, 0>{});
+            dfx_static_for<0, 16>([&](auto gc) {
+                constexpr int g = decltype(gc)::value, n = g / 8, kc = g % 8;
+                if constexpr (g + 1 < 16) request(std::integral_constant<int, g + 1>{});
+                dfx_h8 whi[TILES], wlo[TILES];
+                dfx_static_for<0, TILES>([&](auto ic) {
+                    constexpr int i = decltype(ic)::value, f = kc * TILES + i;
                     if constexpr (SC.cls[f] == 0) {
                         whi[i] = wr[SC.idx[f]][0];
                         wlo[i] = wr[SC.idx[f]][1];
                     } else {
-                        whi[i] = lhi[grp & 1][i];
-                        wlo[i] = llo[grp & 1][i];
+                        whi[i] = lhi[kc & 1][i];
+                        wlo[i] = llo[kc & 1][i];
                     }
                 });
-                constexpr int ta = DFX_GP_POS_TILE(f0), tb_ = DFX_GP_POS_TILE(f0 + 1), tc = DFX_GP_POS_TILE(f0 + 2);
                 if constexpr (DFX_GP_ABLATE & 4) {
-                    acc[0][ta][0] += (float)whi[0][0] + (float)wlo[1][1] + (float)whi[2][0] + (float)bh[kc & 1][0][0] + (float)bl[kc & 1][1][0];
-                    acc[1][tb_][0] += (float)wlo[0][0] + (float)whi[1][1] + (float)wlo[2][0] + (float)bh[kc & 1][1][0] + (float)bl[kc & 1][0][0];
+                    acc[n][kc % TILES][0] += (float)whi[0][0] + (float)wlo[1][1] + (float)whi[2][0] + (float)wlo[3][0] + (float)whi[4][1] + (float)wlo[5][0] +
+                                             (float)bh[kc & 1][0] + (float)bl[kc & 1][0];
                 } else {
+                    // 18 matrix ops; two on one accumulator are six apart
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    acc[n][ta] = dfx_mfma_16x16x32_f16(wlo[0], bh[kc & 1][n], acc[n][ta]);
-                    acc[n][tb_] = dfx_mfma_16x16x32_f16(wlo[1], bh[kc & 1][n], acc[n][tb_]);
-                    acc[n][tc] = dfx_mfma_16x16x32_f16(wlo[2], bh[kc & 1][n], acc[n][tc]);
-                }
+                    for (int i = 0; i < TILES; ++i) acc[n][i] = dfx_mfma_16x16x32_f16(wlo[i], bh[kc & 1], acc[n][i]);
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    acc[n][ta] = dfx_mfma_16x16x32_f16(whi[0], bl[kc & 1][n], acc[n][ta]);
-                    acc[n][tb_] = dfx_mfma_16x16x32_f16(whi[1], bl[kc & 1][n], acc[n][tb_]);
-                    acc[n][tc] = dfx_mfma_16x16x32_f16(whi[2], bl[kc & 1][n], acc[n][tc]);
-                }
+                    for (int i = 0; i < TILES; ++i) acc[n][i] = dfx_mfma_16x16x32_f16(whi[i], bl[kc & 1], acc[n][i]);
 #pragma unroll
-                for (int n = 0; n < 2; ++n) {
-                    acc[n][ta] = dfx_mfma_16x16x32_f16(whi[0], bh[kc & 1][n], acc[n][ta]);
-                    acc[n][tb_] = dfx_mfma_16x16x32_f16(whi[1], bh[kc & 1][n], acc[n][tb_]);
-                    acc[n][tc] = dfx_mfma_16x16x32_f16(whi[2], bh[kc & 1][n], acc[n][tc]);
+                    for (int i = 0; i < TILES; ++i) acc[n][i] = dfx_mfma_16x16x32_f16(whi[i], bh[kc & 1], acc[n][i]);
                 }
+                if constexpr (n == 1) {   // under tile 1's k-chunk kc: slice kc of tile 0's gate math (eight values per lane side by side, so that
+                                          // neighbouring vector instructions do not wait for each other), then its y row pieces and its f16 hi / lo copy
+                    // (the expressions of `gate` above, one slice per k-chunk: keep the two alike)
+                    auto comp = [](const float4 &v, int r) { return r == 0 ? v.x : r == 1 ? v.y : r == 2 ? v.z : v.w; };
+#pragma unroll
+                    for (int s = 0; s < NS; ++s)
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            if constexpr (DFX_GP_ABLATE & 2) {
+                                if constexpr (kc == 0)
+                                    hp[0][s][r] = 0.5f * hp[0][s][r] + 1e-3f * (comp(gv[0][0][s], r) + comp(gv[0][1][s], r) + comp(gv[0][2][s], r) + comp(bn[s], r) +
+                                                                                acc[0][s][r] + acc[0][NS + s][r] + acc[0][2 * NS + s][r]);
+                            } else if constexpr (kc == 0) {
+                                ga[s][r] = -(comp(gv[0][0][s], r) + acc[0][0 * NS + s][r] * A.unscale);
+                                gb[s][r] = -(comp(gv[0][1][s], r) + acc[0][1 * NS + s][r] * A.unscale);
+                            } else if constexpr (kc == 1) {
+                                ga[s][r] = dfx_fast_exp(ga[s][r]);
+                                gb[s][r] = dfx_fast_exp(gb[s][r]);
+                            } else if constexpr (kc == 2) {
+                                ga[s][r] = dfx_fast_rcp(1.f + ga[s][r]);   // r gate
+                                gb[s][r] = dfx_fast_rcp(1.f + gb[s][r]);   // z gate
+                            } else if constexpr (kc == 3) {
+                                const float pre = comp(gv[0][2][s], r) + ga[s][r] * (acc[0][2 * NS + s][r] * A.unscale + comp(bn[s], r));
+                                ga[s][r] = dfx_fast_exp(-2.f * pre);
+                            } else if constexpr (kc == 4) {
+                                ga[s][r] = 2.f * dfx_fast_rcp(1.f + ga[s][r]) - 1.f;   // n gate
+                            } else if constexpr (kc == 5) {
+                                hp[0][s][r] = (1.f - gb[s][r]) * ga[s][r] + gb[s][r] * hp[0][s][r];
+                            }
+                        }
+                    if constexpr (kc == 5) {
+                        // tile 0's row pieces leave here, so that the drain in front of barrier B only has tile 1's to wait for.  Loads and stores share
+                        // the wave's vector-memory counter and count in order: tile 1's gi rows (requested a step ago) are taken over first — a wait
+                        // for them behind these stores would be a wait for the stores' round trip (measured: +0.33 us per step)
+#pragma unroll
+                        for (int g = 0; g < 3; ++g)
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) {
+                                DFX_OPAQUE(gv[1][g][s].x);
+                                DFX_OPAQUE(gv[1][g][s].y);
+                                DFX_OPAQUE(gv[1][g][s].z);
+                                DFX_OPAQUE(gv[1][g][s].w);
+                            }
+                        if (valid[0]) {
+#pragma unroll
+                            for (int s = 0; s < NS; ++s) *reinterpret_cast<float4 *>(yp[0] + t * H + 16 * s) = make_float4(hp[0][s][0], hp[0][s][1], hp[0][s][2], hp[0][s][3]);
+                        }
+                    }
+                    if constexpr (kc >= 6) {
+                        constexpr int s = kc - 6;
+                        static_assert(NS == 2, "one sub-tile's conversion under each of the last two k-chunks");
+                        uint16_t hh[4], hl[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) {
+                            hh[r] = dfx_f32_to_f16_bits(hp[0][s][r]);
+                            hl[r] = dfx_f32_to_f16_bits(hp[0][s][r] - dfx_f16_bits_to_f32(hh[r]));
+                        }
+                        c0hi[s][0] = (uint32_t)hh[0] | ((uint32_t)hh[1] << 16), c0hi[s][1] = (uint32_t)hh[2] | ((uint32_t)hh[3] << 16);
+                        c0lo[s][0] = (uint32_t)hl[0] | ((uint32_t)hl[1] << 16), c0lo[s][1] = (uint32_t)hl[2] | ((uint32_t)hl[3] << 16);
+                    }
+                    if constexpr (!(DFX_GP_ABLATE & 4)) {   // the matrix pipe paces the pass: vector instructions in the shadow of each matrix op
+#pragma unroll
+                        for (int i = 0; i < 3 * TILES; ++i) {
+                            DFX_SCHED_GROUP(0x008, 1);
+                            DFX_SCHED_GROUP(0x002, DFX_GP_VALU_PER_MFMA);
+                        }
+                    }
                 }
                 DFX_SCHED_BARRIER();
+                if constexpr (g == 7) DFX_GP_TICK(8);   // pass A: the matrix ops of clip tile 0 issued
             });
-            DFX_GP_TICK(0);   // matrix ops issued
-            // ---- gates, new state (dfx_gru_h3_run's gate_unit), y
+            DFX_GP_TICK(0);   // pass B: the matrix ops of clip tile 1 issued, tile 0's gates / y stores / conversion among them
+            // ---- gates, new state and y of clip tile 1
 #pragma unroll
-            for (int n = 0; n < 2; ++n)
+            for (int s = 0; s < NS; ++s) {
 #pragma unroll
-                for (int s = 0; s < NS; ++s) {
-#pragma unroll
-                    for (int r = 0; r < 4; ++r) {
-                        const float gr = r == 0 ? gv[n][0][s].x : r == 1 ? gv[n][0][s].y : r == 2 ? gv[n][0][s].z : gv[n][0][s].w;
-                        const float gz = r == 0 ? gv[n][1][s].x : r == 1 ? gv[n][1][s].y : r == 2 ? gv[n][1][s].z : gv[n][1][s].w;
-                        const float gn = r == 0 ? gv[n][2][s].x : r == 1 ? gv[n][2][s].y : r == 2 ? gv[n][2][s].z : gv[n][2][s].w;
-                        const float bb = r == 0 ? bn[s].x : r == 1 ? bn[s].y : r == 2 ? bn[s].z : bn[s].w;
-                        if (DFX_GP_ABLATE & 2) {
-                            hp[n][s][r] = 0.5f * hp[n][s][r] + 1e-3f * (gr + gz + gn + bb + acc[n][s][r] + acc[n][NS + s][r] + acc[n][2 * NS + s][r]);
-                            continue;
-                        }
-                        const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-(gr + acc[n][0 * NS + s][r] * A.unscale)));
-                        const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-(gz + acc[n][1 * NS + s][r] * A.unscale)));
-                        const float pre = gn + rg * (acc[n][2 * NS + s][r] * A.unscale + bb);
-                        const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
-                        hp[n][s][r] = (1.f - zg) * ng + zg * hp[n][s][r];
-                    }
-                    if (valid[n]) *reinterpret_cast<float4 *>(yp[n] + t * H + 16 * s) = make_float4(hp[n][s][0], hp[n][s][1], hp[n][s][2], hp[n][s][3]);
-                }
+                for (int r = 0; r < 4; ++r) gate(1, s, r);
+                if (valid[1]) *reinterpret_cast<float4 *>(yp[1] + t * H + 16 * s) = make_float4(hp[1][s][0], hp[1][s][1], hp[1][s][2], hp[1][s][3]);
+            }
             // ---- the exchange: my units of row t are in the L2 (or released), everybody has read h(t) from the LDS
             DFX_GP_TICK(1);   // gates, y stores issued
             if (!(DFX_GP_ABLATE & 8)) DFX_VMEM_DRAIN();   // (s_barrier does not wait for the other waves' stores: each wave drains its own in front of it)
@@ -374,9 +429,11 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
                 else __hip_atomic_store(fmine, now, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
             }
 #pragma unroll
-            for (int n = 0; n < 2; ++n)
-#pragma unroll
-                for (int s = 0; s < NS; ++s) put4(16 * n + jl, ubase + 16 * s + 4 * q, hp[n][s][0], hp[n][s][1], hp[n][s][2], hp[n][s][3]);
+            for (int s = 0; s < NS; ++s) {
+                *reinterpret_cast<uint2 *>(h16 + ((size_t)0 * ROWS + jl) * HROW + ubase + 16 * s + 4 * q) = make_uint2(c0hi[s][0], c0hi[s][1]);
+                *reinterpret_cast<uint2 *>(h16 + ((size_t)1 * ROWS + jl) * HROW + ubase + 16 * s + 4 * q) = make_uint2(c0lo[s][0], c0lo[s][1]);
+                put4(16 + jl, ubase + 16 * s + 4 * q, hp[1][s][0], hp[1][s][1], hp[1][s][2], hp[1][s][3]);
+            }
             if (tid == 0) {
                 int spins = 0;
                 while (!(DFX_GP_ABLATE & 1) && !dead && (int)(__hip_atomic_load(ftheirs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - now) < 0) {

@@ -537,6 +537,7 @@ struct dfx_model {
     unsigned int *d_psync = nullptr;    // pair form of the persistent GRU phase: [DFX_MAX_GRU_LAYERS * DFX_SEQ_GMAX / 2][48] words
     mutable unsigned int seq_pbase = 0;       // step counter base of the follower hand-overs (yprog / giprog), monotonic like seq_base
     mutable int64_t passes_ps = 0;   // batch passes whose c0 kernels read the pre-split copy of feat_spec (DFX_Q_PASSES_C0_PRESPLIT)
+    mutable int64_t passes_pair = 0; // passes whose persistent GRU phase ran on pairs of CUs (DFX_Q_PASSES_PAIR)
     mutable int64_t last_plan = 0;   // DFX_PLAN_* bits of the last pass (DFX_Q_LAST_PLAN): written by DfxPass::plan() / df_out_rows() / finish()
     mutable int64_t passes_seq = 0, passes_ev = 0;   // passes that ran the persistent phase / that gave it up because another process held the device's ticket (DFX_Q_TICKET_*)
     mutable unsigned int seq_base = 0;  // flag value of "nothing of the current forward pass yet"
@@ -1425,6 +1426,7 @@ extern "C" int dfx_model_query(const dfx_model *m, int what, int64_t *value) {
         case DFX_Q_SPIN_LIMIT: *value = m->spin_limit; return DFX_OK;
         case DFX_Q_PASSES_C0_PRESPLIT: *value = m->passes_ps; return DFX_OK;
         case DFX_Q_LAST_PLAN: *value = m->last_plan; return DFX_OK;
+        case DFX_Q_PASSES_PAIR: *value = m->passes_pair; return DFX_OK;
     }
     DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_query: unknown item %d", what);
 }

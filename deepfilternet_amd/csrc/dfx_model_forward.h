@@ -643,6 +643,7 @@ struct DfxPass {
         }
         // the recurrences on pairs of CUs (dfx_gru_pair.h): 32 clips per pair, W_hh resident; fp16-split arithmetic only (the exact form's fragments are the same bytes, its matrix ops are not)
         const bool use_pair = m->sw.gru_pair && !m->exact_fp32 && groups >= 2 && m->d_psync;
+        m->passes_pair += use_pair ? 1 : 0;
         if (nfollow || use_pair) m->seq_pbase += (unsigned int)T + 1u;
         // a layer's input projection of chunk k, and ready[l] = chunk k + 1 behind it (proj_chunk)
         auto proj_pub = [&](const GruW &g, int l, int k, const float *xin, hipStream_t st) -> int {

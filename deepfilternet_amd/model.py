@@ -139,6 +139,7 @@ class DfNet:
     Q_GRU_PERSISTENT, Q_HWQ_PROBE, Q_EXACT_FP32, Q_SPIN_LIMIT, Q_PASSES_PERSISTENT, Q_PASSES_TICKET_BUSY = 1, 2, 3, 4, 5, 6
     Q_PASSES_C0_PRESPLIT = 7
     Q_LAST_PLAN = 8
+    Q_PASSES_PAIR = 9   # passes whose persistent GRU phase ran its recurrences on pairs of CUs
     # bits of query(Q_LAST_PLAN) (include/dfx.h DFX_PLAN_*): what the last pass decided; PLAN_DF_OUT is a two-bit field
     PLAN_BITS = {"fan": 1 << 0, "fan_skp": 1 << 1, "fuse_h3": 1 << 2, "presplit": 1 << 3, "fuse_tail": 1 << 4, "fuse_enc": 1 << 5,
                  "fuse_enc4": 1 << 6, "enc_fan": 1 << 7, "dfenc": 1 << 8, "c0_fused": 1 << 9, "pipe": 1 << 10, "use_seq": 1 << 11,

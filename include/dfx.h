@@ -229,6 +229,7 @@ int dfx_model_check(const dfx_model *m);
 #define DFX_Q_PASSES_TICKET_BUSY 6  /* big passes that took the event-synchronised form because another PROCESS held the device's ticket for its own
                                        persistent phase (/dev/shm/dfx_persistent_<PCI bus id>.lock, DFX_DEVICE_TICKET=0: no ticket) */
 #define DFX_Q_PASSES_C0_PRESPLIT 7  /* batch passes whose fused DF-encoder kernels read the pre-split copy of feat_spec (default; DFX_C0_PRESPLIT=0: none) */
+#define DFX_Q_PASSES_PAIR 9          /* passes whose persistent GRU phase ran its recurrences on pairs of CUs (dfx_k_gru_seq_p2; DFX_GRU_PAIR=0, one 16-clip group, exact fp32: none) */
 #define DFX_Q_LAST_PLAN 8           /* what the last pass of this handle (batch or streaming) decided: a mask of DFX_PLAN_* bits, 0 before the first pass */
 /* DFX_Q_LAST_PLAN: which fused kernels the pass ran and which form its GRU phase took (decided by the model's shape, the arithmetic mode and the
  * size of the pass; the names are those of DfxPass::plan() in csrc/dfx_model_forward.h).  Diagnostic: the tests use it to see that their shapes
