@@ -7,8 +7,8 @@
 // half p holds the rows of W_hh for the units [128 p, 128 p + 128) of all three gates — 48 fragment pairs per wave, 33 in registers and 15 in LDS,
 // nothing streamed —, computes those units for all 32 clips (two 16-column matrix-op tiles: 288 matrix operations per wave and step as
 // before) and needs the partner's 128 x 32 new h values before the next step.  The exchange medium is y itself (each half stores its units of row t
-// anyway): store -> drain -> barrier -> step flag -> wait for the partner's step flag -> L1 invalidate -> load its half of row t, with R5.12's same-XCD
-// hand-over (no L2 write-back, no L2 invalidate) when both halves registered the same XCD and the agent-scope release / acquire pair otherwise
+// anyway): store -> drain -> barrier -> step flag -> wait for the partner's step flag -> L1 invalidate -> load its half of row t: the light hand-over
+// of dfx_gru_sync.h (where the protocol of all the phase's flags is written down) when both halves registered the same XCD, the full one otherwise
 // (blocks b and b + 8 of a launch sit on one XCD under the round-robin dispatch; placement = speed only).  CUs: a pair per 32 clips = the same 80
 // workgroups at 256 clips as one per 16.
 //
@@ -80,7 +80,7 @@ static constexpr DfxGpSched dfx_gp_make_sched() {   // the LDS-resident pairs sp
     return sc;
 }
 
-// Synchronisation of one half of a pair.  Step counters are pbase + steps, monotonic over the life of the model like DfxGhSync's.
+// The flag words of one half of a pair (the protocol: dfx_gru_sync.h).  Step counters are pbase + steps.
 struct DfxGpSync {
     unsigned int *pflag = nullptr;        // [2 halves] 16 words apart: steps whose y rows this half has stored (and drained / released)
     unsigned int *pxcd = nullptr;         // [2 halves]: tag | (xcd + 1)
@@ -167,22 +167,13 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
     // ---- the pair finds out whether it shares an L2
     unsigned int *const fmine = Y.pflag + 16 * half;
     const unsigned int *const ftheirs = Y.pflag + 16 * (half ^ 1);
-    bool dead = false;   // (thread 0) a wait of this workgroup has timed out: err[2] is raised, no further wait holds the device
+    DfxWaiter W{Y.spin_limit, Y.err};   // (thread 0)
     if (tid == 0) {
-        const unsigned int me = Y.tag | (unsigned int)(dfx_xcc_id() + 1);
+        const unsigned int me = dfx_sync_my_word(Y.tag);
         __hip_atomic_store(Y.pxcd + half, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         if (Y.xme) __hip_atomic_store(Y.xme, me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        unsigned int v;
-        int spins = 0;
-        while ((((v = __hip_atomic_load(Y.pxcd + (half ^ 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & ~15u) != Y.tag) || (v & 15u) == 0u) {
-            if (++spins > Y.spin_limit) {
-                dfx_raise(Y.err + 2);
-                dead = true;
-                break;
-            }
-            __builtin_amdgcn_s_sleep(2);
-        }
-        sflag[0] = (!dead && v == me && !Y.far) ? 1 : 0;
+        const unsigned int v = W.wait_registered<2>(Y.pxcd + (half ^ 1), Y.tag);
+        sflag[0] = (!W.dead && v == me && !Y.far) ? 1 : 0;
         sflag[1] = 0;
         if (Y.stat && half == 0 && v != me) __hip_atomic_fetch_add(Y.stat + 1, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
@@ -224,16 +215,8 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             if (!Y.giprog[i]) continue;
-            int spins = 0;
-            while (!dead && (int)(__hip_atomic_load(Y.giprog[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > Y.spin_limit) {
-                    dfx_raise(Y.err + 2);
-                    dead = true;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(1);
-            }
-            same = same && Y.xprod[i] && __hip_atomic_load(Y.xprod[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (Y.tag | (unsigned int)(dfx_xcc_id() + 1));
+            W.wait_ge<1>(Y.giprog[i], want);
+            same = same && Y.xprod[i] && dfx_sync_is_mine(Y.xprod[i], Y.tag);
         }
         sflag[1] = same && !Y.far ? 1 : 0;
     };
@@ -246,21 +229,10 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
         const int64_t c0 = SEQ ? (int64_t)Y.tb[ck] : A.t0, c1 = SEQ ? (int64_t)Y.tb[ck + 1] : A.t1;
         if (SEQ) {   // the input projection of this chunk must exist
             if (tid == 0 && Y.trace) Y.trace[ck * 3 + 0] = wall_clock64();
-            if (tid == 0 && !Y.giprog[0] && Y.ready) {
-                const unsigned int want = Y.base + (unsigned int)ck + 1u;
-                int spins = 0;
-                while (!dead && (int)(__hip_atomic_load(Y.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                    if (++spins > Y.spin_limit) {
-                        dfx_raise(Y.err + 2);
-                        dead = true;
-                        break;
-                    }
-                    __builtin_amdgcn_s_sleep(8);
-                }
-            }
+            if (tid == 0 && !Y.giprog[0] && Y.ready) W.wait_ge<8>(Y.ready, Y.base + (unsigned int)ck + 1u);
             if (tid == 0 && Y.giprog[0] && ck == 0) poll_gi(Y.sblk);
             __syncthreads();
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            dfx_sync_acquire(false);
             if (tid == 0 && Y.trace) Y.trace[ck * 3 + 1] = wall_clock64();
         }
         if (c1 > c0) load_gi(c0);
@@ -424,10 +396,7 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
             DFX_GP_TICK(3);   // barrier B
             const bool gi_step = SEQ && Y.giprog[0] && ((t + 1) & (Y.sblk - 1)) == 0 && t + 1 < A.T;   // the next step requests the first row of the next block
             const unsigned int now = Y.pbase + (unsigned int)(t + 1);
-            if (tid == 0) {
-                if (light) __hip_atomic_store(fmine, now, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else __hip_atomic_store(fmine, now, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-            }
+            if (tid == 0) dfx_sync_raise(fmine, now, light);
 #pragma unroll
             for (int s = 0; s < NS; ++s) {
                 *reinterpret_cast<uint2 *>(h16 + ((size_t)0 * ROWS + jl) * HROW + ubase + 16 * s + 4 * q) = make_uint2(c0hi[s][0], c0hi[s][1]);
@@ -435,21 +404,13 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
                 put4(16 + jl, ubase + 16 * s + 4 * q, hp[1][s][0], hp[1][s][1], hp[1][s][2], hp[1][s][3]);
             }
             if (tid == 0) {
-                int spins = 0;
-                while (!(DFX_GP_ABLATE & 1) && !dead && (int)(__hip_atomic_load(ftheirs, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - now) < 0) {
-                    if (++spins > Y.spin_limit) {
-                        dfx_raise(Y.err + 2);
-                        dead = true;
-                        break;
-                    }
-                }
+                if (!(DFX_GP_ABLATE & 1)) W.wait_ge<0>(ftheirs, now);   // (no sleep: the partner is a step's length away at most)
                 if (gi_step) poll_gi(t + 1 + Y.sblk);
             }
             DFX_GP_TICK(4);   // own half in LDS, partner's flag seen
             __syncthreads();
             DFX_GP_TICK(5);   // barrier C
-            if (light && !(gi_step && sflag[1] == 0)) DFX_L1_INV();
-            else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+            dfx_sync_acquire(light && !(gi_step && sflag[1] == 0));
             // the partner's half first, the next step's gi behind it (vector loads return in order: the gi rows may come from HBM)
             const bool more = t + 1 < A.T && !(DFX_GP_ABLATE & 1);
             float4 o[4];
@@ -467,9 +428,7 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
             }
             DFX_GP_TICK(6);   // partner's half loaded and in LDS
             if (SEQ && tid == 0 && Y.yprog && (((t + 1) & (Y.yblk - 1)) == 0 || t + 1 == A.T)) {   // a block of group 2 pg + p's rows is complete (both halves' units)
-                const bool cons_same = !Y.far && Y.xcons && __hip_atomic_load(Y.xcons, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (Y.tag | (unsigned int)(dfx_xcc_id() + 1));
-                if (cons_same) __hip_atomic_store(Y.yprog, Y.pbase + (unsigned int)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                else __hip_atomic_store(Y.yprog, Y.pbase + (unsigned int)(t + 1), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+                dfx_sync_raise(Y.yprog, Y.pbase + (unsigned int)(t + 1), !Y.far && Y.xcons && dfx_sync_is_mine(Y.xcons, Y.tag));
             }
             __syncthreads();
             DFX_GP_TICK(7);   // barrier D
@@ -477,7 +436,7 @@ static __device__ __forceinline__ void dfx_gru_p2_run(const DfxGhArgs &A, int64_
         if (SEQ) {   // the pair's rows of chunk ck are complete (the last step's exchange): make them visible device-wide, then say so
             __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
             __syncthreads();
-            if (tid == 0 && Y.done) __hip_atomic_store(Y.done, Y.base + (unsigned int)ck + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            if (tid == 0 && Y.done) dfx_sync_raise(Y.done, Y.base + (unsigned int)ck + 1u, false);
             if (tid == 0 && Y.trace) Y.trace[ck * 3 + 2] = wall_clock64();
         }
     }

@@ -3302,98 +3302,7 @@ __global__ void __launch_bounds__(DFX_PJ_THREADS, 2) dfx_k_proj256(DfxPjArgs A) 
 #define DFX_PH_NC 64
 #define DFX_PH_CHUNK_H8 (8 * 4 * 2 * 64)                 /* dfx_h8 per column chunk: [kc][ct][hi,lo][lane] */
 #define DFX_PH_SMEM ((size_t)2 * DFX_PH_CHUNK_H8 * 16)
-// Same-XCD hand-overs of the persistent GRU phase's followers (round 5, see DfxGhSync::x).
-struct DfxXcd {
-    unsigned int *me = nullptr;            // this party's registration word: tag | (xcd + 1)
-    const unsigned int *prod = nullptr;    // the registration word of the party whose output this one consumes, or null
-    const unsigned int *cons = nullptr;    // ... of the party that consumes this one's output, or null
-    const unsigned int *cons2 = nullptr;   // a second consumer (the emb follower feeds two projection followers), or null
-    unsigned int tag = 0;                  // of this pass (low four bits zero)
-    unsigned int *stat = nullptr;          // dev aid: counts light releases
-};
-static __device__ __forceinline__ void dfx_xcd_register(const DfxXcd &X) {
-    if (X.me && threadIdx.x == 0) __hip_atomic_store(X.me, X.tag | (unsigned int)(dfx_xcc_id() + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-static __device__ __forceinline__ bool dfx_xcd_same(const DfxXcd &X, const unsigned int *other) {
-    return other && __hip_atomic_load(other, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == (X.tag | (unsigned int)(dfx_xcc_id() + 1));
-}
-// the consumer's side of a block hand-over, behind the barrier that follows the poll (every thread)
-static __device__ __forceinline__ void dfx_xcd_acquire(const DfxXcd &X) {
-    if (dfx_xcd_same(X, X.prod)) DFX_L1_INV();
-    else __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-// the producer's side: thread 0, behind a barrier in front of which EVERY wave has drained its stores (DFX_VMEM_DRAIN)
-static __device__ __forceinline__ void dfx_xcd_release(const DfxXcd &X, unsigned int *flag, unsigned int value) {
-    if (dfx_xcd_same(X, X.cons) && (!X.cons2 || dfx_xcd_same(X, X.cons2))) {
-        __hip_atomic_store(flag, value, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (X.stat) __hip_atomic_fetch_add(X.stat, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    } else {
-        __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-// A producer kernel of the persistent GRU phase announces its own completion (round 5): every workgroup, when its rows are stored, adds itself to a
-// counter; the last one resets the counter and raises the flag the consumers poll — the dfx_k_flag_set launch behind the producer (and the ~8 us of
-// host enqueue and dispatch it costs per layer and chunk) is gone.  cnt == nullptr: nothing (every launch outside that phase).
-// A follower workgroup picks the 16-clip group it serves: one whose RECURRENCE runs on this workgroup's XCD (workgroups go round-robin over the 8
-// XCDs with a rotation that differs from launch to launch, so block index g of the follower launch is usually NOT next to group g's recurrence).
-// rec[g] = registration words of the recurrences of one layer (all layers of a launch share the mapping), claim[8] = slots handed out per XCD
-// (zeroed by the host before the launch).  Own XCD first, then the others in turn: as many workgroups as groups, so everyone finds exactly one —
-// also if the dispatch was not an exact round robin.  Thread 0 decides, the result travels through *slot (LDS).  rec == nullptr: group = fallback.
-static __device__ __forceinline__ int dfx_xcd_claim(const unsigned int *rec, unsigned int tag, int groups, unsigned int *claim, int fallback, int spin_limit,
-                                                    unsigned int *err, int *slot) {
-    if (!rec || groups > 64) return fallback;
-    if (threadIdx.x == 0) {
-        auto xcd_of = [&](int g) { return (int)(__hip_atomic_load(rec + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 15u) - 1; };   // (re-read: no array in scratch)
-        bool ok = true;
-        for (int g = 0; g < groups && ok; ++g) {   // every recurrence of this pass has registered (they start first)
-            unsigned int v;
-            int spins = 0;
-            while (((v = __hip_atomic_load(rec + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) & ~15u) != tag || (v & 15u) == 0u) {
-                if (++spins > spin_limit) {
-                    dfx_raise(err + 2);
-                    ok = false;
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-        }
-        int got = -1;
-        const int x0 = dfx_xcc_id();
-        for (int d = 0; d < 8 && got < 0 && ok; ++d) {
-            const int x = (x0 + d) & 7;
-            int cnt = 0;
-            for (int g = 0; g < groups; ++g) cnt += xcd_of(g) == x;
-            if (!cnt) continue;
-            const unsigned int k = __hip_atomic_fetch_add(claim + x, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            if ((int)k >= cnt) continue;
-            for (int g = 0, j = 0; g < groups; ++g)
-                if (xcd_of(g) == x && j++ == (int)k) got = g;
-        }
-        *slot = got < 0 ? fallback : got;   // (got < 0: registrations timed out; err is raised)
-    }
-    __syncthreads();
-    const int r = *slot;
-    __syncthreads();
-    return r;
-}
-struct DfxPublish {
-    unsigned int *cnt = nullptr;   // completion counter of this producer (one word per stream: launches on a stream do not overlap)
-    unsigned int *flag = nullptr;
-    unsigned int value = 0, nblocks = 0;
-};
-static __device__ __forceinline__ void dfx_publish(const DfxPublish &P) {
-    if (!P.cnt) return;
-    DFX_VMEM_DRAIN();  // (s_barrier does not wait for the other waves' stores: each wave drains its own in front of it)
-    __syncthreads();   // the workgroup's stores happen before thread 0's release below (one L2 write-back per workgroup; a release fence in
-                       // every thread in front of the barrier is one per WAVE and costs the step 1.6 ms, measurements R5.10)
-    if (threadIdx.x == 0) {
-        const unsigned int old = __hip_atomic_fetch_add(P.cnt, 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-        if (old + 1u == P.nblocks) {
-            __hip_atomic_store(P.cnt, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            __hip_atomic_store(P.flag, P.value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-        }
-    }
-}
+#include "dfx_gru_sync.h"   // the flag hand-overs of the persistent GRU phase (DfxPublish, DfxXcd, DfxWaiter, the flag kernels): the protocol is written down there
 struct DfxPhArgs {
     const float *a;      // [M, 256]
     const dfx_h8 *wf;    // [N/64][8][4][2][64] fragment-ordered, pre-scaled f16 hi/lo of W[k][n]
@@ -4088,7 +3997,8 @@ struct DfxFollowSync {
 template <int K0, int K1, int K2>
 __global__ void __launch_bounds__(512, 1) dfx_k_emb_follow(DfxFanArgs A, DfxFollowSync Y) {
     __shared__ int gslot;
-    const int g = dfx_xcd_claim(Y.xclaim ? Y.x.prod : nullptr, Y.x.tag, Y.groups, Y.xclaim, (int)blockIdx.x, Y.spin_limit, Y.err, &gslot);
+    DfxWaiter W{Y.spin_limit, Y.err};
+    const int g = dfx_xcd_claim(Y.xclaim ? Y.x.prod : nullptr, Y.x.tag, Y.groups, Y.xclaim, (int)blockIdx.x, W, &gslot);
     const int tid = threadIdx.x, wave = tid >> 6;
     const int64_t b0 = (int64_t)g * 16;
     const int nclip = (int)(Y.B - b0 < 16 ? Y.B - b0 : 16);
@@ -4108,17 +4018,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_emb_follow(DfxFanArgs A, DfxFoll
     dfx_xcd_register(X);
     for (int64_t t0 = 0; t0 < Y.T; t0 += DFX_EF_STEPS) {
         const int64_t t1 = t0 + DFX_EF_STEPS < Y.T ? t0 + DFX_EF_STEPS : Y.T;
-        if (tid == 0) {
-            const unsigned int want = Y.pbase + (unsigned int)t1;
-            int spins = 0;
-            while ((int)(__hip_atomic_load(Y.src + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > Y.spin_limit) {
-                    dfx_raise(Y.err + 2);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-        }
+        if (tid == 0) W.wait_ge<4>(Y.src + g, Y.pbase + (unsigned int)t1);
         __syncthreads();
         dfx_xcd_acquire(X);
         A.rm = DfxRowMap{Y.T, t1 - t0, t0};
@@ -4131,7 +4031,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_emb_follow(DfxFanArgs A, DfxFoll
         // kernels anywhere on the chip (the DF tail, the decoder tails) while this kernel is still running — they must leave this XCD's L2.
         // (Those readers are ordered behind a recurrence's chunk flag, whose release writes back the RECURRENCE's L2: the same one only as long as
         // nothing else disturbs the round-robin dispatch — two handles at once gave wrong samples with the light form here.)
-        if (tid == 0) __hip_atomic_store(Y.dst + g, Y.pbase + (unsigned int)t1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) dfx_sync_raise(Y.dst + g, Y.pbase + (unsigned int)t1, false);
     }
 }
 
@@ -4526,10 +4426,8 @@ struct DfxGhArgs {
                           // share few L2s, and L2s that other kernels can be kept away from (placement = speed only)
 };
 
-// Chunk-level synchronisation of the persistent form (dfx_k_gru_seq): the time axis is cut into K chunks; chunk k of a layer may run once
-// the layer's input projection of that chunk exists (ready >= base + k + 1, written by a flag kernel behind the projection on its
-// stream) and is announced to the consumers when it is complete (done[group] = base + k + 1).  Flags are monotonic over the life of the
-// model (no resets), compared as signed differences; every spin is bounded (a timeout sets err[2] and lets the kernel run on).
+// The flag words of one workgroup of the persistent form (dfx_k_gru_seq); the protocol: dfx_gru_sync.h.  Chunk k of a layer may run once
+// ready >= base + k + 1 and is announced as done[group] = base + k + 1.
 struct DfxGhSync {
     const unsigned int *ready;   // one word: chunks of gi available for this layer
     unsigned int *done;          // [groups]: chunks of y completed by each workgroup of this layer
@@ -4547,14 +4445,8 @@ struct DfxGhSync {
     unsigned int pbase = 0;
     int sblk = 16;               // steps per block of this layer's follower (a power of two)
     int yblk = 16;               // steps between two yprog announcements (= the block of the consumer's follower)
-    // Same-XCD hand-overs (DfxXcd): a producer and a consumer that share an L2 need neither the L2 write-back of an agent-scope release nor the L2
-    // invalidate of an agent-scope acquire — the invalidate alone throws the XCD's share of the streamed W_hh out of the L2 every 16 steps of every
-    // recurrence on it (measured with both left out: 7.9 -> 7.3 us per step).  Every party registers the XCD it runs on; a hand-over whose partner
-    // is registered on the same XCD drains its stores (s_waitcnt vmcnt(0) in every wave in front of the barrier), raises the flag with a plain
-    // device-scope store, and the consumer invalidates its L1 only.  Anything else — partner elsewhere, or not registered yet — takes the full form.
-    DfxXcd x;
+    DfxXcd x;                    // same-XCD hand-overs (dfx_gru_sync.h): this workgroup's registration word, its follower's and its consumer's
 };
-#define DFX_SYNC_SPIN_LIMIT (1 << 22)   /* default bound of every flag wait: polls with s_sleep, ~2 s (dfx_model::spin_limit, DFX_SYNC_SPIN_LIMIT) */
 
 // X32 (DFX_EXACT_FP32=1): the same kernel on exact fp32 matrix ops.  A fragment "pair" holds the same 32 bytes per lane — the eight weights
 // W[unit][32 kc + 8 q + 0..7] as fp32 instead of their f16 hi / lo halves — and feeds eight v_mfma_f32_16x16x4_f32 (op j contracts the
@@ -4649,42 +4541,22 @@ static __device__ __forceinline__ void dfx_gru_h3_run(const DfxGhArgs &A, int64_
     for (int g = 0; g < 3; ++g)
 #pragma unroll
         for (int s = 0; s < NS; ++s) gv[g][s] = make_float4(0.1f, 0.2f, 0.3f, 0.4f);
+    DfxWaiter W{Y.spin_limit, Y.err};
     // (follower-fed layer) the gi rows of steps < upto must exist before they are requested
     auto wait_gi = [&](int64_t upto) {
-        if (tid == 0) {
-            const unsigned int want = Y.pbase + (unsigned int)(upto < A.T ? upto : A.T);
-            int spins = 0;
-            while ((int)(__hip_atomic_load(Y.giprog, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > Y.spin_limit) {
-                    dfx_raise(Y.err + 2);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(2);
-            }
-        }
+        if (tid == 0) W.wait_ge<2>(Y.giprog, Y.pbase + (unsigned int)(upto < A.T ? upto : A.T));
         __syncthreads();
         dfx_xcd_acquire(Y.x);
     };
     if (SEQ) dfx_xcd_register(Y.x);
     const int nchunk = SEQ ? Y.K : 1;
-    const bool dead = false;
     for (int ck = 0; ck < nchunk; ++ck) {
     const int64_t c0 = SEQ ? (int64_t)Y.tb[ck] : A.t0, c1 = SEQ ? (int64_t)Y.tb[ck + 1] : A.t1;
     if (SEQ) {   // the input projection of this chunk must exist
         if (tid == 0 && Y.trace) Y.trace[ck * 3 + 0] = wall_clock64();
-        if (tid == 0 && !dead && !Y.giprog) {
-            const unsigned int want = Y.base + (unsigned int)ck + 1u;
-            int spins = 0;
-            while ((int)(__hip_atomic_load(Y.ready, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > Y.spin_limit) {
-                    dfx_raise(Y.err + 2);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(8);
-            }
-        }
+        if (tid == 0 && !Y.giprog) W.wait_ge<8>(Y.ready, Y.base + (unsigned int)ck + 1u);
         __syncthreads();
-        __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+        dfx_sync_acquire(false);
         if (Y.giprog && ck == 0) wait_gi(Y.sblk);   // (later blocks: one step before their first row is requested, below)
         if (tid == 0 && Y.trace) Y.trace[ck * 3 + 1] = wall_clock64();
     }
@@ -4814,7 +4686,7 @@ static __device__ __forceinline__ void dfx_gru_h3_run(const DfxGhArgs &A, int64_
     if (SEQ) {   // this workgroup's rows of chunk ck are complete: make them visible device-wide, then say so
         __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
         __syncthreads();
-        if (tid == 0) __hip_atomic_store(Y.done + grp, Y.base + (unsigned int)ck + 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        if (tid == 0) dfx_sync_raise(Y.done + grp, Y.base + (unsigned int)ck + 1u, false);
         if (tid == 0 && Y.trace) Y.trace[ck * 3 + 2] = wall_clock64();
     }
     }
@@ -4954,20 +4826,36 @@ static __device__ __forceinline__ DfxXcd dfx_pf_xcd(const DfxPfArgs &A, int f, i
     if (A.xme[f]) X.me = A.xme[f] + g, X.prod = A.xprod[f] ? A.xprod[f] + g : nullptr, X.cons = A.xcons[f] ? A.xcons[f] + g : nullptr, X.tag = A.xtag, X.stat = A.xstat;
     return X;
 }
+// What the two forms of the follower share: a workgroup finds the layer f and the group g it serves and registers (false: no layer for this block),
+// waits for its producer's block of steps [.., t1) and announces its own.  `slot`: one int of LDS for the claim.
+static __device__ __forceinline__ bool dfx_pf_begin(const DfxPfArgs &A, DfxWaiter &W, int *slot, int &f, int &g) {
+    f = (int)(blockIdx.x / (unsigned)A.groups);
+    if (f >= A.nf) return false;
+    g = dfx_xcd_claim(A.xrec ? (A.xcons[f] ? A.xcons[f] : A.xrec) : nullptr, A.xtag, A.groups,   // (the registrations of the layer this follower FEEDS: with groups % 8 != 0 the layers sit on different XCDs)
+                      A.xclaim ? A.xclaim + 8 * f : nullptr, (int)(blockIdx.x % (unsigned)A.groups), W, slot);
+    dfx_xcd_register(dfx_pf_xcd(A, f, g));
+    return true;
+}
+static __device__ __forceinline__ void dfx_pf_wait_block(const DfxPfArgs &A, DfxWaiter &W, int f, int g, int t1) {
+    if (threadIdx.x == 0) W.wait_ge<4>(A.yprog[f] + g, A.pbase + (unsigned int)t1);
+    __syncthreads();
+    dfx_xcd_acquire(dfx_pf_xcd(A, f, g));
+}
+// (thread 0 speaks, behind the block's last barrier, in front of which every wave has drained its stores)
+static __device__ __forceinline__ void dfx_pf_raise_block(const DfxPfArgs &A, int f, int g, int t1) {
+    if (threadIdx.x == 0) dfx_xcd_release(dfx_pf_xcd(A, f, g), A.giprog[f] + g, A.pbase + (unsigned int)t1);
+}
 __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow(DfxPfArgs A) {
     constexpr int NW = 8, CT = 4, NTH = 64 * NW, SB = 2 * NW, N = 768;   // SB steps per block
     constexpr int CH8 = 8 * CT * 2 * 64;
     constexpr int PER_T = CH8 / NTH;
     DFX_DYN_SMEM(dfx_h8, ws);  // [2][CH8]
-    const int f = (int)(blockIdx.x / (unsigned)A.groups);
-    if (f >= A.nf) return;
-    const int g = dfx_xcd_claim(A.xrec ? (A.xcons[f] ? A.xcons[f] : A.xrec) : nullptr, A.xtag, A.groups,   // (the registrations of the layer this follower FEEDS: with groups % 8 != 0 the layers sit on different XCDs)
-                                A.xclaim ? A.xclaim + 8 * f : nullptr, (int)(blockIdx.x % (unsigned)A.groups), A.spin_limit, A.err,
-                                reinterpret_cast<int *>(ws));
+    DfxWaiter W{A.spin_limit, A.err};
+    int f, g;
+    if (!dfx_pf_begin(A, W, reinterpret_cast<int *>(ws), f, g)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
     constexpr int nchunks = N / (16 * CT);
     const int T = (int)A.T;
-    dfx_xcd_register(dfx_pf_xcd(A, f, g));
     for (int t0 = 0; t0 < T; t0 += SB) {
         const int t1 = t0 + SB < T ? t0 + SB : T;
         int zoff = 0, jz = jl;
@@ -4982,19 +4870,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow(DfxPfArgs A) {
         // the first chunk of W does not depend on the producer: stage it in front of the wait (buffer 0 is free: nchunks is even)
 #pragma unroll
         for (int i = 0; i < PER_T; ++i) ws[i * NTH + tid] = wf[i * NTH + tid];
-        if (tid == 0) {
-            const unsigned int want = A.pbase + (unsigned int)t1;
-            int spins = 0;
-            while ((int)(__hip_atomic_load(A.yprog[f] + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > A.spin_limit) {
-                    dfx_raise(A.err + 2);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-        }
-        __syncthreads();
-        dfx_xcd_acquire(dfx_pf_xcd(A, f, g));
+        dfx_pf_wait_block(A, W, f, g, t1);
         dfx_h8 xh[2][8], xl[2][8];
         float unscale[2];
         int trow[2];
@@ -5095,8 +4971,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow(DfxPfArgs A) {
             }
             __syncthreads();
         }
-        // the block's gi rows are stored (in front of the last barrier): say so
-        if (tid == 0) dfx_xcd_release(dfx_pf_xcd(A, f, g), A.giprog[f] + g, A.pbase + (unsigned int)t1);
+        dfx_pf_raise_block(A, f, g, t1);   // the block's gi rows are stored (in front of the last barrier): say so
     }
 }
 
@@ -5111,15 +4986,12 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow_x32(DfxPfArgs A) {
     constexpr int PER_T = CHF / 4 / NTH;      // float4 pieces per thread and chunk (8)
     constexpr int HP = PER_T / 2;
     DFX_DYN_SMEM(float, wsf);  // [2][CHF]
-    const int f = (int)(blockIdx.x / (unsigned)A.groups);
-    if (f >= A.nf) return;
-    const int g = dfx_xcd_claim(A.xrec ? (A.xcons[f] ? A.xcons[f] : A.xrec) : nullptr, A.xtag, A.groups,   // (the registrations of the layer this follower FEEDS: with groups % 8 != 0 the layers sit on different XCDs)
-                                A.xclaim ? A.xclaim + 8 * f : nullptr, (int)(blockIdx.x % (unsigned)A.groups), A.spin_limit, A.err,
-                                reinterpret_cast<int *>(wsf));
+    DfxWaiter W{A.spin_limit, A.err};
+    int f, g;
+    if (!dfx_pf_begin(A, W, reinterpret_cast<int *>(wsf), f, g)) return;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
     constexpr int nchunks = N / (16 * CT);
     const int T = (int)A.T;
-    dfx_xcd_register(dfx_pf_xcd(A, f, g));
     // piece i of a chunk (i compile-time): k = 32 i + kt, kt = tid / 16, columns 4 n4 .. + 3 of the chunk, n4 = tid % 16; its LDS row is
     // 4 (k % 64) + k / 64 = 4 kt + 128 (i % 2) + i / 2, whose parity — the column flip — is that of i / 2: one source and two destination bases per thread
     const int kt = tid >> 4, n4 = tid & 15;
@@ -5144,19 +5016,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow_x32(DfxPfArgs A) {
         float *orow = A.gi[f] + (okc ? clip : 0) * A.T * N;
 #pragma unroll
         for (int i = 0; i < PER_T; ++i) *piece_dst(wsf, i) = *piece_src(w, 0, i);
-        if (tid == 0) {
-            const unsigned int want = A.pbase + (unsigned int)t1;
-            int spins = 0;
-            while ((int)(__hip_atomic_load(A.yprog[f] + g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - want) < 0) {
-                if (++spins > A.spin_limit) {
-                    dfx_raise(A.err + 2);
-                    break;
-                }
-                __builtin_amdgcn_s_sleep(4);
-            }
-        }
-        __syncthreads();
-        dfx_xcd_acquire(dfx_pf_xcd(A, f, g));
+        dfx_pf_wait_block(A, W, f, g, t1);
         float4 xv[2][16];
         int trow[2];
         bool okr[2];
@@ -5227,48 +5087,6 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow_x32(DfxPfArgs A) {
             }
             __syncthreads();
         }
-        if (tid == 0) dfx_xcd_release(dfx_pf_xcd(A, f, g), A.giprog[f] + g, A.pbase + (unsigned int)t1);
+        dfx_pf_raise_block(A, f, g, t1);
     }
 }
-
-// flag kernels of the persistent GRU phase: dfx_k_flag_set runs behind a producer on its stream (the kernel boundary in front of it
-// has made the producer's writes visible), dfx_k_wait_ge holds its stream until all n flags have reached the target
-__global__ void dfx_k_flag_set(unsigned int *flag, unsigned int value) {
-    if (threadIdx.x == 0) __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
-}
-__global__ void dfx_k_wait_ge(const unsigned int *flags, int n, unsigned int target, unsigned int *err, int spin_limit) {
-    bool ok = false;
-    int spins = 0;
-    while (!ok) {
-        ok = true;
-        for (int i = threadIdx.x; i < n; i += blockDim.x)
-            ok = ok && (int)(__hip_atomic_load(flags + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) - target) >= 0;
-        ok = __all(ok);   // one wave
-        if (!ok) {
-            if (++spins > spin_limit) {
-                if (threadIdx.x == 0) dfx_raise(err + 2);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(16);
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-}
-
-// Handshake of dfx_model_create (DFX_Q_HWQ_PROBE): one single-wave launch per stream of the persistent phase; each adds itself to a
-// counter and waits, bounded, until all n have arrived — which only happens if the n streams really run at the same time (streams
-// that share a hardware queue run one after the other: the first then waits in vain and raises *fail).
-__global__ void dfx_k_probe_meet(unsigned int *cnt, unsigned int n, int spin_limit, unsigned int *fail) {
-    if (threadIdx.x == 0) {
-        __hip_atomic_fetch_add(cnt, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        int spins = 0;
-        while (__hip_atomic_load(cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < n) {
-            if (++spins > spin_limit) {
-                dfx_raise(fail);
-                break;
-            }
-            __builtin_amdgcn_s_sleep(16);
-        }
-    }
-}
-

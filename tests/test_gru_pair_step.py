@@ -60,3 +60,16 @@ def test_pair_step_with_agent_scope_hand_overs(hip_backend, monkeypatch):
     y_far = _run(monkeypatch, p, x, {"DFX_GRU_PAIR_FAR": "1"}, True, pair=True)
     assert torch.equal(y_far, _run(monkeypatch, p, x, {}, True, pair=True))
     assert torch.equal(y_far, _run(monkeypatch, p, x, {"DFX_GRU_PAIR": "0"}, True))
+
+
+@pytest.mark.gpu
+def test_exact_fp32_phase_on_one_cu_gives_the_bits_of_the_launch_form(hip_backend, monkeypatch):
+    """DFX_EXACT_FP32=1: the persistent phase runs dfx_k_gru_seq_x32 (one CU per 16 clips: the exact mode has no pair form) fed by
+    dfx_k_proj_follow_x32, whose hand-overs are those of csrc/dfx_gru_sync.h, against one launch per layer and time chunk.  20 clips x 17
+    frames: a partly live second group, a full block of the projection followers plus one step."""
+    p = named_params("df3")
+    clips, frames = 20, 17
+    x = torch.from_numpy((0.1 * np.random.default_rng(11).standard_normal((clips, frames * HOP))).astype(np.float32)).cuda()
+    y_seq = _run(monkeypatch, p, x, {"DFX_EXACT_FP32": "1"}, True)   # the persistent phase ran, not on pairs
+    assert torch.isfinite(y_seq).all() and float(y_seq.abs().max()) > 0
+    assert torch.equal(y_seq, _run(monkeypatch, p, x, {"DFX_EXACT_FP32": "1", "DFX_GRU_SEQ": "0"}, False))   # neither ran
