@@ -125,6 +125,15 @@ SIGNATURES = {
     "dfx_stream_set_pausable": (_i, [_vp, _i]),
     "dfx_stream_process_active": (_i, [_vp, _fp, _i64, _fp, _fp, _vp, _vp]),
     "dfx_stream_process_raw": (_i, [_vp, _fp, _fp, _fp, _vp, _fp, _vp]),
+    "dfx_stream_set_sample_rate": (_i, [_vp, _i, _i, C.c_double, _i, C.c_double]),
+    "dfx_stream_sample_rate": (_i, [_vp]),
+    "dfx_stream_resample_delay": (_i64, [_vp]),
+    "dfx_stream_process_pcm16": (_i, [_vp, _vp, _i64, _vp, _fp, _vp, _vp]),
+    "dfx_stream_resampler_create": (_i, [_vp, _i64, _i64, C.POINTER(_vp)]),
+    "dfx_stream_resampler_free": (None, [_vp]),
+    "dfx_stream_resampler_reset": (_i, [_vp, C.POINTER(_i64), _i64, _vp]),
+    "dfx_stream_resampler_delay": (_i, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dfx_stream_resampler_process": (_i, [_vp, _vp, _i, _i64, _i64, _vp, _i, _i64, _vp, _vp]),
     "dfx_prof_kernel_count": (_i, []),
     "dfx_prof_kernel_name": (C.c_char_p, [_i]),
     "dfx_prof_enable": (_i, [C.c_uint32]),

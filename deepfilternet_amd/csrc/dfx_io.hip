@@ -263,3 +263,5 @@ extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, i
     DFX_LAUNCH_CHECK();
     return DFX_OK;
 }
+
+#include "dfx_io_stream.h"

@@ -246,6 +246,16 @@ struct dfx_stream_state {
     bool lim_rows = false, beta_rows = false, thr_rows = false;
     unsigned char *set_buf = nullptr;   // float lim [B] (linear), beta [B], thr [B][3]
     size_t sb_lim = 0, sb_beta = 0, sb_thr = 0;
+    // Streaming at the caller's rate (dfx_stream_set_sample_rate): an up-sampler sr -> model rate in front of the pass and a down-sampler
+    // behind it, both over all rows and in step form (dfx_stream_resampler_*: csrc/dfx_io_stream.h), around model-rate staging rows
+    // [B, nmax * hop].  sr == 0: no rate set — a call takes today's path (the staging rows then serve dfx_stream_process_pcm16 alone).
+    int sr = 0;
+    int64_t hop_native = 0;
+    dfx_resampler *rs_up = nullptr, *rs_dn = nullptr;
+    dfx_stream_resampler *up = nullptr, *dn = nullptr;
+    float *stage_in = nullptr, *stage_out = nullptr;   // [B, nmax * hop] each
+    void *thru_tmp = nullptr;                          // [B, nmax * hop_native] floats: where the down-sampler writes during the pass-through
+    std::vector<unsigned char> row_active;             // [B], this call: the resamplers' mask (a paused stream's rows: 0)
     // (Replaying a steady-state call from a hipGraph was built in round 1 and removed in round 4: on ROCm 7.2 the replay of the hop's kernel nodes
     // took 2.0-2.2 ms per call where plain launches take 0.4.)
 };
@@ -362,11 +372,23 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     return DFX_OK;
 }
 
+// the handle's sample-rate converters (dfx_stream_set_sample_rate) go; the staging rows stay
+static void stream_rate_clear(dfx_stream_state *s) {
+    dfx_stream_resampler_free(s->up), dfx_stream_resampler_free(s->dn);
+    dfx_resampler_free(s->rs_up), dfx_resampler_free(s->rs_dn);
+    if (s->thru_tmp) (void)hipFree(s->thru_tmp);
+    s->up = s->dn = nullptr, s->rs_up = s->rs_dn = nullptr, s->thru_tmp = nullptr;
+    s->sr = 0, s->hop_native = 0;
+}
+
 extern "C" void dfx_stream_free(dfx_stream_state *s) {
     if (!s) return;
     if (s->buf) (void)hipFree(s->buf);
     if (s->gate_buf) (void)hipFree(s->gate_buf);
     if (s->set_buf) (void)hipFree(s->set_buf);
+    stream_rate_clear(s);
+    if (s->stage_in) (void)hipFree(s->stage_in);
+    if (s->stage_out) (void)hipFree(s->stage_out);
     delete s;
 }
 
@@ -405,6 +427,10 @@ extern "C" int dfx_stream_reset(dfx_stream_state *s, void *stream) {
     s->hflip = 0;
     s->c0ring_ok = true;   // (zeros = the causal padding in front of the stream)
     s->fresh = true;
+    if (s->sr) {
+        if (int rc = dfx_stream_resampler_reset(s->up, nullptr, 0, stream)) return rc;
+        if (int rc = dfx_stream_resampler_reset(s->dn, nullptr, 0, stream)) return rc;
+    }
     return DFX_OK;
 }
 
@@ -488,6 +514,13 @@ extern "C" int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids,
     }
     for (int64_t i = 0; i < count; ++i)
         for (int k = 0; k < ch; ++k) s->birth[(size_t)(ids[i] * ch + k)] = s->frames;
+    if (s->sr) {   // the streams' rows of both converters start over too
+        std::vector<int64_t> rows((size_t)count * ch);
+        for (int64_t i = 0; i < count; ++i)
+            for (int k = 0; k < ch; ++k) rows[(size_t)(i * ch + k)] = ids[i] * ch + k;
+        if (int rc = dfx_stream_resampler_reset(s->up, rows.data(), (int64_t)rows.size(), stream)) return rc;
+        if (int rc = dfx_stream_resampler_reset(s->dn, rows.data(), (int64_t)rows.size(), stream)) return rc;
+    }
     if (s->frames > 0) {   // (frames == 0: every stream of the handle is at its start anyway)
         s->mixed_until = s->frames + s->H + s->L;
         s->warm_until = s->frames + s->L;
@@ -585,7 +618,7 @@ extern "C" int dfx_stream_set_pausable(dfx_stream_state *s, int enable) {
     return DFX_OK;
 }
 
-extern "C" int dfx_stream_frame_length(const dfx_stream_state *s) { return s ? s->st->hop : 0; }
+extern "C" int dfx_stream_frame_length(const dfx_stream_state *s) { return s ? (s->sr ? (int)s->hop_native : s->st->hop) : 0; }
 extern "C" int dfx_stream_delay_frames(const dfx_stream_state *s) { return s ? s->L : 0; }
 
 extern "C" int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db) {
@@ -1166,8 +1199,95 @@ static int stream_call_end(const dfx_model *m, hipStream_t s) {
     return model_poll(m);
 }
 static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s);
-extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, const unsigned char *active,
-                                         void *stream) {
+// ---- streaming at the caller's rate, and on 16-bit PCM ---------------------------------------------------------------------------------
+static int stream_stage_alloc(dfx_stream_state *S) {   // the model-rate staging rows [B, nmax * hop]
+    if (S->stage_in) return DFX_OK;
+    const size_t bytes = (size_t)S->B * S->nmax * S->st->hop * 4;
+    if (hipMalloc(reinterpret_cast<void **>(&S->stage_in), bytes) != hipSuccess) DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream: staging rows of %zu bytes", bytes);
+    if (hipMalloc(reinterpret_cast<void **>(&S->stage_out), bytes) != hipSuccess) {
+        (void)hipFree(S->stage_in);
+        S->stage_in = nullptr;
+        DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream: staging rows of %zu bytes", bytes);
+    }
+    return DFX_OK;
+}
+
+extern "C" int dfx_stream_set_sample_rate(dfx_stream_state *S, int sr, int lowpass_filter_width, double rolloff, int method, double beta) {
+    if (!S || sr <= 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_sample_rate: null handle or bad rate");
+    if (!S->fresh) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_sample_rate: the handle has consumed hops (set the rate before the first process call, or at a dfx_stream_reset)");
+    const int msr = S->st->sr, hop = S->st->hop;
+    int64_t g = sr, b = msr;
+    while (b) {
+        const int64_t t = g % b;
+        g = b, b = t;
+    }
+    const int q = (int)(msr / g);
+    if (sr != msr && hop % q)
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_set_sample_rate: at %d Hz the model's hop of %d samples (%d Hz) is not a whole number of resampler frames (the hop must be a multiple of %d)",
+                 sr, hop, msr, q);
+    if (int rc = dfx_require_device()) return rc;
+    stream_rate_clear(S);
+    if (sr == msr) return DFX_OK;
+    const int64_t h = (int64_t)hop / q * (sr / g);
+    int rc;
+    if ((rc = dfx_resampler_create(sr, msr, lowpass_filter_width, rolloff, method, beta, &S->rs_up)) ||
+        (rc = dfx_resampler_create(msr, sr, lowpass_filter_width, rolloff, method, beta, &S->rs_dn)) ||
+        (rc = dfx_stream_resampler_create(S->rs_up, S->B, (int64_t)S->nmax * h, &S->up)) ||
+        (rc = dfx_stream_resampler_create(S->rs_dn, S->B, (int64_t)S->nmax * hop, &S->dn)) || (rc = stream_stage_alloc(S))) {
+        stream_rate_clear(S);
+        return rc;
+    }
+    if (hipMalloc(&S->thru_tmp, (size_t)S->B * S->nmax * h * 4) != hipSuccess) {
+        stream_rate_clear(S);
+        DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream_set_sample_rate: device allocation failed");
+    }
+    S->sr = sr, S->hop_native = h;
+    return DFX_OK;
+}
+extern "C" int dfx_stream_sample_rate(const dfx_stream_state *S) { return S ? (S->sr ? S->sr : S->st->sr) : 0; }
+extern "C" int64_t dfx_stream_resample_delay(const dfx_stream_state *S) {
+    if (!S || !S->sr) return 0;
+    int64_t pu = 0, pd = 0;
+    (void)dfx_stream_resampler_delay(S->up, &pu, nullptr);
+    (void)dfx_stream_resampler_delay(S->dn, nullptr, &pd);   // (the down-sampler's delay in ITS output samples: the caller's rate)
+    return pu + pd;
+}
+
+// The pass between the converters (a rate is set) or between the PCM kernels (16-bit PCM at the model's rate): x -> stage_in -> the
+// model-rate pass, unchanged -> stage_out -> y, all on the caller's stream.
+static int stream_process_staged(dfx_stream_state *S, const void *x, int64_t n, void *y, bool pcm16, float *lsnr_out, hipStream_t s) {
+    const int64_t B = S->B, T = n * S->st->hop;
+    int rc;
+    if (!S->sr) {
+        if ((rc = dfx_pcm16_to_f32(static_cast<const int16_t *>(x), B * T, S->stage_in, s))) return rc;
+        if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
+        return dfx_f32_to_pcm16(S->stage_out, B * T, static_cast<int16_t *>(y), s);
+    }
+    const int64_t Tn = n * S->hop_native;
+    const unsigned char *act = nullptr;
+    if (S->any_paused) {   // a paused stream's rows sit both converters out
+        const int ch = S->channels;
+        S->row_active.resize((size_t)B);
+        for (int64_t r = 0; r < B; ++r) S->row_active[(size_t)r] = !S->paused[(size_t)(r / ch)];
+        act = S->row_active.data();
+    }
+    // (the handle-wide pass-through: the model-rate pass hands stage_in through and moves its STFT memory; the down-sampler's history follows
+    // those rows, its output is dropped and the caller gets its own samples back)
+    const bool thru = S->lim == 1.f;
+    if ((rc = dfx_stream_resampler_process(S->up, x, pcm16, Tn, Tn, S->stage_in, 0, T, act, s))) return rc;
+    if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
+    if ((rc = dfx_stream_resampler_process(S->dn, S->stage_out, 0, T, T, thru ? S->thru_tmp : y, thru ? 0 : pcm16, Tn, act, s))) return rc;
+    if (thru) {
+        const size_t row = (size_t)Tn * (pcm16 ? 2 : 4);
+        DFX_HIP(hipMemcpyAsync(y, x, (size_t)B * row, hipMemcpyDeviceToDevice, s));
+        for (int64_t r = 0; act && r < B; ++r)
+            if (!act[r]) DFX_HIP(hipMemsetAsync(static_cast<unsigned char *>(y) + (size_t)r * row, 0, row, s));
+    }
+    return DFX_OK;
+}
+
+static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, void *y, bool pcm16, float *lsnr_out, const unsigned char *active,
+                              void *stream) {
     if (!S || n <= 0 || n > S->nmax || !x || !y) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process: bad arguments (1 <= n_frames <= max_frames)");
     if (active && !S->pausable) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_active: a mask needs a pausable handle (dfx_stream_set_pausable)");
     if (int rc = dfx_require_device()) return rc;
@@ -1180,15 +1300,28 @@ extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, in
         for (size_t k = 0; active && k < ns; ++k)
             if (!active[k]) S->paused[k] = 1, S->any_paused = true;
     }
+    const bool staged = S->sr != 0 || pcm16;
+    if (staged)
+        if (int rc = stream_stage_alloc(S)) return rc;
     {
         DfxTurn turn(S->m, s, false);   // (the enqueue lock only: a hop starts no persistent phase)
         S->fresh = false;
-        if (int rc = stream_process_impl(S, x, n, y, lsnr_out, s)) return rc;
+        if (int rc = staged ? stream_process_staged(S, x, n, y, pcm16, lsnr_out, s)
+                            : stream_process_impl(S, static_cast<const float *>(x), n, static_cast<float *>(y), lsnr_out, s))
+            return rc;
     }
     return stream_call_end(S->m, s);
 }
+extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, const unsigned char *active,
+                                         void *stream) {
+    return stream_process_any(S, x, n, y, false, lsnr_out, active, stream);
+}
 extern "C" int dfx_stream_process(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, void *stream) {
-    return dfx_stream_process_active(S, x, n, y, lsnr_out, nullptr, stream);
+    return stream_process_any(S, x, n, y, false, lsnr_out, nullptr, stream);
+}
+extern "C" int dfx_stream_process_pcm16(dfx_stream_state *S, const int16_t *x, int64_t n, int16_t *y, float *lsnr_out, const unsigned char *active,
+                                        void *stream) {
+    return stream_process_any(S, x, n, y, true, lsnr_out, active, stream);
 }
 // A call of n hops as passes.  A hop is passed on its own while the handle keeps per-stream forms (gated, pausable: the stage decisions of
 // hop i shape the state hop i+1 starts from) or sits inside the warm-up of a stream that started over on its own

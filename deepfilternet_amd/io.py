@@ -89,6 +89,83 @@ def resample(audio: torch.Tensor, orig_sr: int, new_sr: int, method: str = "sinc
     return y.reshape(*shape[:-1], out_len)
 
 
+class StreamResampler:
+    """``resample`` call by call: ``rows`` independent signals, each call a piece ``[rows, m * block]`` (float32, or int16 PCM) ->
+    ``[rows, m * block * new_sr / orig_sr]`` in the input's dtype, with the filter's memory carried on the device.  Whatever the cut, a row's
+    concatenated output is ``resample(cat(zeros(P), x), orig_sr, new_sr, method)`` cut to whole frames: the output lags by ``delay``
+    samples (``P = ceil(width / block) * block`` input samples — whole frames, so that the samples land on the offline grid), and is
+    bit-identical between cuts.  ``process(x, active=mask)``: rows whose entry is false sit the call out (zeros, no state moves);
+    ``reset(rows)`` makes rows start over.  Parameter sets as in ``resample`` (``get_resample_params``)."""
+
+    def __init__(self, orig_sr: int, new_sr: int, rows: int, method: str = "sinc_fast", max_samples: Optional[int] = None):
+        if int(orig_sr) == int(new_sr):
+            raise ValueError("StreamResampler: the two rates are equal")
+        self._r = _resampler(int(orig_sr), int(new_sr), method, _lib.library_path())   # (kept alive: the handle points into it)
+        self.orig_sr, self.new_sr, self.rows = int(orig_sr), int(new_sr), int(rows)
+        g = int(np.gcd(self.orig_sr, self.new_sr))
+        self.block, self._nw = self.orig_sr // g, self.new_sr // g
+        if max_samples is None:
+            max_samples = -(-self.orig_sr // self.block) * self.block      # one second
+        self.max_samples = int(max_samples)
+        h = C.c_void_p()
+        _lib.check(_lib.lib().dfx_stream_resampler_create(self._r.h, self.rows, self.max_samples, C.byref(h)))
+        self._h = h
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            try:
+                _lib.lib().dfx_stream_resampler_free(h)
+            except Exception:  # noqa: BLE001
+                pass
+
+    def _delays(self) -> Tuple[int, int]:
+        a, b = C.c_int64(), C.c_int64()
+        _lib.check(_lib.lib().dfx_stream_resampler_delay(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    @property
+    def delay(self) -> int:
+        """Output samples by which the output lags the input."""
+        return self._delays()[1]
+
+    @property
+    def delay_in(self) -> int:
+        """The same delay in input samples (``P``)."""
+        return self._delays()[0]
+
+    def reset(self, rows=None) -> None:
+        if rows is None:
+            _lib.check(_lib.lib().dfx_stream_resampler_reset(self._h, None, 0, _lib.stream()))
+            return
+        ids = torch.as_tensor(rows).reshape(-1)
+        if ids.numel() and (ids.is_floating_point() or ids.is_complex() or ids.dtype == torch.bool):
+            raise TypeError("row indices must be integers")
+        ids = ids.to("cpu", torch.int64).contiguous()
+        _lib.check(_lib.lib().dfx_stream_resampler_reset(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), _lib.stream()))
+
+    def process(self, x: torch.Tensor, active=None) -> torch.Tensor:
+        src_dev = x.device
+        pcm16 = x.dtype == torch.int16
+        x = x.to(_lib.device(), torch.int16 if pcm16 else torch.float32).contiguous()
+        if x.dim() != 2 or x.shape[0] != self.rows:
+            raise ValueError(f"x must have shape [{self.rows}, m*{self.block}]")
+        mask = None
+        if active is not None:
+            mask = torch.as_tensor(active).reshape(-1)
+            if mask.is_floating_point() or mask.is_complex():
+                raise TypeError("active must hold bools or integers")
+            if mask.numel() != self.rows:
+                raise ValueError(f"active must have one entry per row ({self.rows})")
+            mask = (mask.to("cpu") != 0).to(torch.uint8).contiguous()
+        T = x.shape[1]
+        out_len = T // self.block * self._nw
+        y = torch.empty((self.rows, out_len), dtype=x.dtype, device=x.device)
+        _lib.check(_lib.lib().dfx_stream_resampler_process(self._h, _lib.ptr(x), int(pcm16), T, T, _lib.ptr(y), int(pcm16), out_len,
+                                                           C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
+        return y.to(src_dev)
+
+
 def pcm16_to_float(pcm: torch.Tensor) -> torch.Tensor:
     """int16 samples -> float32 in [-1, 1) (what torchaudio.load(normalize=True) returns)."""
     x = pcm.to(_lib.device()).contiguous()

@@ -41,6 +41,14 @@ sets its own after ``reset([i])``), and a paused stream's settings can be change
 before: they set every stream's value and make the handle uniform in that setting again.  The undelayed pass-through (``set_atten_lim(0)``)
 is a handle-wide mode; ``set_atten_lim(0, streams=[i])`` mixes with a limit just below 1 instead: stream i's noisy input comes back delayed
 like every other stream's output, and its state keeps advancing.  The steady hop costs no extra launch on a handle with per-stream settings.
+
+``sr=16000`` (8, 12, 16, 24, 32, 44.1, 88.2 or 96 kHz at a 48 kHz model) makes the handle take and return hops at the caller's own rate:
+``frame_length`` is then ``hop * sr / 48000`` samples, an up-sampler in front of the pass and a down-sampler behind it (stateful forms of
+``io.resample``'s filters, ``resample_method`` picks the parameter set) run on the device with the rest of the hop, and ``process`` also
+takes int16 PCM and returns int16 (at any rate, 48 kHz included).  The output equals ``io.resample`` -> a 48 kHz ``DfStream`` ->
+``io.resample`` with each resampler fed its whole-frame delay of zeros first; together they add ``resample_delay`` samples at the caller's
+rate (34 at 16 kHz, 294 at 44.1 kHz with ``sinc_fast``) to the latency.  Rates at which the hop is no whole number of resampler frames
+(22.05 kHz, 11.025 kHz) are refused.
 """
 from __future__ import annotations
 
@@ -57,7 +65,7 @@ from .model import DfNet
 class DfStream:
     def __init__(self, model: DfNet, df_state: DF, streams: int = 1, max_frames: int = 1, atten_lim_db: Optional[float] = None,
                  gating: bool = False, thresholds: Optional[Tuple[float, float, float]] = None, channels: int = 1,
-                 reduce_mask: str = "mean", pausable: bool = False):
+                 reduce_mask: str = "mean", pausable: bool = False, sr: Optional[int] = None, resample_method: str = "sinc_fast"):
         if not isinstance(model, DfNet):
             raise TypeError("DfStream needs a deepfilternet_amd.DfNet (see init_df)")
         h = C.c_void_p()
@@ -76,6 +84,13 @@ class DfStream:
             self.set_gating(True)
         if pausable:
             _lib.check(_lib.lib().dfx_stream_set_pausable(self._h, 1))
+        if sr is not None:
+            from .io import TA_RESAMPLE_KAISER, get_resample_params
+
+            rp = get_resample_params(resample_method)
+            _lib.check(_lib.lib().dfx_stream_set_sample_rate(self._h, int(sr), int(rp["lowpass_filter_width"]), float(rp.get("rolloff", 0.99)),
+                                                             int(rp["resampling_method"] == TA_RESAMPLE_KAISER),
+                                                             float(rp.get("beta", 14.769656459379492))))
 
     def __del__(self):
         h, self._h = getattr(self, "_h", None), None
@@ -87,8 +102,19 @@ class DfStream:
 
     @property
     def frame_length(self) -> int:
-        """df_get_frame_length (capi.rs:108): samples per hop."""
+        """df_get_frame_length (capi.rs:108): samples per hop, at the caller's rate (``sr``)."""
         return int(_lib.lib().dfx_stream_frame_length(self._h))
+
+    @property
+    def sr(self) -> int:
+        """The rate of the hops ``process`` takes and returns (the model's unless ``sr=`` was given)."""
+        return int(_lib.lib().dfx_stream_sample_rate(self._h))
+
+    @property
+    def resample_delay(self) -> int:
+        """Samples at the caller's rate by which the two sample-rate converters delay the output, on top of the STFT's and the lookahead's
+        latency (0 without ``sr=``)."""
+        return int(_lib.lib().dfx_stream_resample_delay(self._h))
 
     @property
     def delay_frames(self) -> int:
@@ -176,7 +202,8 @@ class DfStream:
 
     def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None):
         """df_process_frame (capi.rs:161) for every stream: ``frames`` [streams, n*hop] float32 -> enhanced [streams, n*hop]
-        (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB.
+        (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB.  int16 ``frames`` are
+        16-bit PCM (x / 32768) and come back as int16 (``float_to_pcm16``'s encoding); ``hop`` is ``frame_length``, at the caller's rate.
 
         ``active`` (pausable handles): a sequence or tensor of bools or integers, one per stream (``streams // channels``); a stream whose
         entry is false is paused for all hops of this call (zeros out, lsnr NaN, no state moves; its input rows must still be finite).
@@ -190,7 +217,8 @@ class DfStream:
                 raise ValueError(f"active must have one entry per stream ({self.streams // self.channels})")
             mask = (mask.to("cpu") != 0).to(torch.uint8).contiguous()
         src_dev = frames.device
-        x = frames.to(_lib.device(), torch.float32).contiguous()
+        pcm16 = frames.dtype == torch.int16
+        x = frames.to(_lib.device(), torch.int16 if pcm16 else torch.float32).contiguous()
         hop = self.frame_length
         if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] % hop or x.shape[1] == 0:
             raise ValueError(f"frames must have shape [{self.streams}, n*{hop}]")
@@ -199,7 +227,10 @@ class DfStream:
             raise ValueError(f"at most max_frames={self.max_frames} hops per call")
         y = torch.empty_like(x)
         lsnr = torch.empty((self.streams, n), dtype=torch.float32, device=x.device) if return_lsnr else None
-        if mask is None:
+        if pcm16:
+            _lib.check(_lib.lib().dfx_stream_process_pcm16(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr),
+                                                           C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
+        elif mask is None:
             _lib.check(_lib.lib().dfx_stream_process(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr), _lib.stream()))
         else:
             _lib.check(_lib.lib().dfx_stream_process_active(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr), C.c_void_p(mask.data_ptr()),

@@ -381,7 +381,7 @@ int dfx_stream_reset(dfx_stream_state *s, void *stream);                 /* back
 int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, void *stream);
 /* hops of network time each stream has consumed since its own last reset (host array, [rows / channels]); host bookkeeping, no device access */
 int dfx_stream_frames(const dfx_stream_state *s, int64_t *frames_out);
-int dfx_stream_frame_length(const dfx_stream_state *s);                  /* hop size in samples (df_get_frame_length) */
+int dfx_stream_frame_length(const dfx_stream_state *s);                  /* hop size in samples (df_get_frame_length), at the caller's rate */
 int dfx_stream_delay_frames(const dfx_stream_state *s);                  /* lookahead in hops */
 int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db);         /* df_set_atten_lim: |dB| >= 100 off, < 0.01 bypass */
 int dfx_stream_set_post_filter_beta(dfx_stream_state *s, float beta);    /* df_set_post_filter_beta: 0 disables the post filter */
@@ -415,6 +415,26 @@ int dfx_stream_process_active(dfx_stream_state *s, const float *x, int64_t n_fra
  * the reference signals "absent" with NULL pointers).  Gating must be on; no STFT / deep filtering / synthesis happens here. */
 int dfx_stream_process_raw(dfx_stream_state *s, const float *spec, float *gains, float *coefs, unsigned char *stages, float *lsnr,
                            void *stream);
+/* Streaming at the caller's sample rate.  dfx_stream_set_sample_rate(sr, ...) gives the handle an up-sampler sr -> model rate and a
+ * down-sampler model rate -> sr over all rows (dfx_stream_resampler_*, below; the filter parameters are dfx_resampler_create's) and the
+ * model-rate staging rows for max_frames hops.  dfx_stream_process / _process_active / _process_pcm16 then take and return hops of
+ * h = hop * sr / model_rate samples (dfx_stream_frame_length): x, y [rows, n_frames * h].  h must be a whole number of samples and of
+ * up-sampler blocks, i.e. model_rate / gcd(sr, model_rate) must divide the hop: 8, 12, 16, 24, 32, 44.1, 88.2, 96 kHz at 48 kHz / hop
+ * 480; 22.05 and 11.025 kHz fail with DFX_ERR_UNSUPPORTED.  Accepted only at a reset point (no hop consumed since create / dfx_stream_reset),
+ * else DFX_ERR_INVALID_ARG; sr == the model's rate clears it.  The output equals
+ *   up  = resample(cat(zeros(P_u), x), sr, model_rate)[:, : n_total * hop]
+ *   ref = resample(cat(zeros(P_d), z), model_rate, sr)[:, : n_total * h],   z = what the model-rate handle makes of `up` under the same calls,
+ * so the converters add P_u + P_d * sr / model_rate samples of delay at the caller's rate (dfx_stream_resample_delay; 34 at 16 kHz, 294 at
+ * 44.1 kHz with sinc_fast) on top of the STFT's and the lookahead's.  Resets zero the converters' histories (single streams: their rows), a
+ * paused stream's rows are inactive in both converters, and in the handle-wide pass-through the caller gets its own samples back unchanged
+ * while both converters keep their histories moving.  dfx_stream_process_raw is spectral and knows no rate. */
+int dfx_stream_set_sample_rate(dfx_stream_state *s, int sr, int lowpass_filter_width, double rolloff, int method, double beta);
+int dfx_stream_sample_rate(const dfx_stream_state *s);                   /* the caller's rate (the model's when none was set) */
+int64_t dfx_stream_resample_delay(const dfx_stream_state *s);            /* samples at the caller's rate; 0 without a rate */
+/* dfx_stream_process_active on 16-bit PCM: x, y int16 [rows, n_frames * frame_length] (x / 32768 in, dfx_f32_to_pcm16's encoding out).  At a
+ * converted rate the conversions happen inside the two converter kernels; at the model's rate through dfx_pcm16_to_f32 / dfx_f32_to_pcm16. */
+int dfx_stream_process_pcm16(dfx_stream_state *s, const int16_t *x, int64_t n_frames, int16_t *y, float *lsnr, const unsigned char *active,
+                             void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-frame Wiener / MVDR filters: df.multiframe.MfWf.forward (multiframe.py:282-321) and MfMvdr.forward (:373-413), the filter
@@ -450,6 +470,20 @@ int dfx_resampler_kernel(int orig_sr, int new_sr, int lowpass_filter_width, doub
                          int *taps, int *width, float *w_host /* may be NULL */, int64_t cap_floats);
 int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, int64_t T, int64_t x_stride, float *y, int64_t y_stride,
                  void *stream);
+/* The resampler in step form: per-row state carried across calls.  A call takes in_len = m * block samples per row (block = orig_sr /
+ * gcd, the input samples of one frame; in_len a multiple of it and <= max_in_samples, else DFX_ERR_INVALID_ARG) and writes m * new_sr / gcd.
+ * Whatever the cut into calls, a row's concatenated output equals dfx_resample applied to P zeros followed by the row's signal, cut to
+ * whole frames: P = ceil(width / block) * block input samples of delay = D = P * new_sr / orig_sr output samples (dfx_stream_resampler_delay);
+ * bit-identical between cuts.  x / y: float32, or int16 PCM (x / 32768 in, dfx_f32_to_pcm16's encoding out), row strides in samples.
+ * active_host: HOST array [rows], zero = the row sits the call out (zeros out, its state does not move); NULL = all rows.  reset: rows = HOST
+ * array of row indices, NULL = every row.  The handle refers to `r`, which must outlive it.  All calls are enqueued on `stream`. */
+typedef struct dfx_stream_resampler dfx_stream_resampler;
+int dfx_stream_resampler_create(const dfx_resampler *r, int64_t rows, int64_t max_in_samples, dfx_stream_resampler **out);
+void dfx_stream_resampler_free(dfx_stream_resampler *h);
+int dfx_stream_resampler_reset(dfx_stream_resampler *h, const int64_t *rows /* NULL = all */, int64_t count, void *stream);
+int dfx_stream_resampler_delay(const dfx_stream_resampler *h, int64_t *in_samples, int64_t *out_samples);
+int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_is_pcm16, int64_t in_len, int64_t x_stride, void *y,
+                                 int y_is_pcm16, int64_t y_stride, const unsigned char *active_host /* NULL = all */, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Per-kernel timing (measurement aid, no reference counterpart; the reference only logs wall-clock RTF,

@@ -2,7 +2,7 @@
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
     python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact] [--paused FRACTION]
-                                  [--per-stream-settings]
+                                  [--per-stream-settings] [--sr 16000] [--pcm16]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
@@ -10,6 +10,8 @@ callers come and go.
 the pool (0: a pausable handle on which nobody pauses).
 --per-stream-settings: every stream gets its own attenuation limit and post-filter beta (and, with --gating, thresholds) before the first call
 (DfStream.set_*(..., streams=ids)); the JSON line also carries the host time of one setter call over all ids (setter_host_ms).
+--sr RATE: the handle takes and returns hops at RATE (DfStream(sr=RATE): an up-sampler in front of the 48 kHz pass, a down-sampler behind it);
+--pcm16: the hops are int16 PCM in both directions.  The JSON line carries both; without them the call is the plain 48 kHz float one.
 --exact: the model is created under DFX_EXACT_FP32=1 (every contraction in fp32: the one-hop GRU layers on dfx_k_gru_step_x32).
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
@@ -39,6 +41,8 @@ def main() -> None:
                     help="pausable handle; this share of the streams (a rotating block) sits every call out")
     ap.add_argument("--per-stream-settings", action="store_true",
                     help="a distinct attenuation limit and post-filter beta per stream (with --gating also thresholds), set per stream")
+    ap.add_argument("--sr", type=int, default=None, help="the callers' sample rate (hops of hop * sr / 48000 samples; default: the model's 48 kHz)")
+    ap.add_argument("--pcm16", action="store_true", help="int16 PCM hops in and out")
     ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
     if args.exact:
@@ -56,9 +60,11 @@ def main() -> None:
     exact = bool(model.query(model.Q_EXACT_FP32))
     dev = _lib.device()
     for n in args.frames_per_call:
-        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None)
+        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr)
         hop = rt.frame_length
         x = 0.1 * torch.randn((args.streams, n * hop), device=dev)
+        if args.pcm16:
+            x = (x * 32768.0).to(torch.int16)
         nslots, churn_pos = args.streams, 0
 
         def churn():   # the next K slots of the pool get a new caller
@@ -107,7 +113,7 @@ def main() -> None:
                 torch.cuda.synchronize()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert torch.isfinite(y).all()
+        assert y.dtype == x.dtype and (args.pcm16 or torch.isfinite(y).all())
         # host cost of a call: 32 calls enqueued into empty queues, no wait in between (what bounds the rate on a box with a slow host)
         t1 = time.perf_counter()
         for i in range(32):
@@ -119,7 +125,8 @@ def main() -> None:
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
                           "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "paused": args.paused, "exact_fp32": exact,
-                          "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms,
+                          "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms, "sr": rt.sr, "pcm16": bool(args.pcm16),
+                          "resample_delay_ms": rt.resample_delay / rt.sr * 1e3,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         del rt
 
