@@ -129,6 +129,9 @@ SIGNATURES = {
     "dfx_stream_sample_rate": (_i, [_vp]),
     "dfx_stream_resample_delay": (_i64, [_vp]),
     "dfx_stream_process_pcm16": (_i, [_vp, _vp, _i64, _vp, _fp, _vp, _vp]),
+    "dfx_stream_snapshot_bytes": (_i, [_vp, C.POINTER(_i64)]),
+    "dfx_stream_export_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _vp]),
+    "dfx_stream_import_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _i, _vp]),
     "dfx_stream_resampler_create": (_i, [_vp, _i64, _i64, C.POINTER(_vp)]),
     "dfx_stream_resampler_free": (None, [_vp]),
     "dfx_stream_resampler_reset": (_i, [_vp, C.POINTER(_i64), _i64, _vp]),

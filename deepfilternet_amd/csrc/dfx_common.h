@@ -28,6 +28,9 @@ void dfx_set_error(const char *fmt, ...);
     } while (0)
 int dfx_require_device();
 
+// the history rows of a step-form resampler (dfx_io_stream.h), for dfx_stream_export_streams / dfx_stream_import_streams
+void dfx_stream_resampler_rows(const dfx_stream_resampler *h, float **cur, float **other, int *hist);
+
 // ---- FFT plan (passed by value into kernels) ----------------------------------------------------------------------
 #define DFX_MAX_STAGES 12
 struct DfxFftPlan {

@@ -218,6 +218,12 @@ extern "C" int dfx_stream_resampler_reset(dfx_stream_resampler *h, const int64_t
     return DFX_OK;
 }
 
+// The rows' histories for the model's stream export / import (dfx_stream_move.h): the buffer that is current, the one the next call writes, and
+// the floats per row.  Internal (dfx_common.h): a stream's rows are moved by the table kernel that moves the rest of its state.
+void dfx_stream_resampler_rows(const dfx_stream_resampler *h, float **cur, float **other, int *hist) {
+    *cur = h->d_hist[h->cur], *other = h->d_hist[h->cur ^ 1], *hist = h->hist;
+}
+
 extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_is_pcm16, int64_t in_len, int64_t x_stride, void *y,
                                             int y_is_pcm16, int64_t y_stride, const unsigned char *active_host, void *stream) {
     if (!h) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_resampler_process: null handle");

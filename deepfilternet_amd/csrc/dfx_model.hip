@@ -1524,4 +1524,5 @@ extern "C" int dfx_model_workspace_bytes(const dfx_model *m, int64_t B, int64_t 
 #include "dfx_model_launch.h"
 #include "dfx_model_forward.h"
 #include "dfx_model_stream.h"
+#include "dfx_stream_move.h"
 #include "dfx_model_enhance.h"

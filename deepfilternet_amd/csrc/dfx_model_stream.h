@@ -251,6 +251,8 @@ struct dfx_stream_state {
     // [B, nmax * hop].  sr == 0: no rate set — a call takes today's path (the staging rows then serve dfx_stream_process_pcm16 alone).
     int sr = 0;
     int64_t hop_native = 0;
+    int rs_width = 0, rs_method = 0;     // the converters' parameters as they were given (a snapshot's layout fingerprint covers them)
+    double rs_rolloff = 0., rs_beta = 0.;
     dfx_resampler *rs_up = nullptr, *rs_dn = nullptr;
     dfx_stream_resampler *up = nullptr, *dn = nullptr;
     float *stage_in = nullptr, *stage_out = nullptr;   // [B, nmax * hop] each
@@ -1242,6 +1244,7 @@ extern "C" int dfx_stream_set_sample_rate(dfx_stream_state *S, int sr, int lowpa
         DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream_set_sample_rate: device allocation failed");
     }
     S->sr = sr, S->hop_native = h;
+    S->rs_width = lowpass_filter_width, S->rs_method = method, S->rs_rolloff = rolloff, S->rs_beta = beta;
     return DFX_OK;
 }
 extern "C" int dfx_stream_sample_rate(const dfx_stream_state *S) { return S ? (S->sr ? S->sr : S->st->sr) : 0; }

@@ -49,6 +49,14 @@ takes int16 PCM and returns int16 (at any rate, 48 kHz included).  The output eq
 ``io.resample`` with each resampler fed its whole-frame delay of zeros first; together they add ``resample_delay`` samples at the caller's
 rate (34 at 16 kHz, 294 at 44.1 kHz with ``sinc_fast``) to the latency.  Rates at which the hop is no whole number of resampler frames
 (22.05 kHz, 11.025 kHz) are refused.
+
+``snap = rt.export_streams([17, 42])`` copies live streams out of a handle and ``other.import_streams([3, 4], snap)`` continues them in
+another one — to drain a handle, merge two, grow one (create a bigger handle, ``big.import_streams(range(n), rt.export_streams())``, drop
+the old one) or checkpoint calls.  A ``StreamSnapshot`` is two tensors: ``payload`` (uint8 ``[n, snapshot_bytes]`` on the device: every
+state row of the streams in a layout that does not depend on the handle) and ``meta`` (uint8 on the host: format version, a fingerprint of
+the kind of handle, the stream's age and settings); ``.cpu()`` / ``.to(device)`` move it, ``torch.save(snap.state_dict(), f)`` and
+``StreamSnapshot.from_state_dict(torch.load(f))`` take it through files and pipes.  The two handles must be of the same kind (model
+configuration, channels, gating, pausable, ``sr``; weights are not checked); streams, ``max_frames`` and hop count may differ.
 """
 from __future__ import annotations
 
@@ -60,6 +68,40 @@ import torch
 from . import _lib
 from .libdf import DF
 from .model import DfNet
+
+
+class StreamSnapshot:
+    """Streams taken out of a ``DfStream`` (``export_streams``): ``payload`` uint8 [n, bytes per stream] — position-independent bytes, on the
+    device they were exported on until moved — and ``meta`` uint8 [n, META_BYTES] on the host (one ``dfx_stream_meta`` per stream)."""
+    META_BYTES = 48
+
+    def __init__(self, payload: torch.Tensor, meta: torch.Tensor):
+        if payload.dtype != torch.uint8 or meta.dtype != torch.uint8 or payload.dim() != 2 or meta.dim() != 2:
+            raise TypeError("StreamSnapshot: payload and meta are 2-d uint8 tensors")
+        if meta.shape[1] != self.META_BYTES or meta.shape[0] != payload.shape[0]:
+            raise ValueError(f"StreamSnapshot: meta must be [{payload.shape[0]}, {self.META_BYTES}]")
+        self.payload, self.meta = payload, meta.to("cpu").contiguous()
+
+    def __len__(self) -> int:
+        return int(self.payload.shape[0])
+
+    @property
+    def ages(self) -> torch.Tensor:
+        """Hops of network time every stream had consumed when it was exported: int64 [n]."""
+        return self.meta[:, 16:24].contiguous().view(torch.int64).reshape(-1).clone()
+
+    def to(self, device) -> "StreamSnapshot":
+        return StreamSnapshot(self.payload.to(device), self.meta)
+
+    def cpu(self) -> "StreamSnapshot":
+        return self.to("cpu")
+
+    def state_dict(self) -> dict:
+        return {"payload": self.payload, "meta": self.meta}
+
+    @classmethod
+    def from_state_dict(cls, sd: dict) -> "StreamSnapshot":
+        return cls(sd["payload"], sd["meta"])
 
 
 class DfStream:
@@ -192,6 +234,44 @@ class DfStream:
             return
         ids = self._stream_ids(streams)
         _lib.check(_lib.lib().dfx_stream_reset_streams(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), _lib.stream()))
+
+    @property
+    def snapshot_bytes(self) -> int:
+        """Bytes of one stream's record in a ``StreamSnapshot`` of this handle."""
+        n = C.c_int64(0)
+        _lib.check(_lib.lib().dfx_stream_snapshot_bytes(self._h, C.byref(n)))
+        return int(n.value)
+
+    def export_streams(self, streams=None) -> "StreamSnapshot":
+        """A copy of the named streams' state (``None``: every stream, in order) as a ``StreamSnapshot`` on the device; the streams run on.
+        Does not wait for the device."""
+        ids = torch.arange(self.streams // self.channels, dtype=torch.int64) if streams is None else self._stream_ids(streams)
+        n = int(ids.numel())
+        payload = torch.empty((n, self.snapshot_bytes), dtype=torch.uint8, device=_lib.device())
+        meta = torch.zeros((n, StreamSnapshot.META_BYTES), dtype=torch.uint8)
+        _lib.check(_lib.lib().dfx_stream_export_streams(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), n, _lib.ptr(payload),
+                                                        C.c_void_p(meta.data_ptr()), _lib.stream()))
+        return StreamSnapshot(payload, meta)
+
+    def import_streams(self, streams, snap: "StreamSnapshot", settings: bool = True) -> None:
+        """The streams of ``snap`` continue in the slots ``streams`` of this handle (one index per snapshot entry, no index twice): the
+        slots are overwritten completely, every other stream is untouched, the streams keep their ages.  ``settings``: their attenuation
+        limit, post-filter beta and thresholds arrive too; ``False``: the slots keep their own.  The snapshot must come from the same kind
+        of handle (model configuration, channels, gating, pausable, ``sr``); the number of streams, ``max_frames`` and the hop count may
+        differ.  A handle in the undelayed pass-through (``set_atten_lim(0)``) neither exports nor imports.  A snapshot on the host is
+        copied to the device first; otherwise nothing waits."""
+        ids = self._stream_ids(streams)
+        n = int(ids.numel())
+        if not isinstance(snap, StreamSnapshot):
+            raise TypeError("import_streams needs a StreamSnapshot")
+        if len(snap) != n:
+            raise ValueError(f"{n} stream indices but {len(snap)} snapshot entries")
+        if snap.payload.shape[1] != self.snapshot_bytes:
+            raise ValueError(f"snapshot records have {snap.payload.shape[1]} bytes, this handle's have {self.snapshot_bytes}")
+        payload = snap.payload.to(_lib.device()).contiguous()
+        meta = snap.meta.to("cpu").contiguous()
+        _lib.check(_lib.lib().dfx_stream_import_streams(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), n, _lib.ptr(payload),
+                                                        C.c_void_p(meta.data_ptr()), int(bool(settings)), _lib.stream()))
 
     @property
     def frames(self) -> torch.Tensor:

@@ -435,6 +435,41 @@ int64_t dfx_stream_resample_delay(const dfx_stream_state *s);            /* samp
  * converted rate the conversions happen inside the two converter kernels; at the model's rate through dfx_pcm16_to_f32 / dfx_f32_to_pcm16. */
 int dfx_stream_process_pcm16(dfx_stream_state *s, const int16_t *x, int64_t n_frames, int16_t *y, float *lsnr, const unsigned char *active,
                              void *stream);
+/* Moving live streams between handles.  In the reference a caller's DfTract is a value the host owns; here a stream's state is its rows of
+ * the handle's device arrays, in forms that change with the handle and the moment.  A snapshot of a stream is
+ *   payload: one packed record of dfx_stream_snapshot_bytes() bytes in DEVICE memory — every state row of the stream's `channels` rows in a
+ *            canonical layout that does not depend on the handle: STFT memories, running means, the three windows oldest frame first, the GRU
+ *            rows, df_convp's pending sums in the stream's own order, the per-stream forms of gated / pausable handles, the sample-rate
+ *            converters' histories.  Position-independent bytes: copy them to the host, a file, another GPU or process.
+ *   meta:    this HOST struct, written by the export without asking the device.
+ * The fingerprint covers what decides the record's layout and meaning: the dfx_model_cfg, the dfx_state parameters, channels and mask
+ * reduction, gated / pausable / exact fp32 / run_df, the caller's rate with the resampler parameters, and the record size.  WEIGHTS ARE NOT
+ * FINGERPRINTED: importing into a handle of a model with the same configuration and other weights is accepted, and continues the stream
+ * with that model.  Source and destination may differ in the number of streams, max_frames, hop count and the form their windows are in.
+ * Export is a copy (the source stream runs on).  Import overwrites the named streams completely, as dfx_stream_reset_streams does, and
+ * leaves every other stream alone; the stream keeps its age (dfx_stream_frames), so its birth in the destination may lie before the
+ * handle's own start.  with_settings != 0: the stream's limit, beta and thresholds arrive too (as by dfx_stream_set_*_streams); 0: the
+ * destination slot keeps its own.  For H + L hops after an import a non-pausable destination runs the forms of a handle with a reset
+ * stream; past them the steady call enqueues what it did before.  An import ends the reset point of the handle (dfx_stream_set_pausable,
+ * dfx_stream_set_sample_rate).  Both calls are enqueued on `stream`: ids and ages travel as kernel arguments, 192 streams per launch,
+ * nothing is uploaded and nothing waits; the payload must stay valid until the work on `stream` has passed it.
+ * Refused with no state changed (DFX_ERR_INVALID_ARG / DFX_ERR_UNSUPPORTED; dfx_last_error names the first mismatch): null pointers, ids out
+ * of range, duplicate destination ids, a magic, version or fingerprint mismatch, and — the one excluded mode — a handle in the handle-wide
+ * undelayed pass-through (dfx_stream_set_atten_lim |dB| < 0.01), for both calls. */
+#define DFX_STREAM_META_MAGIC 0x53584644u /* "DFXS" */
+#define DFX_STREAM_META_VERSION 1u
+typedef struct dfx_stream_meta {
+    uint32_t magic, version;
+    uint64_t fingerprint;
+    int64_t age;             /* hops of network time the stream has consumed (dfx_stream_frames) */
+    float settings[5];       /* as dfx_stream_get_settings reports them: |lim dB|, beta, min_db, max_db_erb, max_db_df */
+    int32_t pending_current; /* the ungated pending sums in the record are current (0: the destination rebuilds them) */
+} dfx_stream_meta;
+int dfx_stream_snapshot_bytes(const dfx_stream_state *s, int64_t *bytes_per_stream);
+int dfx_stream_export_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, void *payload_dev /*[count][bytes_per_stream]*/,
+                              dfx_stream_meta *meta_host /*[count]*/, void *stream);
+int dfx_stream_import_streams(dfx_stream_state *s, const int64_t *ids, int64_t count, const void *payload_dev,
+                              const dfx_stream_meta *meta_host, int with_settings, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Multi-frame Wiener / MVDR filters: df.multiframe.MfWf.forward (multiframe.py:282-321) and MfMvdr.forward (:373-413), the filter

@@ -2,7 +2,7 @@
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
     python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact] [--paused FRACTION]
-                                  [--per-stream-settings] [--sr 16000] [--pcm16]
+                                  [--per-stream-settings] [--sr 16000] [--pcm16] [--move]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
@@ -12,6 +12,11 @@ the pool (0: a pausable handle on which nobody pauses).
 (DfStream.set_*(..., streams=ids)); the JSON line also carries the host time of one setter call over all ids (setter_host_ms).
 --sr RATE: the handle takes and returns hops at RATE (DfStream(sr=RATE): an up-sampler in front of the 48 kHz pass, a down-sampler behind it);
 --pcm16: the hops are int16 PCM in both directions.  The JSON line carries both; without them the call is the plain 48 kHz float one.
+--move: after the steady hops, 256 streams and then all of them are exported from the handle and imported into a second one of the same size
+(DfStream.export_streams / import_streams); a further JSON line carries the device time of each (hipEvents on the caller's stream, median of
+5), the record size and the bytes/s they reach against the 8 TB/s HBM peak, next to the steady hop time of the same run.  Each is timed twice:
+into an empty queue (`*_ms`: what a caller that waits sees, host enqueue of the launches included) and behind a queued hop of the other handle's
+size (`*_queued_ms`: the launches are already enqueued when the device reaches them — the device time of the copy kernels alone).
 --exact: the model is created under DFX_EXACT_FP32=1 (every contraction in fp32: the one-hop GRU layers on dfx_k_gru_step_x32).
 
 Prints one JSON line per frames-per-call setting: hops/s over all streams, ms per call, and the number of real-time 48 kHz streams
@@ -43,6 +48,7 @@ def main() -> None:
                     help="a distinct attenuation limit and post-filter beta per stream (with --gating also thresholds), set per stream")
     ap.add_argument("--sr", type=int, default=None, help="the callers' sample rate (hops of hop * sr / 48000 samples; default: the model's 48 kHz)")
     ap.add_argument("--pcm16", action="store_true", help="int16 PCM hops in and out")
+    ap.add_argument("--move", action="store_true", help="also time export_streams / import_streams of 256 and of all streams into a second handle")
     ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
     if args.exact:
@@ -128,6 +134,44 @@ def main() -> None:
                           "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms, "sr": rt.sr, "pcm16": bool(args.pcm16),
                           "resample_delay_ms": rt.resample_delay / rt.sr * 1e3,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
+        if args.move:
+            other = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr)
+            other.process(x)
+            rec = rt.snapshot_bytes
+            move = {"metric": "moving streams between handles", "streams": args.streams, "frames_per_call": n, "model": args.model, "record_bytes": rec,
+                    "steady_ms_per_call": ms_call, "hbm_peak_bytes_per_s": 8e12}
+
+            def dev_ms(fn, behind=None):   # median of 5, hipEvents on the caller's stream; behind: a handle whose hop is enqueued first
+                times = []
+                for _ in range(5):
+                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    if behind is not None:
+                        behind.process(x)
+                    e0.record()
+                    r = fn()
+                    e1.record()
+                    e1.synchronize()
+                    times.append(e0.elapsed_time(e1))
+                return sorted(times)[2], r
+
+            for count in sorted({min(256, args.streams), args.streams}):
+                ids = torch.arange(count)
+                ex_ms, snap = dev_ms(lambda: rt.export_streams(ids))
+                im_ms, _ = dev_ms(lambda: other.import_streams(ids, snap, settings=False))
+                exq_ms, _ = dev_ms(lambda: rt.export_streams(ids), behind=other)
+                imq_ms, _ = dev_ms(lambda: other.import_streams(ids, snap, settings=False), behind=rt)
+                move[f"export_{count}_queued_ms"], move[f"import_{count}_queued_ms"] = exq_ms, imq_ms
+                move[f"export_{count}_queued_bytes_per_s"], move[f"import_{count}_queued_bytes_per_s"] = 2 * count * rec / (exq_ms * 1e-3), 2 * count * rec / (imq_ms * 1e-3)
+                # a record is read once and written once in either direction
+                move[f"export_{count}_ms"], move[f"import_{count}_ms"] = ex_ms, im_ms
+                move[f"export_{count}_bytes_per_s"], move[f"import_{count}_bytes_per_s"] = 2 * count * rec / (ex_ms * 1e-3), 2 * count * rec / (im_ms * 1e-3)
+                del snap
+            y = other.process(x)
+            torch.cuda.synchronize()
+            assert args.pcm16 or torch.isfinite(y).all()
+            print(json.dumps(move), flush=True)
+            del other
         del rt
 
 
