@@ -559,6 +559,7 @@ struct dfx_model {
         bool seq_trace = false;         // DFX_SEQ_TRACE=1 (dev aid): d_trace below
         char hwq_probe_mode = 0;        // DFX_HWQ_PROBE: '0' no handshake, 'f' ("fail") a failed one, 0 the handshake before the first pass that needs it
         bool erb_enc_split = false;     // DFX_ERB_ENC_SPLIT=1 (test hook): batch passes run the ERB encoder as three launches (dfx_k_erb_enc, dfx_k_pwconv_f x 2) instead of dfx_k_erb_enc4
+        int ws_fill = -1;               // DFX_WS_FILL=0..255 (test hook): every pass starts by setting the bytes of its workspace layout to this value (dfx_ws_fill); -1: no fill
     } sw;
     // Error words, written by kernels, read by the host (page-locked host memory the device can store to: dfx_env_err_words_alloc):
     // [0] unused, [1] fp16-split range, [2] a flag wait of the persistent GRU phase timed out.
@@ -1237,6 +1238,8 @@ static void read_switches(dfx_model *m) {
         if (atoll(v) > 0) m->sw.convp_elems = atoll(v);
     m->sw.erb_enc_split = is("DFX_ERB_ENC_SPLIT", '1');   // test hook: the three-launch form of the ERB encoder in batch passes
     m->sw.c0_presplit = !is("DFX_C0_PRESPLIT", '0');      // test hook: the c0 kernels of batch passes split their feat_spec patches themselves
+    if (const char *v = getenv("DFX_WS_FILL"))              // test hook: a pass may not depend on what its workspace held (tests/test_scratch_contents.py)
+        if (v[0] >= '0' && v[0] <= '9' && atoi(v) <= 255) m->sw.ws_fill = atoi(v);
 #ifdef DFX_DEV
     // dev A/Bs of the phase's side work (product builds have no such switches)
     if (getenv("DFX_TAIL_SPLIT")) m->sw.tail_split = !is("DFX_TAIL_SPLIT", '0');

@@ -174,6 +174,7 @@ static int enhance_any(const dfx_model *m, const dfx_state *st, const float *x, 
     }
     if (int rc = pass_begin(m, B * Tf)) return rc;
     DfxTurn turn(m, s, true);
+    if (int rc = dfx_ws_fill(m, workspace, need, s)) return rc;   // (the row metadata of a varlen call and every chunk's layout)
     int64_t *meta = nullptr;
     bool short_out = false;
     if (lens) {

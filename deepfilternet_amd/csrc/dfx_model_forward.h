@@ -1060,6 +1060,18 @@ static int pass_end(const dfx_model *m, int64_t frames, hipStream_t s) {
     return DFX_OK;
 }
 
+// DFX_WS_FILL (test hook): the bytes a pass's workspace layout covers take the given value, on the pass's own stream and before the pass enqueues
+// or forks anything.  Unset (ws_fill < 0): nothing happens.  The flags and progress words of the GRU phase live in d_sync / d_psync, which the
+// handle owns: the fill cannot reach them.
+// The callers pass the workspace pointer as they were given it and the `need` they check its size against.  The layout itself starts at that pointer
+// rounded up to 256 bytes (dfx_ws_base; `base` in enhance_any) and every `need` ends in 256 bytes of slack for that rounding, so the layout
+// ends at or before workspace + need - 1 for any alignment of the caller's pointer: [workspace, workspace + need) covers it, and is what the caller owns.
+static int dfx_ws_fill(const dfx_model *m, void *workspace, int64_t bytes, hipStream_t s) {
+    if (m->sw.ws_fill < 0 || !workspace || bytes <= 0) return DFX_OK;
+    DFX_HIP(hipMemsetAsync(workspace, m->sw.ws_fill, (size_t)bytes, s));
+    return DFX_OK;
+}
+
 extern "C" int dfx_model_forward(const dfx_model *m, const dfx_bands *bands, const float *spec, const float *feat_erb,
                                  const float *feat_spec, int64_t B, int64_t T, float atten_lim, float *spec_e,
                                  float *mask, float *lsnr, float *df_coefs, void *workspace, int64_t workspace_bytes,
@@ -1067,6 +1079,12 @@ extern "C" int dfx_model_forward(const dfx_model *m, const dfx_bands *bands, con
     if (!m) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_model_forward: bad arguments");
     if (int rc = pass_begin(m, B * T)) return rc;
     DfxTurn turn(m, dfx_stream(stream), true);
+    if (m->sw.ws_fill >= 0 && B > 0 && T > 0) {
+        int64_t need = 0;
+        dfx_model_workspace_bytes(m, B, T, &need);
+        if (workspace_bytes >= need)   // (a smaller one is refused below)
+            if (int rc = dfx_ws_fill(m, workspace, need, dfx_stream(stream))) return rc;
+    }
     if (int rc = model_forward_lane(m, bands, spec, feat_erb, feat_spec, B, T, atten_lim, spec_e, mask, lsnr, df_coefs, workspace,
                                     workspace_bytes, stream, &m->lanes[0], false))
         return rc;

@@ -1186,6 +1186,7 @@ static int stream_body(dfx_stream_state *S, const float *x, int64_t n, float *y,
                        bool p_mixed, bool p_warm) {
     DfxStreamPass p{S, x, n, y, lsnr_out, s, xs, ys, ls, p_mixed, p_warm, S->m->cfg};
     int rc;
+    if ((rc = dfx_ws_fill(S->m, S->buf + S->model_ws, S->model_ws_bytes, s))) return rc;
     if ((rc = p.plan()) || (rc = p.open_gate())) return rc;
     if (p.bypass) return p.pass_through();
     if ((rc = p.features())) return rc;
@@ -1384,6 +1385,7 @@ extern "C" int dfx_stream_process_raw(dfx_stream_state *S, const float *spec, fl
     DfxTurn turn(S->m, s, false);   // (the enqueue lock)
     S->fresh = false;
     const dfx_model *m = S->m;
+    if (int rc = dfx_ws_fill(m, S->buf + S->model_ws, S->model_ws_bytes, s)) return rc;
     const dfx_state *st = S->st;
     const dfx_model_cfg &c = m->cfg;
     const int64_t B = S->B, H = S->H, L = S->L, Hs = H + L, F = st->N / 2 + 1, E = c.nb_erb, Fd = c.nb_df;

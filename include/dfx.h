@@ -255,7 +255,9 @@ int dfx_model_check(const dfx_model *m);
 #define DFX_PLAN_FUSE_DEC (1 << 15)   /* frame-resident last two ERB decoder layers (dfx_k_erb_dec10 / inside dfx_k_erb_tail) */
 int dfx_model_query(const dfx_model *m, int what, int64_t *value);
 
-/* Scratch memory the caller must provide (device bytes) for a [B, T-frames] batch. */
+/* Scratch memory the caller must provide (device bytes) for a [B, T-frames] batch.  What a workspace — this one, dfx_enhance's, dfx_enhance_varlen's —
+ * holds when a pass starts is irrelevant (no pass reads what it has not written, nothing is carried from pass to pass in it), and what it holds
+ * when the pass is through is unspecified. */
 int dfx_model_workspace_bytes(const dfx_model *m, int64_t B, int64_t T, int64_t *bytes);
 
 /* DfNet.forward (deepfilternet3.py:389-456).
