@@ -100,7 +100,9 @@ SIGNATURES = {
     "dfx_mf_filter": (_i, [_fp, _fp, _fp, _i, _i, _i, _i, _i, _i, _f, _f, _i64, _i64, _i, _i, _fp, _vp]),
     "dfx_pcm16_to_f32": (_i, [_vp, _i64, _fp, _vp]),
     "dfx_f32_to_pcm16": (_i, [_fp, _i64, _vp, _vp]),
-    "dfx_resampler_create": (_i, [_i, _i, _i, C.c_double, _i, C.c_double, C.POINTER(_vp)]),
+    "dfx_g711_decode": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
+    "dfx_g711_encode": (_i, [_vp, _i, _i, _i64, _vp, _vp]),
+    "dfx_resampler_create": (_i,[_i, _i, _i, C.c_double, _i, C.c_double, C.POINTER(_vp)]),
     "dfx_resampler_free": (None, [_vp]),
     "dfx_resampler_out_len": (_i64, [_vp, _i64]),
     "dfx_resampler_kernel": (_i, [_i, _i, _i, C.c_double, _i, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _f32p, _i64]),
@@ -129,6 +131,7 @@ SIGNATURES = {
     "dfx_stream_sample_rate": (_i, [_vp]),
     "dfx_stream_resample_delay": (_i64, [_vp]),
     "dfx_stream_process_pcm16": (_i, [_vp, _vp, _i64, _vp, _fp, _vp, _vp]),
+    "dfx_stream_process_g711": (_i, [_vp, _vp, _i, _i64, _vp, _fp, _vp, _vp]),
     "dfx_stream_snapshot_bytes": (_i, [_vp, C.POINTER(_i64)]),
     "dfx_stream_export_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _vp]),
     "dfx_stream_import_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _i, _vp]),

@@ -28,7 +28,7 @@ struct DfxRsStepArgs {
     int frames, orig, nw, nw_pad, K, hist;
     int mt, rg, seg;                             // frames per tile (blockIdx.y), rows per workgroup, window floats per row in LDS
     int fw, jw;                                  // the workgroup's 4 waves: fw groups of 64 (row, frame) slots x jw groups of phase tiles
-    int x_i16, y_i16, masked;
+    int x_fmt, y_fmt, masked;                    // DFX_FMT_* of x and y
 };
 
 struct dfx_stream_resampler {
@@ -39,8 +39,13 @@ struct dfx_stream_resampler {
     int cur = 0;
 };
 
-static __device__ __forceinline__ float dfx_rs_load(const void *x, int x_i16, int64_t i) {
-    return x_i16 ? (float)static_cast<const int16_t *>(x)[i] * (1.0f / 32768.0f) : static_cast<const float *>(x)[i];
+// G711: the instance that also knows the two G.711 formats (a call with codes on either side); float32 / int16 calls run the instance without them
+template <bool G711>
+static __device__ __forceinline__ float dfx_rs_load(const void *x, int fmt, int64_t i) {
+    if (!G711) return fmt ? (float)static_cast<const int16_t *>(x)[i] * (1.0f / 32768.0f) : static_cast<const float *>(x)[i];
+    if (fmt == DFX_FMT_F32) return static_cast<const float *>(x)[i];
+    if (fmt == DFX_FMT_PCM16) return (float)static_cast<const int16_t *>(x)[i] * (1.0f / 32768.0f);
+    return (float)dfx_g711_to_s16(static_cast<const uint8_t *>(x)[i], fmt - DFX_FMT_ULAW + DFX_G711_ULAW) * (1.0f / 32768.0f);
 }
 
 // Workgroup (g, t, z): rows [row0 + g rg, + rg) x frames [t mt, + mt); z splits the phase tiles further when the rows alone give the chip too few
@@ -50,8 +55,9 @@ static __device__ __forceinline__ float dfx_rs_load(const void *x, int x_i16, in
 // between the frames of a row: 4 LDS reads per 4 JT FMAs.  Every accumulator is one fmaf chain over k = 0 .. K-1 (four taps per iteration,
 // then the K % 4 last ones singly: no padded tap is ever multiplied with a sample outside the frame's window).  JT = 16, or 4 where the bank
 // has at most 4 phases (the down-samplers to 8 / 16 kHz have one).  Tile (t = 0, z = 0) also writes the rows' new history (an inactive row's:
-// a copy of the old one).
-template <int JT>
+// a copy of the old one).  x and y are converted from and to their sample formats (DFX_FMT_*) in the loads and stores; the two G.711 forms live in
+// an instance of their own (G711), so that the float32 / int16 instance keeps its registers.
+template <int JT, bool G711>
 __global__ void __launch_bounds__(256) dfx_k_resample_step(const void *__restrict__ x, void *__restrict__ y, const float *__restrict__ wt,
                                                            const float *__restrict__ hist_in, float *__restrict__ hist_out, DfxRsStepArgs A,
                                                            DfxRsMask M) {
@@ -73,7 +79,7 @@ __global__ void __launch_bounds__(256) dfx_k_resample_step(const void *__restric
         at = r * A.seg + i;
         if (A.masked && ((M.bits[mk >> 5] >> (mk & 31)) & 1u)) return 0.f;
         const int w = f0 * A.orig + i;   // index into [history | new input]
-        return w < A.hist ? hist_in[row * A.hist + w] : dfx_rs_load(x, A.x_i16, row * A.x_stride - A.hist + w);
+        return w < A.hist ? hist_in[row * A.hist + w] : dfx_rs_load<G711>(x, A.x_fmt, row * A.x_stride - A.hist + w);
     };
     for (int i0 = tid; i0 < total; i0 += 8 * 256) {
         float v[8];
@@ -95,7 +101,7 @@ __global__ void __launch_bounds__(256) dfx_k_resample_step(const void *__restric
             const int mk = (int)(row - A.row0);
             const bool off = A.masked && ((M.bits[mk >> 5] >> (mk & 31)) & 1u);
             const float *hr = hist_in + row * A.hist;
-            hist_out[row * A.hist + i] = off ? hr[i] : (w < A.hist ? hr[w] : dfx_rs_load(x, A.x_i16, row * A.x_stride - A.hist + w));
+            hist_out[row * A.hist + i] = off ? hr[i] : (w < A.hist ? hr[w] : dfx_rs_load<G711>(x, A.x_fmt, row * A.x_stride - A.hist + w));
         }
     __syncthreads();
     const int wave = tid >> 6, lane = tid & 63;
@@ -137,12 +143,14 @@ __global__ void __launch_bounds__(256) dfx_k_resample_step(const void *__restric
 #pragma unroll
         for (int i = 0; i < JT; ++i) {
             if (j0 + i >= A.nw) continue;
-            if (A.y_i16) {   // dfx_k_f32_to_pcm16's encoding
+            if (G711 ? A.y_fmt == DFX_FMT_PCM16 : A.y_fmt != DFX_FMT_F32) {   // dfx_k_f32_to_pcm16's encoding
                 float v = acc[i] * 32768.0f;
                 v = v != v ? 0.f : fminf(fmaxf(v, -9.0e18f), 9.0e18f);
                 static_cast<int16_t *>(y)[yo + j0 + i] = (int16_t)(uint16_t)(uint64_t)(int64_t)v;
-            } else {
+            } else if (!G711 || A.y_fmt == DFX_FMT_F32) {
                 static_cast<float *>(y)[yo + j0 + i] = acc[i];
+            } else {   // G.711: the saturating rule (dfx_g711.h); an inactive row's exact zeros come out as the law's silence code
+                static_cast<uint8_t *>(y)[yo + j0 + i] = (uint8_t)dfx_s16_to_g711(dfx_f32_to_s16_sat(acc[i]), A.y_fmt - DFX_FMT_ULAW + DFX_G711_ULAW);
             }
         }
     }
@@ -224,9 +232,11 @@ void dfx_stream_resampler_rows(const dfx_stream_resampler *h, float **cur, float
     *cur = h->d_hist[h->cur], *other = h->d_hist[h->cur ^ 1], *hist = h->hist;
 }
 
-extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_is_pcm16, int64_t in_len, int64_t x_stride, void *y,
-                                            int y_is_pcm16, int64_t y_stride, const unsigned char *active_host, void *stream) {
+extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_format, int64_t in_len, int64_t x_stride, void *y,
+                                            int y_format, int64_t y_stride, const unsigned char *active_host, void *stream) {
     if (!h) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_resampler_process: null handle");
+    if (x_format < DFX_FMT_F32 || x_format > DFX_FMT_ALAW || y_format < DFX_FMT_F32 || y_format > DFX_FMT_ALAW)
+        DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_resampler_process: sample formats %d, %d (DFX_FMT_F32 .. DFX_FMT_ALAW)", x_format, y_format);
     const dfx_resampler *r = h->r;
     if (in_len < 0 || in_len % r->orig)
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_resampler_process: %lld input samples are not a multiple of the block (%d)", (long long)in_len, r->orig);
@@ -241,7 +251,7 @@ extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void 
     DfxRsStepArgs A;
     A.x_stride = x_stride, A.y_stride = y_stride;
     A.frames = (int)frames, A.orig = r->orig, A.nw = r->nw, A.nw_pad = r->nw_pad, A.K = r->K, A.hist = h->hist;
-    A.x_i16 = x_is_pcm16 != 0, A.y_i16 = y_is_pcm16 != 0, A.masked = active_host != nullptr;
+    A.x_fmt = x_format, A.y_fmt = y_format, A.masked = active_host != nullptr;
     // The 4 waves: jw of them split the phase tiles (as many as there are tiles: 1 / 2 / 4), fw = 4 / jw own 64 (row, frame) slots each.  A
     // workgroup takes up to 64 fw frames of a row (as many as the window has room for) and, where a call has fewer, as many rows as fill its
     // slots; nz: the phase tiles go over that many workgroups more when the rows give the chip fewer than ~1024 of them.
@@ -261,6 +271,7 @@ extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void 
     if (tiles > 65535) DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_resampler_process: call too long");
     const int64_t wgs = dfx_ceil_div(h->rows, A.rg) * tiles, zmax = dfx_ceil_div(ntiles, A.jw), zwant = dfx_ceil_div(1024, wgs);
     const unsigned nz = (unsigned)(zwant < zmax ? zwant : zmax);
+    const bool g711 = x_format >= DFX_FMT_ULAW || y_format >= DFX_FMT_ULAW;
     hipStream_t s = dfx_stream(stream);
     DfxKScope ks(DFX_K_RESAMPLE, s);
     DfxRsMask M;
@@ -274,11 +285,17 @@ extern "C" int dfx_stream_resampler_process(dfx_stream_resampler *h, const void 
                 if (!active_host[k]) M.bits[(k - row0) >> 5] |= 1u << ((k - row0) & 31);
         }
         const dim3 grid((unsigned)dfx_ceil_div(A.row_end - row0, A.rg), tiles, nz);
-        if (jt == 4)
-            dfx_launch(dfx_k_resample_step<4>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
+        if (jt == 4 && g711)
+            dfx_launch(dfx_k_resample_step<4, true>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
+                       (const float *)h->d_hist[h->cur], h->d_hist[h->cur ^ 1], A, M);
+        else if (g711)
+            dfx_launch(dfx_k_resample_step<DFX_RS_JT, true>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
+                       (const float *)h->d_hist[h->cur], h->d_hist[h->cur ^ 1], A, M);
+        else if (jt == 4)
+            dfx_launch(dfx_k_resample_step<4, false>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
                        (const float *)h->d_hist[h->cur], h->d_hist[h->cur ^ 1], A, M);
         else
-            dfx_launch(dfx_k_resample_step<DFX_RS_JT>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
+            dfx_launch(dfx_k_resample_step<DFX_RS_JT, false>, grid, dim3(256), smem, s, (const void *)x, y, (const float *)r->d_wt,
                        (const float *)h->d_hist[h->cur], h->d_hist[h->cur ^ 1], A, M);
         DFX_LAUNCH_CHECK();
     }

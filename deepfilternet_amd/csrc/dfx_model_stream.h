@@ -248,7 +248,7 @@ struct dfx_stream_state {
     size_t sb_lim = 0, sb_beta = 0, sb_thr = 0;
     // Streaming at the caller's rate (dfx_stream_set_sample_rate): an up-sampler sr -> model rate in front of the pass and a down-sampler
     // behind it, both over all rows and in step form (dfx_stream_resampler_*: csrc/dfx_io_stream.h), around model-rate staging rows
-    // [B, nmax * hop].  sr == 0: no rate set — a call takes today's path (the staging rows then serve dfx_stream_process_pcm16 alone).
+    // [B, nmax * hop].  sr == 0: no rate set — a call takes today's path (the staging rows then serve dfx_stream_process_pcm16 / _g711 alone).
     int sr = 0;
     int64_t hop_native = 0;
     int rs_width = 0, rs_method = 0;     // the converters' parameters as they were given (a snapshot's layout fingerprint covers them)
@@ -1202,7 +1202,7 @@ static int stream_call_end(const dfx_model *m, hipStream_t s) {
     return model_poll(m);
 }
 static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, hipStream_t s);
-// ---- streaming at the caller's rate, and on 16-bit PCM ---------------------------------------------------------------------------------
+// ---- streaming at the caller's rate, on 16-bit PCM and on G.711 codes ------------------------------------------------------------------
 static int stream_stage_alloc(dfx_stream_state *S) {   // the model-rate staging rows [B, nmax * hop]
     if (S->stage_in) return DFX_OK;
     const size_t bytes = (size_t)S->B * S->nmax * S->st->hop * 4;
@@ -1257,40 +1257,52 @@ extern "C" int64_t dfx_stream_resample_delay(const dfx_stream_state *S) {
     return pu + pd;
 }
 
-// The pass between the converters (a rate is set) or between the PCM kernels (16-bit PCM at the model's rate): x -> stage_in -> the
-// model-rate pass, unchanged -> stage_out -> y, all on the caller's stream.
-static int stream_process_staged(dfx_stream_state *S, const void *x, int64_t n, void *y, bool pcm16, float *lsnr_out, hipStream_t s) {
+// The pass between the converters (a rate is set) or between the PCM / G.711 kernels (16-bit PCM or codes at the model's rate): x -> stage_in
+// -> the model-rate pass, unchanged -> stage_out -> y, all on the caller's stream.  fmt: the DFX_FMT_* of x and y, a property of the call.
+static int stream_process_staged(dfx_stream_state *S, const void *x, int64_t n, void *y, int fmt, float *lsnr_out, hipStream_t s) {
     const int64_t B = S->B, T = n * S->st->hop;
+    const bool g711 = fmt == DFX_FMT_ULAW || fmt == DFX_FMT_ALAW;
+    const int law = fmt - DFX_FMT_ULAW + DFX_G711_ULAW;                   // (of a G.711 call)
+    const size_t sample = fmt == DFX_FMT_F32 ? 4 : (fmt == DFX_FMT_PCM16 ? 2 : 1);
+    const int quiet = g711 ? (law == DFX_G711_ULAW ? 0xFF : 0xD5) : 0;             // the byte a row of silence is filled with
+    // (the handle-wide pass-through: the model-rate pass hands stage_in through and moves its STFT memory)
+    const bool thru = S->lim == 1.f;
     int rc;
-    if (!S->sr) {
-        if ((rc = dfx_pcm16_to_f32(static_cast<const int16_t *>(x), B * T, S->stage_in, s))) return rc;
-        if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
-        return dfx_f32_to_pcm16(S->stage_out, B * T, static_cast<int16_t *>(y), s);
-    }
-    const int64_t Tn = n * S->hop_native;
     const unsigned char *act = nullptr;
-    if (S->any_paused) {   // a paused stream's rows sit both converters out
+    if (S->any_paused && (S->sr || (g711 && thru))) {   // a paused stream's rows sit both converters out
         const int ch = S->channels;
         S->row_active.resize((size_t)B);
         for (int64_t r = 0; r < B; ++r) S->row_active[(size_t)r] = !S->paused[(size_t)(r / ch)];
         act = S->row_active.data();
     }
-    // (the handle-wide pass-through: the model-rate pass hands stage_in through and moves its STFT memory; the down-sampler's history follows
-    // those rows, its output is dropped and the caller gets its own samples back)
-    const bool thru = S->lim == 1.f;
-    if ((rc = dfx_stream_resampler_process(S->up, x, pcm16, Tn, Tn, S->stage_in, 0, T, act, s))) return rc;
-    if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
-    if ((rc = dfx_stream_resampler_process(S->dn, S->stage_out, 0, T, T, thru ? S->thru_tmp : y, thru ? 0 : pcm16, Tn, act, s))) return rc;
-    if (thru) {
-        const size_t row = (size_t)Tn * (pcm16 ? 2 : 4);
+    // the caller's own samples back, as they came (G.711: the bytes, not a re-encoding — 0x7F stays 0x7F); a paused stream's rows: silence
+    auto hand_back = [&](size_t row) -> int {
         DFX_HIP(hipMemcpyAsync(y, x, (size_t)B * row, hipMemcpyDeviceToDevice, s));
         for (int64_t r = 0; act && r < B; ++r)
-            if (!act[r]) DFX_HIP(hipMemsetAsync(static_cast<unsigned char *>(y) + (size_t)r * row, 0, row, s));
+            if (!act[r]) DFX_HIP(hipMemsetAsync(static_cast<unsigned char *>(y) + (size_t)r * row, quiet, row, s));
+        return DFX_OK;
+    };
+    if (!S->sr) {
+        if (g711) {
+            if ((rc = dfx_g711_decode(static_cast<const uint8_t *>(x), law, B * T, S->stage_in, 0, s))) return rc;
+            if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
+            if (thru) return hand_back((size_t)T);
+            return dfx_g711_encode(S->stage_out, 0, law, B * T, static_cast<uint8_t *>(y), s);
+        }
+        if ((rc = dfx_pcm16_to_f32(static_cast<const int16_t *>(x), B * T, S->stage_in, s))) return rc;
+        if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
+        return dfx_f32_to_pcm16(S->stage_out, B * T, static_cast<int16_t *>(y), s);
     }
+    const int64_t Tn = n * S->hop_native;
+    // (in the pass-through the down-sampler's history follows the model-rate rows, its output is dropped and the caller gets its own samples back)
+    if ((rc = dfx_stream_resampler_process(S->up, x, fmt, Tn, Tn, S->stage_in, DFX_FMT_F32, T, act, s))) return rc;
+    if ((rc = stream_process_impl(S, S->stage_in, n, S->stage_out, lsnr_out, s))) return rc;
+    if ((rc = dfx_stream_resampler_process(S->dn, S->stage_out, DFX_FMT_F32, T, T, thru ? S->thru_tmp : y, thru ? DFX_FMT_F32 : fmt, Tn, act, s))) return rc;
+    if (thru) return hand_back((size_t)Tn * sample);
     return DFX_OK;
 }
 
-static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, void *y, bool pcm16, float *lsnr_out, const unsigned char *active,
+static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, void *y, int fmt, float *lsnr_out, const unsigned char *active,
                               void *stream) {
     if (!S || n <= 0 || n > S->nmax || !x || !y) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process: bad arguments (1 <= n_frames <= max_frames)");
     if (active && !S->pausable) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_active: a mask needs a pausable handle (dfx_stream_set_pausable)");
@@ -1304,13 +1316,13 @@ static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, voi
         for (size_t k = 0; active && k < ns; ++k)
             if (!active[k]) S->paused[k] = 1, S->any_paused = true;
     }
-    const bool staged = S->sr != 0 || pcm16;
+    const bool staged = S->sr != 0 || fmt != DFX_FMT_F32;
     if (staged)
         if (int rc = stream_stage_alloc(S)) return rc;
     {
         DfxTurn turn(S->m, s, false);   // (the enqueue lock only: a hop starts no persistent phase)
         S->fresh = false;
-        if (int rc = staged ? stream_process_staged(S, x, n, y, pcm16, lsnr_out, s)
+        if (int rc = staged ? stream_process_staged(S, x, n, y, fmt, lsnr_out, s)
                             : stream_process_impl(S, static_cast<const float *>(x), n, static_cast<float *>(y), lsnr_out, s))
             return rc;
     }
@@ -1318,14 +1330,19 @@ static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, voi
 }
 extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, const unsigned char *active,
                                          void *stream) {
-    return stream_process_any(S, x, n, y, false, lsnr_out, active, stream);
+    return stream_process_any(S, x, n, y, DFX_FMT_F32, lsnr_out, active, stream);
 }
 extern "C" int dfx_stream_process(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, void *stream) {
-    return stream_process_any(S, x, n, y, false, lsnr_out, nullptr, stream);
+    return stream_process_any(S, x, n, y, DFX_FMT_F32, lsnr_out, nullptr, stream);
 }
 extern "C" int dfx_stream_process_pcm16(dfx_stream_state *S, const int16_t *x, int64_t n, int16_t *y, float *lsnr_out, const unsigned char *active,
                                         void *stream) {
-    return stream_process_any(S, x, n, y, true, lsnr_out, active, stream);
+    return stream_process_any(S, x, n, y, DFX_FMT_PCM16, lsnr_out, active, stream);
+}
+extern "C" int dfx_stream_process_g711(dfx_stream_state *S, const uint8_t *x, int law, int64_t n, uint8_t *y, float *lsnr_out, const unsigned char *active,
+                                       void *stream) {
+    if (law != DFX_G711_ULAW && law != DFX_G711_ALAW) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_g711: law %d (DFX_G711_ULAW or DFX_G711_ALAW)", law);
+    return stream_process_any(S, x, n, y, law - DFX_G711_ULAW + DFX_FMT_ULAW, lsnr_out, active, stream);
 }
 // A call of n hops as passes.  A hop is passed on its own while the handle keeps per-stream forms (gated, pausable: the stage decisions of
 // hop i shape the state hop i+1 starts from) or sits inside the warm-up of a stream that started over on its own

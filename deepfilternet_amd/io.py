@@ -1,7 +1,7 @@
 """Host-side mirror of ``df/io.py`` (load_audio :25-57, save_audio :60-84, get_resample_params :92-111, resample :114-116) with
 the sample work on the MI355X: the file is parsed on the host (a RIFF/WAVE reader / writer of its own, below — the reference goes
-through torchaudio, which is not a dependency here; 8 / 16 / 24 / 32-bit integer PCM and 32 / 64-bit IEEE float, plain or
-WAVE_FORMAT_EXTENSIBLE), the int16 -> float scaling, the sample-rate conversion and the float -> int16 encoding run as HIP kernels
+through torchaudio, which is not a dependency here; 8 / 16 / 24 / 32-bit integer PCM, 32 / 64-bit IEEE float and 8-bit G.711 A-law /
+mu-law, plain or WAVE_FORMAT_EXTENSIBLE), the int16 -> float scaling, the G.711 codec, the sample-rate conversion and the float -> int16 encoding run as HIP kernels
 (csrc/dfx_io.hip), so a file -> file loop like ``enhance.main`` (enhance.py:73-89) keeps its audio on the device between decode and
 encode (the rarer sample formats are scaled with torch ops on the device):
 
@@ -144,10 +144,12 @@ class StreamResampler:
         ids = ids.to("cpu", torch.int64).contiguous()
         _lib.check(_lib.lib().dfx_stream_resampler_reset(self._h, C.cast(ids.data_ptr(), C.POINTER(C.c_int64)), int(ids.numel()), _lib.stream()))
 
-    def process(self, x: torch.Tensor, active=None) -> torch.Tensor:
+    def process(self, x: torch.Tensor, active=None, law: Optional[str] = None) -> torch.Tensor:
+        """``x`` float32, int16 PCM, or uint8 G.711 codes of ``law`` ("ulaw" / "alaw": decoded in the kernel's loads, the output encoded
+        in its stores with ``float_to_g711``'s saturating rule; an inactive row comes back as the law's silence code)."""
         src_dev = x.device
-        pcm16 = x.dtype == torch.int16
-        x = x.to(_lib.device(), torch.int16 if pcm16 else torch.float32).contiguous()
+        fmt = _sample_format(x, law, "StreamResampler.process")
+        x = x.to(_lib.device(), _FMT_DTYPES[fmt]).contiguous()
         if x.dim() != 2 or x.shape[0] != self.rows:
             raise ValueError(f"x must have shape [{self.rows}, m*{self.block}]")
         mask = None
@@ -161,7 +163,7 @@ class StreamResampler:
         T = x.shape[1]
         out_len = T // self.block * self._nw
         y = torch.empty((self.rows, out_len), dtype=x.dtype, device=x.device)
-        _lib.check(_lib.lib().dfx_stream_resampler_process(self._h, _lib.ptr(x), int(pcm16), T, T, _lib.ptr(y), int(pcm16), out_len,
+        _lib.check(_lib.lib().dfx_stream_resampler_process(self._h, _lib.ptr(x), fmt, T, T, _lib.ptr(y), fmt, out_len,
                                                            C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
         return y.to(src_dev)
 
@@ -183,12 +185,84 @@ def float_to_pcm16(audio: torch.Tensor) -> torch.Tensor:
     return out
 
 
-_WAVE_PCM, _WAVE_FLOAT, _WAVE_EXTENSIBLE = 1, 3, 0xFFFE
+G711_LAWS = {"ulaw": 1, "alaw": 2}                # DFX_G711_ULAW, DFX_G711_ALAW (include/dfx.h)
+G711_SILENCE = {"ulaw": 0xFF, "alaw": 0xD5}
+_FMT_DTYPES = {0: torch.float32, 1: torch.int16, 2: torch.uint8, 3: torch.uint8}   # DFX_FMT_*
+
+
+def _law(law) -> int:
+    try:
+        return G711_LAWS[law]
+    except (KeyError, TypeError):
+        raise ValueError(f'law must be "ulaw" or "alaw", not {law!r}') from None
+
+
+def _sample_format(x: torch.Tensor, law, who: str) -> int:
+    """DFX_FMT_* of a tensor of samples: uint8 are G.711 codes and need a law; everything but int16 and uint8 is taken as float32."""
+    if x.dtype == torch.uint8:
+        if law is None:
+            raise ValueError(f'{who}: uint8 samples are G.711 codes and need law="ulaw" or law="alaw"')
+        return _law(law) + 1
+    return 1 if x.dtype == torch.int16 else 0
+
+
+def _g711_decode(codes: torch.Tensor, law: str, to_pcm16: bool) -> torch.Tensor:
+    if codes.dtype != torch.uint8:
+        raise TypeError("G.711 codes are uint8")
+    k = _law(law)
+    x = codes.to(_lib.device())
+    if not x.is_contiguous():
+        x = x.contiguous()
+    out = torch.empty(x.shape, dtype=torch.int16 if to_pcm16 else torch.float32, device=x.device)
+    _lib.check(_lib.lib().dfx_g711_decode(_lib.ptr(x), k, x.numel(), _lib.ptr(out), int(to_pcm16), _lib.stream()))
+    return out
+
+
+def _g711_encode(x: torch.Tensor, law: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    k = _law(law)
+    pcm16 = x.dtype == torch.int16
+    x = x.to(_lib.device(), torch.int16 if pcm16 else torch.float32).contiguous()
+    if out is None:
+        out = torch.empty(x.shape, dtype=torch.uint8, device=x.device)
+    elif out.dtype != torch.uint8 or out.numel() != x.numel() or not out.is_contiguous() or not _lib.on_device(out):
+        raise ValueError("out must be a contiguous uint8 tensor of the input's size on the library's device")
+    _lib.check(_lib.lib().dfx_g711_encode(_lib.ptr(x), int(pcm16), k, x.numel(), _lib.ptr(out), _lib.stream()))
+    return out
+
+
+def g711_to_float(codes: torch.Tensor, law: str) -> torch.Tensor:
+    """uint8 G.711 codes (``law`` "ulaw" / "alaw") -> float32, the 16-bit linear value / 32768: what torchaudio.load(normalize=True)
+    returns for a mu-law / A-law WAVE file.  A contiguous view is read where it lies, whatever its byte offset."""
+    return _g711_decode(codes, law, False)
+
+
+def g711_to_pcm16(codes: torch.Tensor, law: str) -> torch.Tensor:
+    """uint8 G.711 codes -> their 16-bit linear values (int16)."""
+    return _g711_decode(codes, law, True)
+
+
+def float_to_g711(audio: torch.Tensor, law: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """float32 -> uint8 G.711 codes: ``trunc(clamp(x * 32768, -32768, 32767))`` (NaN -> 0), then the sign-magnitude encoder.  Unlike
+    ``float_to_pcm16`` this SATURATES.  ``out``: a contiguous uint8 tensor (or view, at any byte offset) to write into."""
+    return _g711_encode(audio if audio.dtype != torch.int16 else audio.to(torch.float32) / 32768.0, law, out)
+
+
+def pcm16_to_g711(pcm: torch.Tensor, law: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """int16 -> uint8 G.711 codes."""
+    if pcm.dtype != torch.int16:
+        raise TypeError("pcm16_to_g711 takes int16 samples")
+    return _g711_encode(pcm, law, out)
+
+
+_WAVE_PCM, _WAVE_FLOAT, _WAVE_ALAW, _WAVE_ULAW, _WAVE_EXTENSIBLE = 1, 3, 6, 7, 0xFFFE
+_WAVE_G711 = {_WAVE_ALAW: "alaw", _WAVE_ULAW: "ulaw"}
 
 
 def _read_riff(file: str, frame_offset: int = 0, num_frames: int = -1):
-    """-> (samples [T, C] numpy array in the file's own sample type (24-bit: int32, sign-extended), sample_rate, total frames, bits, float?).
-    RIFF/WAVE with a 'fmt ' chunk of tag 1 (integer PCM), 3 (IEEE float) or 0xFFFE (extensible: the sub-format's first two bytes)."""
+    """-> (samples [T, C] numpy array in the file's own sample type (24-bit: int32, sign-extended; G.711: the uint8 codes), sample_rate,
+    total frames, bits, float?, G.711 law or None).
+    RIFF/WAVE with a 'fmt ' chunk of tag 1 (integer PCM), 3 (IEEE float), 6 (A-law), 7 (mu-law) or 0xFFFE (extensible: the sub-format's
+    first two bytes); the two G.711 tags only in the extended chunk (18 bytes or more) the WAVE format prescribes for non-PCM data."""
     with open(file, "rb") as f:
         head = f.read(12)
         if len(head) < 12 or head[:4] != b"RIFF" or head[8:12] != b"WAVE":
@@ -209,13 +283,20 @@ def _read_riff(file: str, frame_offset: int = 0, num_frames: int = -1):
                     if valid not in (0, bits):
                         raise RuntimeError(f"{file}: extensible WAVE with {valid} valid bits in {bits}-bit containers is not decoded")
                     tag = struct.unpack("<H", body[24:26])[0]
-                fmt = (tag, nch, rate, align, bits)
+                fmt = (tag, nch, rate, align, bits, size)
             elif cid == b"data":
                 if fmt is None:
                     raise RuntimeError(f"{file}: 'data' chunk before 'fmt '")
-                tag, nch, rate, align, bits = fmt
-                if tag not in (_WAVE_PCM, _WAVE_FLOAT) or (tag == _WAVE_PCM and bits not in (8, 16, 24, 32)) or (tag == _WAVE_FLOAT and bits not in (32, 64)):
-                    raise RuntimeError(f"{file}: unsupported WAVE sample format (tag {tag}, {bits} bits); integer PCM 8/16/24/32 and IEEE float 32/64 are decoded")
+                tag, nch, rate, align, bits, fmt_size = fmt
+                if (tag not in (_WAVE_PCM, _WAVE_FLOAT, _WAVE_ALAW, _WAVE_ULAW) or (tag == _WAVE_PCM and bits not in (8, 16, 24, 32))
+                        or (tag == _WAVE_FLOAT and bits not in (32, 64)) or (tag in _WAVE_G711 and bits != 8)):
+                    raise RuntimeError(f"{file}: unsupported WAVE sample format (tag {tag}, {bits} bits); integer PCM 8/16/24/32, IEEE float 32/64 "
+                                       "and 8-bit G.711 (A-law, mu-law) are decoded")
+                if tag in _WAVE_G711 and fmt_size < 18:
+                    # A non-PCM format carries the extended 'fmt ' chunk (cbSize: 18 bytes at least, which is what every writer of G.711 files
+                    # emits, save_audio included); a 16-byte PCM header with a G.711 tag stays refused, as it has always been.
+                    raise RuntimeError(f"{file}: unsupported WAVE sample format (tag {tag}, {bits} bits, in a 'fmt ' chunk of {fmt_size} bytes); "
+                                       "G.711 is decoded from the 18-byte or extensible 'fmt ' chunk that non-PCM formats carry")
                 bps = bits // 8
                 if align != nch * bps or nch < 1:
                     raise RuntimeError(f"{file}: inconsistent 'fmt ' chunk (block align {align}, {nch} channels x {bps} bytes)")
@@ -241,18 +322,22 @@ def _read_riff(file: str, frame_offset: int = 0, num_frames: int = -1):
                     b = np.frombuffer(raw, dtype=np.uint8).reshape(-1, 3).astype(np.int32)
                     x = b[:, 0] | (b[:, 1] << 8) | (b[:, 2] << 16)
                     x = (x ^ 0x800000) - 0x800000
-                return x.reshape(n, nch), rate, total, bits, tag == _WAVE_FLOAT
+                return x.reshape(n, nch), rate, total, bits, tag == _WAVE_FLOAT, _WAVE_G711.get(tag)
             else:
                 f.seek(size + (size & 1), 1)
 
 
-def _write_riff(file: str, data: np.ndarray, sr: int, is_float: bool) -> None:
-    """data [T, C]: int16 -> 16-bit PCM (tag 1), float32 -> 32-bit IEEE float (tag 3, with the 'fact' chunk non-PCM formats carry)."""
+def _write_riff(file: str, data: np.ndarray, sr: int, is_float: bool, law: Optional[str] = None) -> None:
+    """data [T, C]: int16 -> 16-bit PCM (tag 1), float32 -> 32-bit IEEE float (tag 3, with the 'fact' chunk non-PCM formats carry);
+    ``law``: uint8 G.711 codes -> tag 7 (mu-law) / 6 (A-law): an 18-byte 'fmt ' chunk (cbSize 0), a 'fact' chunk, one byte per sample."""
     T, nch = data.shape
-    bps = 4 if is_float else 2
-    payload = np.ascontiguousarray(data.astype("<f4" if is_float else "<i2", copy=False)).tobytes()
+    bps = 1 if law else (4 if is_float else 2)
+    payload = np.ascontiguousarray(data.astype(np.uint8 if law else ("<f4" if is_float else "<i2"), copy=False)).tobytes()
     pad = b"\x00" if len(payload) & 1 else b""
-    if is_float:
+    if law:
+        fmt = struct.pack("<HHIIHHH", _WAVE_ULAW if law == "ulaw" else _WAVE_ALAW, nch, int(sr), int(sr) * nch, nch, 8, 0)
+        extra = b"fact" + struct.pack("<II", 4, T)
+    elif is_float:
         fmt = struct.pack("<HHIIHHH", _WAVE_FLOAT, nch, int(sr), int(sr) * nch * bps, nch * bps, 8 * bps, 0)
         extra = b"fact" + struct.pack("<II", 4, T)
     else:
@@ -268,22 +353,33 @@ def load_audio(file: str, sr: Optional[int] = None, verbose: bool = True, **kwar
     Sample formats as torchaudio.load(normalize=True) scales them: int16 / 32768 (a HIP kernel), 24-bit / 2^23, int32 / 2^31,
     uint8 (x - 128) / 128, float32 as stored, float64 rounded to float32.
     ``pcm16=True`` (extension): a 16-bit file that needs no resampling is handed back as its int16 samples (on the device) — ``enhance()``
-    takes them as they are."""
+    takes them as they are.
+    A-law / mu-law files (``meta.encoding`` "ALAW" / "ULAW", 8 bits): the codes' 16-bit linear values / 32768 (``g711_to_float``);
+    read from the extended 'fmt ' chunk (18 bytes or more, or extensible) that non-PCM formats carry — a G.711 tag in a 16-byte PCM header is
+    refused as before.
+    ``g711=True`` (extension): the call returns ``(audio, meta, law)``; a G.711 file that needs no resampling comes back as its uint8
+    codes (on the device) with ``law`` "ulaw" / "alaw" — what ``DfStream.process(..., law=law)`` takes —, anything else as usual with
+    ``law`` None."""
     method = kwargs.pop("method", "sinc_fast")
     want_pcm = bool(kwargs.pop("pcm16", False))
+    want_g711 = bool(kwargs.pop("g711", False))
     frames = kwargs.get("num_frames", -1)
     off = kwargs.get("frame_offset", 0)
     if frames is not None and frames > 0 and sr is not None:
-        _, rate0, _, _, _ = _read_riff(file, 0, 1)        # io.py:46-47 scales num_frames by the file's own rate: read it first
+        rate0 = _read_riff(file, 0, 1)[1]        # io.py:46-47 scales num_frames by the file's own rate: read it first
         if rate0 < sr:   # (the reference's `num_frames *= rate0 // sr` is 0 there, which torchaudio reads as "nothing": say so instead of loading the whole file)
             raise RuntimeError(f"{file}: num_frames with a file rate ({rate0}) below the requested rate ({sr}) selects no frames (df/io.py:46-47)")
         frames *= rate0 // sr
-    x, orig_sr, n, bits, is_float = _read_riff(file, off, frames)
+    x, orig_sr, n, bits, is_float, law = _read_riff(file, off, frames)
     ch = x.shape[1]
     info = AudioMetaData(sample_rate=orig_sr, num_frames=n, num_channels=ch, bits_per_sample=bits,
-                         encoding="PCM_F" if is_float else ("PCM_U" if bits == 8 else "PCM_S"))
+                         encoding=law.upper() if law else ("PCM_F" if is_float else ("PCM_U" if bits == 8 else "PCM_S")))
     xt = torch.from_numpy(np.array(x.T, order="C"))       # interleaved -> [C, T] (a writable copy)
-    if x.dtype == np.dtype("<i2"):
+    if law:                                               # the bytes go up, the decoder runs on the device
+        if want_g711 and (sr is None or orig_sr == sr):
+            return xt.to(_lib.device()).contiguous(), info, law
+        audio = g711_to_float(xt, law)
+    elif x.dtype == np.dtype("<i2"):
         if want_pcm and (sr is None or orig_sr == sr):
             return xt.to(_lib.device()).contiguous(), info
         audio = pcm16_to_float(xt)
@@ -301,14 +397,16 @@ def load_audio(file: str, sr: Optional[int] = None, verbose: bool = True, **kwar
 
             warnings.warn(f"Audio sampling rate does not match model sampling rate ({orig_sr}, {sr}). Resampling...")
         audio = resample(audio, orig_sr, sr, method=method)
-    return audio.contiguous(), info
+    return (audio.contiguous(), info, None) if want_g711 else (audio.contiguous(), info)
 
 
 def save_audio(file: str, audio: Union[torch.Tensor, np.ndarray], sr: int, output_dir: Optional[str] = None,
-               suffix: Optional[str] = None, log: bool = False, dtype=torch.int16) -> str:
+               suffix: Optional[str] = None, log: bool = False, dtype=torch.int16, encoding: Optional[str] = None) -> str:
     """io.py:60-84: ``dtype=torch.int16`` (default) writes 16-bit PCM (float input scaled by 2^15 and truncated, io.py:79-80, on the
     device), ``dtype=torch.float32`` a 32-bit IEEE-float WAVE (int16 input divided by 2^15, io.py:81-82) — the two files torchaudio.save
-    writes for an int16 / a float32 tensor."""
+    writes for an int16 / a float32 tensor.
+    ``encoding="ULAW"`` / ``"ALAW"`` (extension): an 8-bit G.711 WAVE (format tag 7 / 6) instead; float or int16 input is encoded on the
+    device (``float_to_g711``: saturating; ``pcm16_to_g711``), uint8 input is taken as codes of that law.  ``dtype`` is not used then."""
     outpath = file
     if suffix is not None:
         base, ext = os.path.splitext(file)
@@ -317,9 +415,17 @@ def save_audio(file: str, audio: Union[torch.Tensor, np.ndarray], sr: int, outpu
         outpath = os.path.join(output_dir, os.path.basename(outpath))
     if dtype not in (torch.int16, torch.float32):
         raise ValueError(f"save_audio: dtype must be torch.int16 or torch.float32, not {dtype}")
+    if encoding not in (None, "ULAW", "ALAW"):
+        raise ValueError(f'save_audio: encoding must be None, "ULAW" or "ALAW", not {encoding!r}')
     audio = torch.as_tensor(audio)
     if audio.ndim == 1:
         audio = audio.unsqueeze(0)
+    if encoding is not None:
+        law = encoding.lower()
+        if audio.dtype != torch.uint8:
+            audio = pcm16_to_g711(audio, law) if audio.dtype == torch.int16 else float_to_g711(audio, law)
+        _write_riff(outpath, audio.cpu().numpy().T, int(sr), False, law)
+        return outpath
     if dtype == torch.int16 and audio.dtype != torch.int16:
         audio = float_to_pcm16(audio)
     if dtype == torch.float32 and audio.dtype != torch.float32:

@@ -107,12 +107,18 @@ class StreamSnapshot:
 class DfStream:
     def __init__(self, model: DfNet, df_state: DF, streams: int = 1, max_frames: int = 1, atten_lim_db: Optional[float] = None,
                  gating: bool = False, thresholds: Optional[Tuple[float, float, float]] = None, channels: int = 1,
-                 reduce_mask: str = "mean", pausable: bool = False, sr: Optional[int] = None, resample_method: str = "sinc_fast"):
+                 reduce_mask: str = "mean", pausable: bool = False, sr: Optional[int] = None, resample_method: str = "sinc_fast",
+                 law: Optional[str] = None):
         if not isinstance(model, DfNet):
             raise TypeError("DfStream needs a deepfilternet_amd.DfNet (see init_df)")
         h = C.c_void_p()
         _lib.check(_lib.lib().dfx_stream_create(model.handle, df_state.handle, int(streams), int(max_frames), C.byref(h)))
         self._h = h
+        if law is not None:
+            from .io import _law
+
+            _law(law)   # ("ulaw" / "alaw": the G.711 law of uint8 frames, unless a call names its own)
+        self.law = law
         self._model, self._df = model, df_state  # keep the handles the runtime points into alive
         self.streams, self.max_frames = int(streams), int(max_frames)
         if atten_lim_db is not None:
@@ -280,10 +286,13 @@ class DfStream:
         _lib.check(_lib.lib().dfx_stream_frames(self._h, C.cast(out.data_ptr(), C.POINTER(C.c_int64))))
         return out
 
-    def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None):
+    def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None, law: Optional[str] = None):
         """df_process_frame (capi.rs:161) for every stream: ``frames`` [streams, n*hop] float32 -> enhanced [streams, n*hop]
         (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB.  int16 ``frames`` are
         16-bit PCM (x / 32768) and come back as int16 (``float_to_pcm16``'s encoding); ``hop`` is ``frame_length``, at the caller's rate.
+        uint8 ``frames`` are G.711 codes — an RTP payload's bytes — of ``law`` ("ulaw" / "alaw"; default: the handle's ``law=``) and come
+        back as codes (``io.g711_to_float`` in, ``io.float_to_g711``'s saturating rule out; a paused stream: the law's silence code; in the
+        undelayed pass-through the very bytes).  The format belongs to the call: one handle takes any of them from call to call.
 
         ``active`` (pausable handles): a sequence or tensor of bools or integers, one per stream (``streams // channels``); a stream whose
         entry is false is paused for all hops of this call (zeros out, lsnr NaN, no state moves; its input rows must still be finite).
@@ -297,8 +306,11 @@ class DfStream:
                 raise ValueError(f"active must have one entry per stream ({self.streams // self.channels})")
             mask = (mask.to("cpu") != 0).to(torch.uint8).contiguous()
         src_dev = frames.device
-        pcm16 = frames.dtype == torch.int16
-        x = frames.to(_lib.device(), torch.int16 if pcm16 else torch.float32).contiguous()
+        from .io import _FMT_DTYPES, _sample_format
+
+        fmt = _sample_format(frames, law if law is not None else self.law, "DfStream.process")
+        pcm16 = fmt == 1
+        x = frames.to(_lib.device(), _FMT_DTYPES[fmt]).contiguous()
         hop = self.frame_length
         if x.dim() != 2 or x.shape[0] != self.streams or x.shape[1] % hop or x.shape[1] == 0:
             raise ValueError(f"frames must have shape [{self.streams}, n*{hop}]")
@@ -307,7 +319,10 @@ class DfStream:
             raise ValueError(f"at most max_frames={self.max_frames} hops per call")
         y = torch.empty_like(x)
         lsnr = torch.empty((self.streams, n), dtype=torch.float32, device=x.device) if return_lsnr else None
-        if pcm16:
+        if fmt >= 2:
+            _lib.check(_lib.lib().dfx_stream_process_g711(self._h, _lib.ptr(x), fmt - 1, n, _lib.ptr(y), _lib.ptr(lsnr),
+                                                          C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
+        elif pcm16:
             _lib.check(_lib.lib().dfx_stream_process_pcm16(self._h, _lib.ptr(x), n, _lib.ptr(y), _lib.ptr(lsnr),
                                                            C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
         elif mask is None:

@@ -36,6 +36,14 @@ extern "C" {
 
 #define DFX_VERSION 200 /* 0.2.0 */
 
+/* G.711 companding laws (dfx_g711_decode / _encode, dfx_stream_process_g711) and the sample formats of dfx_stream_resampler_process */
+#define DFX_G711_ULAW 1
+#define DFX_G711_ALAW 2
+#define DFX_FMT_F32 0   /* float32 */
+#define DFX_FMT_PCM16 1 /* int16: x / 32768 in, dfx_f32_to_pcm16's encoding out */
+#define DFX_FMT_ULAW 2  /* uint8 G.711 mu-law codes */
+#define DFX_FMT_ALAW 3  /* uint8 G.711 A-law codes */
+
 int dfx_version(void);
 const char *dfx_status_string(int status);
 const char *dfx_last_error(void);
@@ -437,6 +445,15 @@ int64_t dfx_stream_resample_delay(const dfx_stream_state *s);            /* samp
  * converted rate the conversions happen inside the two converter kernels; at the model's rate through dfx_pcm16_to_f32 / dfx_f32_to_pcm16. */
 int dfx_stream_process_pcm16(dfx_stream_state *s, const int16_t *x, int64_t n_frames, int16_t *y, float *lsnr, const unsigned char *active,
                              void *stream);
+/* dfx_stream_process_pcm16 for G.711 codes, the bytes of an 8 kHz RTP payload: x, y uint8 [rows, n_frames * frame_length], law =
+ * DFX_G711_ULAW or DFX_G711_ALAW (anything else: DFX_ERR_INVALID_ARG); the codec is dfx_g711_decode / dfx_g711_encode's, below.  At a
+ * converted rate both conversions happen inside the two converter kernels (one byte per sample over the bus in either direction); at the
+ * model's rate through dfx_g711_decode / dfx_g711_encode and the staging rows.  In the handle-wide undelayed pass-through the caller gets
+ * its own BYTES back, not a re-encoding (0x7F stays 0x7F); a paused stream's rows come back as the law's silence code (0xFF / 0xD5).  The
+ * sample format belongs to the call, not to the stream: it enters neither the snapshot record nor the fingerprint, one handle may be called
+ * with float, 16-bit PCM and either law from call to call, and a stream may move between handles fed different formats at the same rate. */
+int dfx_stream_process_g711(dfx_stream_state *s, const uint8_t *x, int law, int64_t n_frames, uint8_t *y, float *lsnr,
+                            const unsigned char *active, void *stream);
 /* Moving live streams between handles.  In the reference a caller's DfTract is a value the host owns; here a stream's state is its rows of
  * the handle's device arrays, in forms that change with the handle and the moment.  A snapshot of a stream is
  *   payload: one packed record of dfx_stream_snapshot_bytes() bytes in DEVICE memory — every state row of the stream's `channels` rows in a
@@ -495,9 +512,28 @@ int dfx_mf_filter(const float *spec, const float *ifc, const float *mat, int op,
  *                      | kaiser_best (1, 16, 0.9475937167399596, 14.769656459379492).  x [B, T] (row stride x_stride) ->
  *                      y [B, dfx_resampler_out_len(T)] (row stride y_stride), device pointers.
  *   dfx_resampler_kernel   the filter bank itself (host arithmetic, no device): W [phases][taps] float32.
+ *   dfx_g711_decode / dfx_g711_encode   G.711 codes (uint8, law = DFX_G711_ULAW | DFX_G711_ALAW) <-> float32 or int16, what
+ *                      torchaudio.load(normalize=True) / libsndfile make of a mu-law / A-law WAVE file.  Closed forms, no table:
+ *     decode to a 16-bit linear value s (float: s / 32768)
+ *       mu-law: u = ~c & 0xFF;  t = (((u & 15) << 3) + 132) << ((u >> 4) & 7);  s = (u & 0x80) ? 132 - t : t - 132          range +-32124
+ *       A-law:  a = c ^ 0x55, e = (a >> 4) & 7, m = a & 15;  t = e == 0 ? (m << 4) + 8 : ((m << 4) + 264) << (e - 1);
+ *               s = (a & 0x80) ? t : -t                                                                                     range +-32256
+ *     encode a 16-bit linear value s: sign-magnitude, as G.711 defines it (the codes of s and -s differ in the sign bit only, s = 1 .. 32767;
+ *     |-32768| = 32768 is taken care of by the min)
+ *       mu-law: m = min(|s|, 32635) + 132;  e = msb(m) - 7;  c = ~((s < 0 ? 0x80 : 0) | e << 4 | ((m >> (e + 3)) & 15)) & 0xFF
+ *       A-law:  m = min(|s|, 32767) >> 3;  e = m < 32 ? 0 : msb(m) - 4;  mant = e == 0 ? (m >> 1) & 15 : (m >> e) & 15;
+ *               c = ((s < 0 ? 0 : 0x80) | e << 4 | mant) ^ 0x55
+ *     float -> code: s = trunc(clamp(x * 32768, -32768, 32767)), NaN -> 0, then encode.  This rule SATURATES; dfx_f32_to_pcm16 wraps like
+ *     save_audio's cast and is unchanged.  Silence is 0xFF (mu-law) / 0xD5 (A-law); encode(decode(c)) == c for every code but mu-law's
+ *     0x7F (negative zero), which gives 0xFF.
+ *     codes / out (encode) may start at any byte address and n may be anything up to 2^40: 16 codes per lane as one 16-byte access between a
+ *     single-code head and tail.  out (decode) / x (encode): float32, or int16 when the _is_pcm16 argument is non-zero.  n == 0: DFX_OK;
+ *     another law, or a null buffer with n > 0: DFX_ERR_INVALID_ARG.
  * ---------------------------------------------------------------------------------------------------------------- */
 int dfx_pcm16_to_f32(const int16_t *pcm, int64_t n, float *out, void *stream);
 int dfx_f32_to_pcm16(const float *x, int64_t n, int16_t *out, void *stream);
+int dfx_g711_decode(const uint8_t *codes, int law, int64_t n, void *out, int out_is_pcm16, void *stream);
+int dfx_g711_encode(const void *x, int x_is_pcm16, int law, int64_t n, uint8_t *out, void *stream);
 typedef struct dfx_resampler dfx_resampler;
 int dfx_resampler_create(int orig_sr, int new_sr, int lowpass_filter_width, double rolloff, int method, double beta,
                          dfx_resampler **out);
@@ -511,16 +547,18 @@ int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, int64_t T, i
  * gcd, the input samples of one frame; in_len a multiple of it and <= max_in_samples, else DFX_ERR_INVALID_ARG) and writes m * new_sr / gcd.
  * Whatever the cut into calls, a row's concatenated output equals dfx_resample applied to P zeros followed by the row's signal, cut to
  * whole frames: P = ceil(width / block) * block input samples of delay = D = P * new_sr / orig_sr output samples (dfx_stream_resampler_delay);
- * bit-identical between cuts.  x / y: float32, or int16 PCM (x / 32768 in, dfx_f32_to_pcm16's encoding out), row strides in samples.
- * active_host: HOST array [rows], zero = the row sits the call out (zeros out, its state does not move); NULL = all rows.  reset: rows = HOST
+ * bit-identical between cuts.  x / y, each in its own format (DFX_FMT_*, anything else: DFX_ERR_INVALID_ARG): float32, int16 PCM
+ * (x / 32768 in, dfx_f32_to_pcm16's encoding out) or G.711 codes (dfx_g711_decode's value / 32768 in, dfx_g711_encode's saturating
+ * float -> code rule out), converted inside the kernel's loads and stores; row strides in samples.
+ * active_host: HOST array [rows], zero = the row sits the call out (zeros out — as codes: the law's silence —, its state does not move); NULL = all rows.  reset: rows = HOST
  * array of row indices, NULL = every row.  The handle refers to `r`, which must outlive it.  All calls are enqueued on `stream`. */
 typedef struct dfx_stream_resampler dfx_stream_resampler;
 int dfx_stream_resampler_create(const dfx_resampler *r, int64_t rows, int64_t max_in_samples, dfx_stream_resampler **out);
 void dfx_stream_resampler_free(dfx_stream_resampler *h);
 int dfx_stream_resampler_reset(dfx_stream_resampler *h, const int64_t *rows /* NULL = all */, int64_t count, void *stream);
 int dfx_stream_resampler_delay(const dfx_stream_resampler *h, int64_t *in_samples, int64_t *out_samples);
-int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_is_pcm16, int64_t in_len, int64_t x_stride, void *y,
-                                 int y_is_pcm16, int64_t y_stride, const unsigned char *active_host /* NULL = all */, void *stream);
+int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_format, int64_t in_len, int64_t x_stride, void *y,
+                                 int y_format, int64_t y_stride, const unsigned char *active_host /* NULL = all */, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
  * Per-kernel timing (measurement aid, no reference counterpart; the reference only logs wall-clock RTF,

@@ -2,7 +2,7 @@
 """Streaming throughput (BASELINE.json configs[3]-style: many concurrent real-time streams, frame by frame) on one MI355X.
 
     python tools/bench_stream.py [--streams 4096] [--frames-per-call 1 4 16] [--calls 200] [--gating] [--churn K] [--exact] [--paused FRACTION]
-                                  [--per-stream-settings] [--sr 16000] [--pcm16] [--move]
+                                  [--per-stream-settings] [--sr 16000] [--pcm16 | --g711 {ulaw,alaw}] [--move]
 
 --churn K: K streams start over before every call (DfStream.reset(ids)), rotating through the pool: the hop time of a service whose
 callers come and go.
@@ -11,7 +11,8 @@ the pool (0: a pausable handle on which nobody pauses).
 --per-stream-settings: every stream gets its own attenuation limit and post-filter beta (and, with --gating, thresholds) before the first call
 (DfStream.set_*(..., streams=ids)); the JSON line also carries the host time of one setter call over all ids (setter_host_ms).
 --sr RATE: the handle takes and returns hops at RATE (DfStream(sr=RATE): an up-sampler in front of the 48 kHz pass, a down-sampler behind it);
---pcm16: the hops are int16 PCM in both directions.  The JSON line carries both; without them the call is the plain 48 kHz float one.
+--pcm16: the hops are int16 PCM in both directions; --g711 LAW: uint8 G.711 codes of that law (DfStream(law=LAW): an RTP payload's bytes).  The JSON
+line carries all three; without them the call is the plain 48 kHz float one.
 --move: after the steady hops, 256 streams and then all of them are exported from the handle and imported into a second one of the same size
 (DfStream.export_streams / import_streams); a further JSON line carries the device time of each (hipEvents on the caller's stream, median of
 5), the record size and the bytes/s they reach against the 8 TB/s HBM peak, next to the steady hop time of the same run.  Each is timed twice:
@@ -48,9 +49,12 @@ def main() -> None:
                     help="a distinct attenuation limit and post-filter beta per stream (with --gating also thresholds), set per stream")
     ap.add_argument("--sr", type=int, default=None, help="the callers' sample rate (hops of hop * sr / 48000 samples; default: the model's 48 kHz)")
     ap.add_argument("--pcm16", action="store_true", help="int16 PCM hops in and out")
+    ap.add_argument("--g711", choices=["ulaw", "alaw"], default=None, help="uint8 G.711 hops in and out, of this law")
     ap.add_argument("--move", action="store_true", help="also time export_streams / import_streams of 256 and of all streams into a second handle")
     ap.add_argument("--exact", action="store_true", help="exact fp32 arithmetic (DFX_EXACT_FP32=1) instead of the fp16-split default")
     args = ap.parse_args()
+    if args.pcm16 and args.g711:
+        ap.error("--pcm16 and --g711 exclude each other")
     if args.exact:
         os.environ["DFX_EXACT_FP32"] = "1"   # read when the model is created
     from deepfilternet_amd import _lib
@@ -66,11 +70,15 @@ def main() -> None:
     exact = bool(model.query(model.Q_EXACT_FP32))
     dev = _lib.device()
     for n in args.frames_per_call:
-        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr)
+        rt = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr, law=args.g711)
         hop = rt.frame_length
         x = 0.1 * torch.randn((args.streams, n * hop), device=dev)
         if args.pcm16:
             x = (x * 32768.0).to(torch.int16)
+        if args.g711:
+            from deepfilternet_amd.io import float_to_g711
+
+            x = float_to_g711(x, args.g711)
         nslots, churn_pos = args.streams, 0
 
         def churn():   # the next K slots of the pool get a new caller
@@ -119,7 +127,7 @@ def main() -> None:
                 torch.cuda.synchronize()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        assert y.dtype == x.dtype and (args.pcm16 or torch.isfinite(y).all())
+        assert y.dtype == x.dtype and (not y.is_floating_point() or torch.isfinite(y).all())
         # host cost of a call: 32 calls enqueued into empty queues, no wait in between (what bounds the rate on a box with a slow host)
         t1 = time.perf_counter()
         for i in range(32):
@@ -131,11 +139,11 @@ def main() -> None:
         print(json.dumps({"metric": "streaming 48 kHz hops/s over all streams", "value": hops / dt, "unit": "frames/s", "streams": args.streams,
                           "frames_per_call": n, "ms_per_call": ms_call, "host_ms_per_call": host_ms, "call_budget_ms": 10.0 * n,
                           "realtime_streams_per_gpu": int(hops / dt / 100.0), "model": args.model, "gating": bool(args.gating), "churn": args.churn, "paused": args.paused, "exact_fp32": exact,
-                          "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms, "sr": rt.sr, "pcm16": bool(args.pcm16),
+                          "per_stream_settings": bool(args.per_stream_settings), "setter_host_ms": setter_ms, "sr": rt.sr, "pcm16": bool(args.pcm16), "g711": args.g711,
                           "resample_delay_ms": rt.resample_delay / rt.sr * 1e3,
                           "algorithmic_latency_ms": (p.fft_size - p.hop_size + rt.delay_frames * p.hop_size) / p.sr * 1e3}), flush=True)
         if args.move:
-            other = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr)
+            other = DfStream(model, df_state, streams=args.streams, max_frames=n, gating=args.gating, pausable=args.paused is not None, sr=args.sr, law=args.g711)
             other.process(x)
             rec = rt.snapshot_bytes
             move = {"metric": "moving streams between handles", "streams": args.streams, "frames_per_call": n, "model": args.model, "record_bytes": rec,
@@ -169,7 +177,7 @@ def main() -> None:
                 del snap
             y = other.process(x)
             torch.cuda.synchronize()
-            assert args.pcm16 or torch.isfinite(y).all()
+            assert not y.is_floating_point() or torch.isfinite(y).all()
             print(json.dumps(move), flush=True)
             del other
         del rt
