@@ -115,6 +115,7 @@ SIGNATURES = {
     "dfx_stream_frame_length": (_i, [_vp]),
     "dfx_stream_delay_frames": (_i, [_vp]),
     "dfx_stream_set_atten_lim": (_i, [_vp, _f]),
+    "dfx_stream_set_atten_lim_enhance": (_i, [_vp, _f]),
     "dfx_stream_set_post_filter_beta": (_i, [_vp, _f]),
     "dfx_stream_set_channels": (_i, [_vp, _i, _i]),
     "dfx_stream_set_gating": (_i, [_vp, _i]),
@@ -132,6 +133,8 @@ SIGNATURES = {
     "dfx_stream_resample_delay": (_i64, [_vp]),
     "dfx_stream_process_pcm16": (_i, [_vp, _vp, _i64, _vp, _fp, _vp, _vp]),
     "dfx_stream_process_g711": (_i, [_vp, _vp, _i, _i64, _vp, _fp, _vp, _vp]),
+    "dfx_stream_process_ends": (_i, [_vp, _vp, _i, _i64, _vp, _fp, C.POINTER(_i64), _vp]),
+    "dfx_stream_memory_bytes": (_i, [_vp, _vp, _i64, _i, C.POINTER(_i64)]),
     "dfx_stream_snapshot_bytes": (_i, [_vp, C.POINTER(_i64)]),
     "dfx_stream_export_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _vp]),
     "dfx_stream_import_streams": (_i, [_vp, C.POINTER(_i64), _i64, _vp, _vp, _i, _vp]),

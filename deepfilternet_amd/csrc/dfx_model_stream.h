@@ -175,6 +175,21 @@ __global__ void __launch_bounds__(256) dfx_k_stream_set_rows(DfxRowVals<W> V, in
     for (int j = 0; j < W; ++j) dst[row * W + j] = V.v[k * W + j];
 }
 
+// ---- clips that end inside a call (dfx_stream_process_ends) ---------------------------------------------------------------------------------
+// keep[row] = the hops of this pass that still belong to the row's clip.  The counts travel as kernel arguments, like the pause mask and the
+// varlen path's row metadata (dfx_k_varlen_rows): no upload, no wait, and the caller's array is free when the call returns.
+#define DFX_END_ROWS 512   /* rows per launch: 2 KB of kernel arguments */
+struct DfxEndRows {
+    int64_t *keep;
+    int64_t row0;
+    int n;
+    int cnt[DFX_END_ROWS];
+};
+__global__ void __launch_bounds__(256) dfx_k_stream_end_rows(DfxEndRows A) {
+    const int i = (int)(blockIdx.x * blockDim.x + threadIdx.x);
+    if (i < A.n) A.keep[A.row0 + i] = A.cnt[i];
+}
+
 // ------------------------------------------------------------------------------------------------ streaming (dfx_stream_*)
 // Frame loop of DfTract::process (tract.rs:509-642) for many lockstep streams: every call runs the batch kernels on a window of
 // H history + n new frames per stream (DfxStreamCtx), with all recurrent state carried in the handle.
@@ -258,6 +273,16 @@ struct dfx_stream_state {
     float *stage_in = nullptr, *stage_out = nullptr;   // [B, nmax * hop] each
     void *thru_tmp = nullptr;                          // [B, nmax * hop_native] floats: where the down-sampler writes during the pass-through
     std::vector<unsigned char> row_active;             // [B], this call: the resamplers' mask (a paused stream's rows: 0)
+    // Clips that end inside a call (dfx_stream_process_ends): ended[row] — host — marks a row whose clip has ended and that was not reset since;
+    // call_valid — the running call's valid_hops (null: no row ends in it), from which stream_process_impl derives every pass's counts
+    // pass_keep [B] and whether a row of the pass is short of the pass's hops (pass_ends: then features() zeroes the frames behind the ends).
+    // (a row that has ended stays behind its end in every later call, whichever entry point makes it, until it is reset)
+    std::vector<unsigned char> ended;
+    int64_t n_ended = 0;
+    const int64_t *call_valid = nullptr;
+    std::vector<int> pass_keep;
+    bool pass_ends = false;
+    size_t keep_dev = 0;      // byte offset into buf: int64 [B]
     // (Replaying a steady-state call from a hipGraph was built in round 1 and removed in round 4: on ROCm 7.2 the replay of the hop's kernel nodes
     // took 2.0-2.2 ms per call where plain launches take 0.4.)
 };
@@ -279,25 +304,31 @@ static inline size_t stream_c0ring_row_bytes(const dfx_model_cfg &c) {
 }
 static inline size_t stream_pend2_row_bytes(const dfx_model_cfg &c) { return 2 * stream_c0ring_row_bytes(c); }
 
-extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out) {
-    if (!m || !st || !out || streams <= 0 || max_frames <= 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: bad arguments");
+// what a model and a DF state must be for a handle (dfx_stream_create, dfx_stream_memory_bytes)
+static int stream_create_check(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, const char *who) {
+    if (!m || !st || streams <= 0 || max_frames <= 0) DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: bad arguments", who);
     const dfx_model_cfg &c = m->cfg;
     if (st->N != c.fft_size || st->hop != c.hop_size || st->nb != c.nb_erb)
-        DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: the DF state does not match the model (fft/hop/nb_erb)");
+        DFX_FAIL(DFX_ERR_INVALID_ARG, "%s: the DF state does not match the model (fft/hop/nb_erb)", who);
     if (c.conv_lookahead != c.df_lookahead)
-        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: conv_lookahead != df_lookahead is not supported by the streaming path");
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "%s: conv_lookahead != df_lookahead is not supported by the streaming path", who);
     // (either arithmetic, DF stage on or off: an exact handle keeps its feature windows in ring form and a gated one its c0 window — the forms of
     // every model without fp16-split fragments — and its GRU layers step on dfx_k_gru_step_x32 / dfx_k_gru_rec_x32)
     if (!m->can.fuse_c0)
-        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)");
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "%s: streaming needs the fused DF encoder (df_pathway_kernel_size_t <= 5, df_order <= 8)", who);
     if (!m->can.fuse_enc)   // (what DfxPass::plan() would refuse on the first hop)
-        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_create: streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)");
-    if (int rc = dfx_require_device()) return rc;
-    dfx_stream_state *s = new dfx_stream_state();
-    s->m = m;
-    s->st = st;
-    s->B = streams;
-    s->nmax = max_frames;
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "%s: streaming needs the fused ERB encoder head (nb_erb even and <= 62, a frame's rows within the LDS)", who);
+    return DFX_OK;
+}
+
+// The layout of a handle's device buffer for s->m, s->st, s->B rows and s->nmax hops per call: every byte offset, the window geometry and
+// s->bytes.  No device access: dfx_stream_create allocates what this plans, dfx_stream_memory_bytes reports it.
+static void stream_layout(dfx_stream_state *s) {
+    const dfx_model *m = s->m;
+    const dfx_state *st = s->st;
+    const dfx_model_cfg &c = m->cfg;
+    const int64_t streams = s->B;
+    const int max_frames = s->nmax;
     s->L = c.df_lookahead;
     // history in front of the new frames: 2 frames for the 3-tap input convolutions + kt-1 frames of (recomputed) c0 for df_convp
     const int hist_conv = 2 + (c.df_pathway_kernel_size_t - 1), hist_df = c.df_order - 1 - c.df_lookahead;
@@ -353,18 +384,35 @@ extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_
     s->lsnr = take((size_t)B * (H + n) * 4);
     s->birth_dev = take((size_t)B * 8);
     s->tz_rows = take((size_t)B * 4);
+    s->keep_dev = take((size_t)B * 8);
+    dfx_model_workspace_bytes(m, B, H + n, &s->model_ws_bytes);
+    s->model_ws = take((size_t)s->model_ws_bytes);
+    s->bytes = off;
+}
+
+extern "C" int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out) {
+    if (!out) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_create: bad arguments");
+    if (int rc = stream_create_check(m, st, streams, max_frames, "dfx_stream_create")) return rc;
+    const dfx_model_cfg &c = m->cfg;
+    if (int rc = dfx_require_device()) return rc;
+    dfx_stream_state *s = new dfx_stream_state();
+    s->m = m;
+    s->st = st;
+    s->B = streams;
+    s->nmax = max_frames;
+    stream_layout(s);
+    const int64_t B = streams;
     s->birth.assign((size_t)B, 0);
+    s->ended.assign((size_t)B, 0);
     s->row_lim_db.assign((size_t)B, 100.f);
     s->row_beta.assign((size_t)B, c.mask_pf ? c.pf_beta : 0.f);
     s->row_thr.resize((size_t)B * 3);
     for (int64_t b = 0; b < B; ++b)
         for (int j = 0; j < 3; ++j) s->row_thr[(size_t)b * 3 + j] = s->thr[j];
-    dfx_model_workspace_bytes(m, B, H + n, &s->model_ws_bytes);
-    s->model_ws = take((size_t)s->model_ws_bytes);
-    s->bytes = off;
     if (hipMalloc(reinterpret_cast<void **>(&s->buf), s->bytes) != hipSuccess) {
+        const size_t bytes = s->bytes;
         delete s;
-        DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream_create: device allocation of %zu bytes failed", off);
+        DFX_FAIL(DFX_ERR_ALLOC, "dfx_stream_create: device allocation of %zu bytes failed", bytes);
     }
     if (int rc = dfx_stream_reset(s, nullptr)) {
         dfx_stream_free(s);
@@ -421,6 +469,8 @@ extern "C" int dfx_stream_reset(dfx_stream_state *s, void *stream) {
     if (s->gate_buf) DFX_HIP(hipMemset(s->gate_buf, 0, s->gate_bytes));  // skip counters, c0 windows (zero = the causal padding)
     s->frames = 0;
     s->birth.assign((size_t)s->B, 0);   // (the device copy is part of buf: zeros)
+    s->ended.assign((size_t)s->B, 0);
+    s->n_ended = 0;
     s->mixed_until = s->warm_until = 0;
     s->flip = 0;
     s->lin_pos = 0;
@@ -515,7 +565,11 @@ extern "C" int dfx_stream_reset_streams(dfx_stream_state *s, const int64_t *ids,
         DFX_LAUNCH_CHECK();
     }
     for (int64_t i = 0; i < count; ++i)
-        for (int k = 0; k < ch; ++k) s->birth[(size_t)(ids[i] * ch + k)] = s->frames;
+        for (int k = 0; k < ch; ++k) {
+            const size_t r = (size_t)(ids[i] * ch + k);
+            s->birth[r] = s->frames;
+            s->n_ended -= s->ended[r], s->ended[r] = 0;
+        }
     if (s->sr) {   // the streams' rows of both converters start over too
         std::vector<int64_t> rows((size_t)count * ch);
         for (int64_t i = 0; i < count; ++i)
@@ -631,6 +685,23 @@ extern "C" int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db) {
     else s->lim = powf(10.f, -lim / 20.f);
     s->row_lim_db.assign((size_t)s->B, lim >= 100.f ? 100.f : lim);
     s->lim_rows = false;   // uniform again: passes take the scalar (lim == 1: the undelayed pass-through, a handle-wide mode)
+    return DFX_OK;
+}
+
+// The handle's limit by enhance()'s rule instead of the runtime's (enhance.py:238-240 as dfx_enhance applies it, dfx_model_enhance.h:170-174): 0 = no
+// limit, every other value mixes with 10^(-|dB|/20) kept below 1 — no undelayed pass-through for tiny values, no "off" from 100 dB on.  What a
+// driver needs whose streams are the clips of an enhance() call (enhance_long).
+extern "C" int dfx_stream_set_atten_lim_enhance(dfx_stream_state *s, float atten_lim_db) {
+    if (!s || std::isnan(atten_lim_db)) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_set_atten_lim_enhance: null handle or NaN");
+    float lim = 0.f;
+    if (atten_lim_db != 0.f) {
+        lim = powf(10.f, -fabsf(atten_lim_db) / 20.f);
+        if (lim >= 1.f) lim = 0.99999994f;
+    }
+    s->lim = lim;
+    // dfx_stream_get_settings reports what is in force: |dB| as given — from 100 on a real limit here, not the runtime's "off" — and 100 for "no limit"
+    s->row_lim_db.assign((size_t)s->B, atten_lim_db == 0.f ? 100.f : fabsf(atten_lim_db));
+    s->lim_rows = false;
     return DFX_OK;
 }
 
@@ -1044,7 +1115,29 @@ struct DfxStreamPass {
                                        norm_fe_cs, norm_fs_cs)))
             return rc;
         if (skip > 0) DFX_HIP(hipMemsetAsync(out_spec, 0, (size_t)B * n * Fp * 8, s));  // warm-up hops: zero spectra (tract.rs rolling buffers)
-        return DFX_OK;
+        return S->pass_ends ? end_rows() : DFX_OK;
+    }
+
+    // Clips that end inside this pass (dfx_stream_process_ends): rule (2) of dfx_enhance_varlen (dfx_model_enhance.h:40-48) — behind a row's last
+    // frame its spectrum and its normalised features are zeros, MF.DF's padding (multiframe.py:72-76) and pad_feat's (deepfilternet3.py:359,409-410)
+    // — applied where the analysis and the norm scan have just written the new frames: new_spec (every window copy of the pass reads it later) and
+    // norm_fe / norm_fs, i.e. the new_* rows or, when the norms write straight into them, the linear windows.  A stream pass makes no pre-split
+    // copy of feat_spec.  The counts reach keep [B] as kernel arguments; one dfx_k_zero_tails launch does the rest.
+    int end_rows() {
+        int64_t *keep = reinterpret_cast<int64_t *>(S->buf + S->keep_dev);
+        for (int64_t r0 = 0; r0 < B; r0 += DFX_END_ROWS) {
+            DfxEndRows A;
+            A.keep = keep, A.row0 = r0;
+            A.n = (int)(B - r0 < DFX_END_ROWS ? B - r0 : DFX_END_ROWS);
+            for (int i = 0; i < A.n; ++i) A.cnt[i] = S->pass_keep[(size_t)(r0 + i)];
+            dfx_launch(dfx_k_stream_end_rows, dim3((unsigned)dfx_ceil_div((int64_t)A.n, 256)), dim3(256), 0, s, A);
+            DFX_LAUNCH_CHECK();
+        }
+        DfxTails t;
+        t.add(new_spec, n * F2, n * F2, F2);
+        t.add(norm_fe, norm_fe_cs ? norm_fe_cs : n * E, n * E, E);
+        t.add(norm_fs, norm_fs_cs ? norm_fs_cs : n * D2, n * D2, D2);
+        return dfx_launch_zero_tails(t, keep, B, s);
     }
 
     // ---- the three windows' enqueue steps.  What only the DF branch needs (the DF feature window) is enqueued on that branch's stream
@@ -1302,10 +1395,21 @@ static int stream_process_staged(dfx_stream_state *S, const void *x, int64_t n, 
     return DFX_OK;
 }
 
+// valid (dfx_stream_process_ends; host [B] or null): the hops of this call that lie inside each row's clip.
 static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, void *y, int fmt, float *lsnr_out, const unsigned char *active,
-                              void *stream) {
+                              void *stream, const int64_t *valid = nullptr) {
     if (!S || n <= 0 || n > S->nmax || !x || !y) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process: bad arguments (1 <= n_frames <= max_frames)");
     if (active && !S->pausable) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_active: a mask needs a pausable handle (dfx_stream_set_pausable)");
+    if (S->lim == 1.f) valid = nullptr;   // (the handle-wide pass-through runs no network: nothing reads the frames behind an end)
+    bool ends = false;
+    for (int64_t b = 0; valid && b < S->B; ++b) {
+        if (valid[b] < 0 || valid[b] > n)
+            DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_ends: valid_hops[%lld] = %lld is not in [0, n_frames = %lld]", (long long)b, (long long)valid[b], (long long)n);
+        if (S->ended[(size_t)b] && valid[b] != 0)
+            DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_ends: stream %lld has ended (valid_hops must be 0 until dfx_stream_reset_streams), got %lld", (long long)b,
+                     (long long)valid[b]);
+        ends |= valid[b] < n;
+    }
     if (int rc = dfx_require_device()) return rc;
     if (int rc = model_poll(S->m)) return rc;
     hipStream_t s = dfx_stream(stream);
@@ -1322,11 +1426,39 @@ static int stream_process_any(dfx_stream_state *S, const void *x, int64_t n, voi
     {
         DfxTurn turn(S->m, s, false);   // (the enqueue lock only: a hop starts no persistent phase)
         S->fresh = false;
-        if (int rc = staged ? stream_process_staged(S, x, n, y, fmt, lsnr_out, s)
-                            : stream_process_impl(S, static_cast<const float *>(x), n, static_cast<float *>(y), lsnr_out, s))
-            return rc;
+        S->call_valid = ends ? valid : nullptr;   // (no row ends in this call: it enqueues what a call without counts enqueues)
+        const int rc = staged ? stream_process_staged(S, x, n, y, fmt, lsnr_out, s)
+                              : stream_process_impl(S, static_cast<const float *>(x), n, static_cast<float *>(y), lsnr_out, s);
+        S->call_valid = nullptr;
+        if (rc) return rc;
+        for (int64_t b = 0; ends && b < S->B; ++b)
+            if (valid[b] < n && !S->ended[(size_t)b]) S->ended[(size_t)b] = 1, ++S->n_ended;
     }
     return stream_call_end(S->m, s);
+}
+// Clips that end inside a call: valid_hops[b] = v (host, [streams]) says that the first v hops of this call are the last frames of row b's clip;
+// the frames behind them — in this call and in every later one, until the row is reset — are MF.DF's and pad_feat's zero padding behind a clip
+// (multiframe.py:72-76, deepfilternet3.py:359,409-410), as in dfx_enhance_varlen, so that the row's output is dfx_enhance(pad=0) of exactly its
+// own frames, delayed, its last `lookahead` frames included.
+extern "C" int dfx_stream_process_ends(dfx_stream_state *S, const void *x, int x_format, int64_t n, void *y, float *lsnr_out, const int64_t *valid_hops,
+                                       void *stream) {
+    if (!S) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_ends: null handle");
+    if (x_format != DFX_FMT_F32 && x_format != DFX_FMT_PCM16)
+        DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_process_ends: x_format %d (DFX_FMT_F32 or DFX_FMT_PCM16)", x_format);
+    if (S->gated || S->pausable || S->channels > 1 || S->sr)
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "dfx_stream_process_ends: not on a gated or pausable handle, with channels > 1 or at a caller's sample rate");
+    return stream_process_any(S, x, n, y, x_format, lsnr_out, nullptr, stream, valid_hops);
+}
+// The device bytes dfx_stream_create(m, st, streams, max_frames) allocates for a handle without a sample rate: its state and window buffer, and the
+// two staging rows [streams, max_frames * hop] that the first 16-bit PCM (or G.711) call adds.  No device access.
+extern "C" int dfx_stream_memory_bytes(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, int64_t *bytes) {
+    if (!bytes) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_stream_memory_bytes: bad arguments");
+    if (int rc = stream_create_check(m, st, streams, max_frames, "dfx_stream_memory_bytes")) return rc;
+    dfx_stream_state s;
+    s.m = m, s.st = st, s.B = streams, s.nmax = max_frames;
+    stream_layout(&s);
+    *bytes = (int64_t)s.bytes + 2 * (int64_t)((size_t)streams * max_frames * st->hop * 4);
+    return DFX_OK;
 }
 extern "C" int dfx_stream_process_active(dfx_stream_state *S, const float *x, int64_t n, float *y, float *lsnr_out, const unsigned char *active,
                                          void *stream) {
@@ -1364,6 +1496,15 @@ static int stream_process_impl(dfx_stream_state *S, const float *x, int64_t n, f
                 if (S->paused[(size_t)i] || born == 0 || age >= Hs) continue;
                 mixed = true;
                 if (age < S->L) warm = true;
+            }
+        }
+        S->pass_ends = false;
+        if ((S->call_valid || S->n_ended) && advances) {   // the hops of this pass that lie inside each row's clip: valid_hops less the hops of the earlier passes
+            S->pass_keep.resize((size_t)S->B);
+            for (int64_t b = 0; b < S->B; ++b) {
+                const int64_t v = S->ended[(size_t)b] ? 0 : (S->call_valid ? S->call_valid[b] - done : k);
+                S->pass_keep[(size_t)b] = (int)(v < 0 ? 0 : (v > k ? k : v));
+                S->pass_ends |= v < k;
             }
         }
         if (int rc = stream_body(S, x + done * hop, k, y + done * hop, lsnr_out ? lsnr_out + done : nullptr, s, n * hop, n * hop, n, mixed, warm)) return rc;

@@ -340,7 +340,11 @@ extern "C" int dfx_stream_import_streams(dfx_stream_state *s, const int64_t *ids
     }
     if (int rc = stream_move_launch<true>(s, R, rb, ids, births.data(), count, const_cast<unsigned char *>(static_cast<const unsigned char *>(payload_dev)), hs)) return rc;
     for (int64_t i = 0; i < count; ++i)
-        for (int k = 0; k < ch; ++k) s->birth[(size_t)(ids[i] * ch + k)] = births[(size_t)i];
+        for (int k = 0; k < ch; ++k) {
+            const size_t r = (size_t)(ids[i] * ch + k);
+            s->birth[r] = births[(size_t)i];
+            s->n_ended -= s->ended[r], s->ended[r] = 0;   // (a slot that is overwritten holds a live stream again)
+        }
     // the rows no longer share one start: the per-row t_zero for the next window of hops, one hop per pass while a stream is in warm-up
     if (s->mixed_until < s->frames + s->H + s->L) s->mixed_until = s->frames + s->H + s->L;
     if (young && s->warm_until < s->frames + s->L) s->warm_until = s->frames + s->L;

@@ -114,7 +114,7 @@ def _norm_alpha(df: DF, tau: float = 1.0) -> float:
 
 def _workspace_cap(model: DfNet, need: int) -> Optional[int]:
     """Bytes the enhance() workspace may take: DFX_WORKSPACE_CAP_GB if set, else 90 % of what the device has free plus the workspace this
-    model already holds (None when that cannot be asked, e.g. on the CPU interpreter build).  The device is only asked when the answer can
+    model already holds (None when that cannot be asked, e.g. on the CPU interpreter build; ``model`` None: a buffer of its own, nothing held).  The device is only asked when the answer can
     matter: a request that fits into the workspace the model already holds needs no allocation at all."""
     env = os.environ.get("DFX_WORKSPACE_CAP_GB")
     if env:
@@ -147,16 +147,15 @@ def enhance(model: DfNet, df_state: DF, audio: torch.Tensor, pad: bool = True, a
     # a page-locked host batch moves by DMA without the driver's staging copies (and comes back into page-locked memory): the
     # transfer is then asynchronous on the launch stream, ~55 GB/s over PCIe Gen5 instead of ~10 for pageable memory
     pinned = src_dev.type == "cpu" and audio.is_pinned() and _lib.device().type == "cuda"
-    x = audio.to(_lib.device(), torch.int16 if pcm16 else torch.float32, non_blocking=pinned).contiguous()
-    if x.dim() != 2:
+    if audio.dim() != 2:
         raise ValueError("audio must have shape [C, T]")
-    B, T = x.shape
+    B, T = audio.shape
     hop = df_state.hop_size()
     n_fft = df_state.fft_size()
     out_len = T if pad else ((T // hop) * hop)
-    y = torch.empty((B, out_len), dtype=x.dtype, device=x.device)
+    dt = torch.int16 if pcm16 else torch.float32
     if B == 0 or out_len == 0:
-        return y.to(src_dev)
+        return torch.empty((B, out_len), dtype=dt, device=_lib.device()).to(src_dev)
     nbytes = C.c_int64()
     L = _lib.lib()
     lim_db = float(atten_lim_db) if atten_lim_db is not None else 0.0
@@ -174,7 +173,12 @@ def enhance(model: DfNet, df_state: DF, audio: torch.Tensor, pad: bool = True, a
     if cap is not None and need > cap:
         lo, hi = 1, B                      # largest sub-batch whose workspace fits (the requirement grows with the batch)
         if ws_bytes(1) > cap:
-            raise MemoryError(f"enhance(): a single clip of {T} samples needs {ws_bytes(1)} bytes of workspace, {cap} available")
+            # one clip alone does not fit: its rows go through time-chunked stream passes in bounded memory (enhance_long) — decided before
+            # anything of the clip is on the device: a host clip is then staged chunk by chunk and never uploaded whole
+            err = MemoryError(f"enhance(): a single clip of {T} samples needs {ws_bytes(1)} bytes of workspace, {cap} available")
+            if not _long_serves(model, df_state):
+                raise err
+            return enhance_long(model, df_state, [audio], pad=pad, atten_lim_db=atten_lim_db)[0]
         while lo < hi:
             mid = (lo + hi + 1) // 2
             if ws_bytes(mid) <= cap:
@@ -182,6 +186,8 @@ def enhance(model: DfNet, df_state: DF, audio: torch.Tensor, pad: bool = True, a
             else:
                 hi = mid - 1
         sub = lo if lo < 16 else lo - lo % 16   # whole groups of 16 clips (one GRU workgroup each) when there are that many
+    x = audio.to(_lib.device(), dt, non_blocking=pinned).contiguous()
+    y = torch.empty((B, out_len), dtype=dt, device=x.device)
     ws = model.workspace(need if sub == B else ws_bytes(sub))
     for b0 in range(0, B, sub):
         n = min(sub, B - b0)
@@ -215,9 +221,11 @@ def _varlen_ws_bytes(model: DfNet, df_state: DF, lens, pad: bool) -> int:
     return int(nbytes.value)
 
 
-def _plan_passes(model: DfNet, df_state: DF, lens, pad: bool):
+def _plan_passes(model: DfNet, df_state: DF, lens, pad: bool, long_rows: Optional[list] = None):
     """[(first row, rows, workspace bytes)] over rows sorted longest first: at most _BATCH_ROWS rows per pass, and — the rule of enhance() — a
-    workspace within _workspace_cap (fewer rows, whole groups of 16, when the cap says so)."""
+    workspace within _workspace_cap (fewer rows, whole groups of 16, when the cap says so).  A row whose workspace does not fit the cap even
+    alone is appended to ``long_rows`` — the caller takes it through enhance_long's stream passes — where that list is given and the stream
+    runtime serves the model; else MemoryError."""
     passes, r = [], 0
     while r < len(lens):
         n = min(_BATCH_ROWS, len(lens) - r)
@@ -225,7 +233,11 @@ def _plan_passes(model: DfNet, df_state: DF, lens, pad: bool):
         cap = _workspace_cap(model, need)
         if cap is not None and need > cap:
             if _varlen_ws_bytes(model, df_state, lens[r:r + 1], pad) > cap:
-                raise MemoryError(f"enhance_batch(): a clip of {lens[r]} samples needs more workspace than the {cap} bytes available")
+                if long_rows is None or not _long_serves(model, df_state):
+                    raise MemoryError(f"enhance_batch(): a clip of {lens[r]} samples needs more workspace than the {cap} bytes available")
+                long_rows.append(r)
+                r += 1
+                continue
             lo, hi = 1, n
             while lo < hi:
                 mid = (lo + hi + 1) // 2
@@ -280,7 +292,12 @@ def enhance_batch(model: DfNet, df_state: DF, clips, pad: bool = True, atten_lim
         if not rows:
             continue
         lens = [views[i].shape[1] for i, _ in rows]
-        passes = _plan_passes(model, df_state, lens, pad)
+        long_rows = []
+        passes = _plan_passes(model, df_state, lens, pad, long_rows)
+        if long_rows:
+            _long_rows(model, df_state, [(views[rows[r][0]][rows[r][1]], results[rows[r][0]][rows[r][1]]) for r in long_rows], pad, atten_lim_db)
+        if not passes:
+            continue
         ws = model.workspace(max(p[2] for p in passes))
         pending = None
         for r0, n, _ in passes:
@@ -336,6 +353,232 @@ def _unpack_host(results, prow, outs, yh, ev, done):
     for j, (i, ch) in enumerate(prow):
         if j not in done:
             results[i][ch].copy_(yh[j, : outs[j]])
+
+
+# Hops per call of enhance_long.  tools/bench_long.py's sweep over 128 / 256 / 512 / 1024 is nearly flat (9.0 to 9.5 M frames/s): 256 is the last
+# step that buys more than 2 %, at 7.8 GB for 256 slots (docs/measurements.md, "Clips of any length").
+_LONG_HOPS = 256
+# What the last enhance_long call ran with: slots, hops_per_call, the handle's device bytes (dfx_stream_memory_bytes), stream calls made.
+last_long_plan: dict = {}
+
+
+def _stream_bytes(model: DfNet, df_state: DF, slots: int, hops: int) -> int:
+    nbytes = C.c_int64()
+    _lib.check(_lib.lib().dfx_stream_memory_bytes(model.handle, df_state.handle, int(slots), int(hops), C.byref(nbytes)))
+    return int(nbytes.value)
+
+
+def _long_serves(model: DfNet, df_state: DF) -> bool:
+    """Does the stream runtime take this model (dfx_stream_create's refusals: include/dfx.h, "Engine configurations")?"""
+    try:
+        _stream_bytes(model, df_state, 1, 16)
+    except RuntimeError:
+        return False
+    return True
+
+
+def _plan_long(model: DfNet, df_state: DF, rows: int, most_hops: int, slots: Optional[int], hops_per_call: Optional[int]):
+    """(slots, hops_per_call, device bytes) of enhance_long's stream handle: the defaults or the caller's values, no more hops per call than
+    the longest row takes, and under the cap of enhance() (DFX_WORKSPACE_CAP_GB, else 90 % of the free device memory) — slots halve first, down
+    to 16, then hops down to 16, then the last slots.  MemoryError when one slot of 16 hops does not fit."""
+    if slots is None:
+        slots = min(rows, _BATCH_ROWS)
+        slots = slots if slots < 16 else slots - slots % 16   # whole groups of 16 rows (one GRU workgroup each) when there are that many
+    s = max(1, min(int(slots), rows))
+    h = max(1, min(int(hops_per_call) if hops_per_call is not None else _LONG_HOPS, most_hops))
+    h_min = min(16, h)
+    need = _stream_bytes(model, df_state, s, h)
+    cap = _workspace_cap(None, need)
+    while cap is not None and need > cap:
+        if s > 16:
+            s = max(16, s // 2 // 16 * 16)
+        elif h > h_min:
+            h = max(h_min, h // 2)
+        elif s > 1:
+            s //= 2
+        else:
+            raise MemoryError(f"enhance_long(): a stream handle of one slot and {h} hops needs {need} bytes, {cap} available")
+        need = _stream_bytes(model, df_state, s, h)
+    return s, h, need
+
+
+@torch.no_grad()
+def enhance_long(model: DfNet, df_state: DF, clips, pad: bool = True, atten_lim_db: Optional[float] = None, slots: Optional[int] = None,
+                 hops_per_call: Optional[int] = None) -> list:
+    """``enhance()`` of clips of any length in bounded device memory.  ``clips`` is what ``enhance_batch`` accepts — ``[C_i, T_i]`` or ``[T_i]``,
+    float32 or int16, host (page-locked or not) or device — and result i has the shape, dtype and device of
+    ``enhance(model, df_state, clips[i], pad, atten_lim_db)``.
+
+    Every channel of every clip is a row; the rows run, longest first, through the ``slots`` streams of one
+    ``DfStream(streams=slots, max_frames=hops_per_call)``: a call feeds every busy slot its row's next ``hops_per_call`` hops (zeros behind
+    the row's own samples), a row's frame count ``(T + (n_fft if pad else 0)) // hop`` gives the call's ``valid_hops`` — behind its last frame
+    the row sees the batch path's zero padding (``dfx_stream_process_ends``) — and a slot whose row has put out its last sample is reset and
+    takes the next row at the following call.  The device holds the handle (``dfx_stream_memory_bytes``; ``last_long_plan`` reports it) and two
+    calls' worth of samples, whatever the clips' lengths; ``slots`` and ``hops_per_call`` shrink until the handle fits the cap of ``enhance()``
+    (``DFX_WORKSPACE_CAP_GB``, else 90 % of the free memory), and MemoryError is raised only when one slot of 16 hops does not fit.
+
+    The samples are those of ``enhance()`` to rounding, not bit for bit: a stream's chunks take the windowed forward pass and, on one-hop
+    passes, kernels of their own, whose sums run in another order than the whole-clip pass (include/dfx.h: "the results do not depend on the
+    cut beyond rounding") — about 1e-6 RMS at a signal of 0.1 RMS, and 16-bit results may differ by one LSB where that rounding crosses a
+    truncation boundary.  ``atten_lim_db`` follows ``enhance()``'s rule for every value (``dfx_stream_set_atten_lim_enhance``).  A model with
+    ``mask_pf`` is served by the stream runtime's post filter, libDF's, which leaves the last ``(ch * F) % 4`` bins of a frame alone where
+    ``enhance()`` filters every bin: there the results agree to 1e-4.
+
+    ``enhance()``, ``enhance_batch()`` and ``enhance_files()`` come here by themselves with the rows of a clip whose workspace does not fit the
+    cap alone — where they used to raise MemoryError — and with nothing else."""
+    if not isinstance(model, DfNet):
+        raise TypeError("enhance_long() of deepfilternet_amd needs a deepfilternet_amd.DfNet (see init_df)")
+    clips = list(clips)
+    cuda = _lib.device().type == "cuda"
+    hop = df_state.hop_size()
+    results, pairs = [], []
+    for a in clips:
+        if a.dim() not in (1, 2):
+            raise ValueError("enhance_long(): every clip must have shape [C, T] or [T]")
+        v = a.unsqueeze(0) if a.dim() == 1 else a
+        T = v.shape[1]
+        dt = torch.int16 if a.dtype == torch.int16 else torch.float32
+        pinned = cuda and a.device.type == "cpu" and a.is_pinned()
+        r = torch.empty((v.shape[0], T if pad else T // hop * hop), dtype=dt, device=a.device, pin_memory=pinned)
+        results.append(r)
+        pairs += [(v[ch] if v.dtype == dt else v[ch].to(dt), r[ch]) for ch in range(v.shape[0])]
+    _long_rows(model, df_state, pairs, pad, atten_lim_db, slots, hops_per_call)
+    return [r[0] if a.dim() == 1 else r for r, a in zip(results, clips)]
+
+
+def _long_rows(model: DfNet, df_state: DF, pairs, pad: bool, atten_lim_db: Optional[float], slots: Optional[int] = None,
+               hops_per_call: Optional[int] = None) -> None:
+    """enhance_long over rows: ``pairs`` = (samples [T], result [out_len]) of every row, 1-D tensors of one dtype per pair."""
+    from .streaming import DfStream
+
+    pairs = [(s, d) for s, d in pairs if d.numel() > 0]   # (a row without output — shorter than a hop without pad, or empty — is done)
+    if not pairs:
+        return
+    hop, n_fft = df_state.hop_size(), df_state.fft_size()
+    look = int(model.p.df_lookahead)
+    o0 = look * hop + (n_fft - hop if pad else 0)         # a row's output starts at this stream sample (enhance.py:248-249 behind the lookahead)
+    most = max(-(-(o0 + d.shape[0]) // hop) for _, d in pairs)
+    slots, hops, nbytes = _plan_long(model, df_state, len(pairs), most, slots, hops_per_call)
+    rt = DfStream(model, df_state, streams=slots, max_frames=hops)
+    rt.set_atten_lim_enhance(atten_lim_db)
+    assert rt.delay_frames == look
+    calls = 0
+    for dt in (torch.int16, torch.float32):   # the sample format belongs to the call: 16-bit rows first, then float rows, on the same handle
+        group = sorted((p for p in pairs if p[1].dtype == dt), key=lambda p: -p[0].shape[0])
+        if group:
+            rt.reset()   # (every slot free and none behind an end)
+            calls += _long_group(rt, group, dt, hop, (n_fft if pad else 0), o0)
+    model.poll()
+    last_long_plan.clear()
+    last_long_plan.update(slots=slots, hops_per_call=hops, bytes=nbytes, calls=calls)
+
+
+class _Slot:
+    __slots__ = ("src", "dst", "T", "frames", "fed", "need")
+
+    def __init__(self, src, dst, hop, pad_n, o0):
+        self.src, self.dst, self.T = src, dst, int(src.shape[0])
+        self.frames = (self.T + pad_n) // hop          # enhance.py:230-235
+        self.fed = 0                                   # hops fed so far
+        self.need = -(-(o0 + dst.shape[0]) // hop)     # hops until the row's last output sample is out (<= frames + lookahead)
+
+
+def _long_group(rt, group, dt, hop: int, pad_n: int, o0: int) -> int:
+    """The rows of one sample format through the handle's slots; returns the number of stream calls."""
+    dev = _lib.device()
+    cuda = dev.type == "cuda"
+    S, nmax = rt.streams, rt.max_frames
+    queue = list(reversed(group))                # (pop() takes the longest row left)
+    slot = [None] * S
+    stale = [False] * S                          # the slot's row is finished and no new one has taken it: behind its end until the next reset
+    stage_in, stage_out, ev_in = [None, None], [None, None], [None, None]
+    pending, calls = None, 0
+    while queue or any(s is not None for s in slot):
+        new = []
+        for j in range(S):
+            if slot[j] is None and queue:
+                slot[j] = _Slot(*queue.pop(), hop, pad_n, o0)
+                new.append(j)
+        if new:   # a new row takes a slot at a call boundary: the slot starts over
+            rt.reset(new)
+            for j in new:
+                stale[j] = False
+        busy = [j for j in range(S) if slot[j] is not None]
+        n = min(nmax, max(slot[j].need - slot[j].fed for j in busy))
+        W = n * hop
+        b = calls & 1
+        # ---- this call's samples [S, n * hop]: host rows through a page-locked staging buffer (two of them, in turn) and one asynchronous copy,
+        # device rows with the multi-tensor copy; zeros behind a row's own samples and in the slots without a row
+        host = [j for j in busy if not _lib.on_device(slot[j].src)]
+        took = {j: max(0, min(slot[j].T, slot[j].fed * hop + W) - slot[j].fed * hop) for j in busy}
+        if host:
+            if ev_in[b] is not None:
+                ev_in[b].synchronize()   # (the copy that last read this buffer)
+            if stage_in[b] is None:
+                stage_in[b] = torch.empty((S * nmax * hop,), dtype=dt, pin_memory=cuda)
+            h = stage_in[b][: S * W].view(S, W)
+            for j in host:
+                a, m = slot[j].fed * hop, took[j]
+                h[j, :m].copy_(slot[j].src[a:a + m])
+                if m < W:
+                    h[j, m:].zero_()
+            x = h.to(dev, non_blocking=cuda)
+            if cuda:
+                ev_in[b] = torch.cuda.Event()
+                ev_in[b].record()
+            elif x.data_ptr() == h.data_ptr():
+                x = x.clone()
+        else:
+            x = torch.empty((S, W), dtype=dt, device=dev)
+        on_dev = [j for j in busy if j not in set(host)]
+        _copy_rows([x[j, : took[j]] for j in on_dev if took[j]], [slot[j].src[slot[j].fed * hop: slot[j].fed * hop + took[j]] for j in on_dev if took[j]])
+        for j in range(S):
+            if slot[j] is None:
+                x[j].zero_()
+            elif j in on_dev and took[j] < W:
+                x[j, took[j]:].zero_()
+        # ---- the hops of this call inside every row's clip; a slot without a row: all of them before its first row, none behind a finished one
+        valid = [min(n, max(0, slot[j].frames - slot[j].fed)) if slot[j] is not None else (0 if stale[j] else n) for j in range(S)]
+        y = rt.process(x, valid_hops=None if all(v == n for v in valid) else valid)   # (polls the model's error words)
+        calls += 1
+        # ---- the part of every row's output window that came out in this call
+        d_dst, d_src, h_items = [], [], []
+        for j in busy:
+            s = slot[j]
+            a = s.fed * hop
+            lo, hi = max(a, o0), min(a + W, o0 + s.dst.shape[0])
+            if hi > lo:
+                if _lib.on_device(s.dst):
+                    d_dst.append(s.dst[lo - o0: hi - o0])
+                    d_src.append(y[j, lo - a: hi - a])
+                else:
+                    h_items.append((s.dst[lo - o0: hi - o0], j, lo - a, hi - a))
+            s.fed += n
+            if s.fed >= s.need:
+                slot[j], stale[j] = None, True
+        _copy_rows(d_dst, d_src)
+        if pending is not None:   # the previous call's host rows are unpacked while this call runs
+            _unpack_long(*pending)
+            pending = None
+        if h_items:
+            if stage_out[b] is None:
+                stage_out[b] = torch.empty((S * nmax * hop,), dtype=dt, pin_memory=cuda)
+            yh = stage_out[b][: S * W].view(S, W)
+            yh.copy_(y, non_blocking=cuda)
+            ev = torch.cuda.Event() if cuda else None
+            if ev is not None:
+                ev.record()
+            pending = (yh, ev, h_items)
+    if pending is not None:
+        _unpack_long(*pending)
+    return calls
+
+
+def _unpack_long(yh, ev, items) -> None:
+    if ev is not None:
+        ev.synchronize()
+    for dst, j, lo, hi in items:
+        dst.copy_(yh[j, lo:hi])
 
 
 def enhance_files(model: DfNet, df_state: DF, input_files, output_dir: Optional[str] = None, suffix: Optional[str] = None,

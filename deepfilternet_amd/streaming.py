@@ -25,6 +25,11 @@ its own ``enhance(pad=False)`` delayed; one launch per GRU layer on a one-hop ca
 
 ``rt.reset([3, 17])`` makes single streams start over (a new caller in a used slot) while all others run on; ``rt.frames`` are the per-stream ages in hops.
 
+``rt.process(hops, valid_hops=[...])`` ends clips inside a call: entry ``v`` of a stream says that the call's first ``v`` hops are the last frames
+of its clip; what follows (feed zeros) is the batch path's zero padding behind a clip — spectrum and normalised features — so the stream's
+output is ``enhance(pad=False)`` of exactly its own frames, delayed, its last ``delay_frames`` frames included.  An ended stream takes 0 until
+``reset([i])`` gives the slot to the next clip.  ``deepfilternet_amd.enhance.enhance_long`` drives a handle this way for clips of any length.
+
 ``pausable=True`` lets single streams sit calls out: ``rt.process(hop, active=mask)`` with one bool per stream.  A stream whose entry is
 false is paused for that call — none of its state moves and its age stands still, its rows of the output are exact zeros and its lsnr
 NaN, and its next active hop is processed as if the paused calls had not happened (every caller keeps its own clock, as with one
@@ -202,6 +207,12 @@ class DfStream:
         else:
             self._set_streams(_lib.lib().dfx_stream_set_atten_lim_streams, streams, [lim_db], 1)
 
+    def set_atten_lim_enhance(self, atten_lim_db: Optional[float]) -> None:
+        """The handle-wide limit by ``enhance()``'s rule (df/enhance.py:238-240) instead of the runtime's: ``None`` or 0 = no limit, every other
+        value mixes with ``10 ** (-abs(dB) / 20)`` kept below 1 — no undelayed pass-through below 0.01 dB, no "off" from 100 dB on.  For handles
+        whose streams are the clips of an ``enhance()`` call (``enhance_long``).  ``settings`` then reports ``abs(dB)`` as given."""
+        _lib.check(_lib.lib().dfx_stream_set_atten_lim_enhance(self._h, float(atten_lim_db) if atten_lim_db is not None else 0.0))
+
     def set_post_filter_beta(self, beta, streams=None) -> None:
         """df_set_post_filter_beta (capi.rs:146): 0 disables the post filter.  ``streams`` as in ``set_atten_lim``."""
         if streams is None:
@@ -286,7 +297,7 @@ class DfStream:
         _lib.check(_lib.lib().dfx_stream_frames(self._h, C.cast(out.data_ptr(), C.POINTER(C.c_int64))))
         return out
 
-    def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None, law: Optional[str] = None):
+    def process(self, frames: torch.Tensor, return_lsnr: bool = False, active=None, law: Optional[str] = None, valid_hops=None):
         """df_process_frame (capi.rs:161) for every stream: ``frames`` [streams, n*hop] float32 -> enhanced [streams, n*hop]
         (on the device the input came from); with ``return_lsnr`` also the local SNR estimates [streams, n] in dB.  int16 ``frames`` are
         16-bit PCM (x / 32768) and come back as int16 (``float_to_pcm16``'s encoding); ``hop`` is ``frame_length``, at the caller's rate.
@@ -296,7 +307,23 @@ class DfStream:
 
         ``active`` (pausable handles): a sequence or tensor of bools or integers, one per stream (``streams // channels``); a stream whose
         entry is false is paused for all hops of this call (zeros out, lsnr NaN, no state moves; its input rows must still be finite).
-        ``None`` = all streams take part.  The mask is read on the host: a device tensor is copied there first, which waits for the device."""
+        ``None`` = all streams take part.  The mask is read on the host: a device tensor is copied there first, which waits for the device.
+
+        ``valid_hops`` (``dfx_stream_process_ends``; float32 or int16 frames on a handle without gating, pausing, ``channels`` or ``sr``): a
+        sequence or tensor of integers, one per stream, read on the host.  Entry ``v`` (0 <= v <= n) says that the first ``v`` hops of this
+        call are the last frames of that stream's clip: what follows — feed zeros — is the batch path's zero padding behind a clip, so the
+        stream's output is ``enhance(pad=False)`` of exactly its own frames, delayed, the last ``delay_frames`` frames included.  A stream
+        that has ended takes 0 in every later call until ``reset([i])``.  ``None`` = no stream ends in this call."""
+        ends = None
+        if valid_hops is not None:
+            ends = torch.as_tensor(valid_hops).reshape(-1)
+            if ends.is_floating_point() or ends.is_complex() or ends.dtype == torch.bool:
+                raise TypeError("valid_hops must hold integers")
+            if ends.numel() != self.streams:
+                raise ValueError(f"valid_hops must have one entry per stream ({self.streams})")
+            if active is not None:
+                raise ValueError("valid_hops and active cannot be combined (clip ends are not served on pausable handles)")
+            ends = ends.to("cpu", torch.int64).contiguous()
         mask = None
         if active is not None:
             mask = torch.as_tensor(active).reshape(-1)
@@ -319,7 +346,12 @@ class DfStream:
             raise ValueError(f"at most max_frames={self.max_frames} hops per call")
         y = torch.empty_like(x)
         lsnr = torch.empty((self.streams, n), dtype=torch.float32, device=x.device) if return_lsnr else None
-        if fmt >= 2:
+        if ends is not None:
+            if fmt >= 2:
+                raise ValueError("valid_hops: float32 or int16 frames")
+            _lib.check(_lib.lib().dfx_stream_process_ends(self._h, _lib.ptr(x), fmt, n, _lib.ptr(y), _lib.ptr(lsnr),
+                                                          C.cast(ends.data_ptr(), C.POINTER(C.c_int64)), _lib.stream()))
+        elif fmt >= 2:
             _lib.check(_lib.lib().dfx_stream_process_g711(self._h, _lib.ptr(x), fmt - 1, n, _lib.ptr(y), _lib.ptr(lsnr),
                                                           C.c_void_p(mask.data_ptr()) if mask is not None else None, _lib.stream()))
         elif pcm16:

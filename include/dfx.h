@@ -379,6 +379,12 @@ int dfx_enhance_varlen_pcm16(const dfx_model *m, const dfx_state *st, const int1
  *   way).  Thresholds set on a handle without gating are stored and take effect once gating is on; a pausable handle that is not gated keeps
  *   running every stage on every hop, and a mask-only model keeps having no DF threshold.  A per-row handle enqueues the same kernels per
  *   hop as a uniform one: the finishing kernel and the stage decision read each row's values from small device arrays.
+ *   Clip ends (dfx_stream_process_ends, below): a stream has no end, so "equals dfx_enhance(pad=0) delayed" stops `lookahead` frames short of a
+ *   clip's last frame — they only come out when more hops are fed, and the features of fed silence are not the batch path's zero padding.  A
+ *   call may say per row how many of its hops are still frames of the row's clip; behind them the row sees that padding, and its output is
+ *   dfx_enhance(pad=0) of exactly its own frames, delayed, the last ones included.  With dfx_stream_reset_streams and
+ *   dfx_stream_memory_bytes this is what a time-chunked enhance() of clips of any length in bounded memory is built from (enhance_long in the
+ *   Python package).
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dfx_stream_state dfx_stream_state;
 int dfx_stream_create(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, dfx_stream_state **out);
@@ -394,6 +400,13 @@ int dfx_stream_frames(const dfx_stream_state *s, int64_t *frames_out);
 int dfx_stream_frame_length(const dfx_stream_state *s);                  /* hop size in samples (df_get_frame_length), at the caller's rate */
 int dfx_stream_delay_frames(const dfx_stream_state *s);                  /* lookahead in hops */
 int dfx_stream_set_atten_lim(dfx_stream_state *s, float lim_db);         /* df_set_atten_lim: |dB| >= 100 off, < 0.01 bypass */
+/* The handle-wide limit by enhance()'s rule (df/enhance.py:238-240, as dfx_enhance applies it) instead of the runtime's: 0 = no limit, any
+ * other value mixes with 10^(-|dB|/20) kept below 1 — no undelayed pass-through below 0.01 dB and no "off" from 100 dB on.  For drivers whose
+ * streams are the clips of an enhance() call.  Makes the handle uniform in the setting, like dfx_stream_set_atten_lim.  dfx_stream_get_settings
+ * then reports |atten_lim_db| as given (above 100 too: a real limit here) and 100 for 0 = no limit.  The rule belongs to the handle, not to its
+ * streams: a stream exported from it carries the |dB| value, and the importing handle applies its own runtime's rule to it (|dB| >= 100: off;
+ * < 0.01: lim = 0.99999994). */
+int dfx_stream_set_atten_lim_enhance(dfx_stream_state *s, float atten_lim_db);
 int dfx_stream_set_post_filter_beta(dfx_stream_state *s, float beta);    /* df_set_post_filter_beta: 0 disables the post filter */
 int dfx_stream_set_channels(dfx_stream_state *s, int channels, int reduce_mask); /* rows per stream; 0 none / 1 max / 2 mean */
 int dfx_stream_set_gating(dfx_stream_state *s, int enable);              /* DfTract::process's per-frame stage decisions, per stream */
@@ -454,6 +467,26 @@ int dfx_stream_process_pcm16(dfx_stream_state *s, const int16_t *x, int64_t n_fr
  * with float, 16-bit PCM and either law from call to call, and a stream may move between handles fed different formats at the same rate. */
 int dfx_stream_process_g711(dfx_stream_state *s, const uint8_t *x, int law, int64_t n_frames, uint8_t *y, float *lsnr,
                             const unsigned char *active, void *stream);
+/* Clips that end inside a call.  A stream has no end: the last `lookahead` frames of a clip only come out when more hops are fed, and the
+ * features of fed silence are not the zero padding the batch path puts behind a clip (MF.DF's, df/multiframe.py:72-76, and pad_feat's,
+ * df/deepfilternet3.py:359,409-410).  dfx_stream_process_ends is dfx_stream_process (x_format DFX_FMT_F32: float x, y) or
+ * dfx_stream_process_pcm16 (DFX_FMT_PCM16: int16 x, y; anything else DFX_ERR_INVALID_ARG) with valid_hops: a HOST array [streams], NULL =
+ * all n_frames.  valid_hops[b] = v, 0 <= v <= n_frames, says that the first v hops of this call are the last frames of row b's clip; every
+ * later hop of the row — the rest of this call and all hops of later calls, whichever entry point makes them — lies behind the clip's end
+ * until the row is reset (dfx_stream_reset_streams, dfx_stream_reset, or a stream imported into the slot).  Behind the end the row's spectrum
+ * and its normalised ERB and DF features are zero wherever the network and the deep filter read them (rule (2) of dfx_enhance_varlen); the hops
+ * are still processed, and they push the clip's last frames out.  The row then yields dfx_enhance(pad=0) of exactly its own frames, delayed
+ * by `lookahead` hops, its last frames included; past that its output, lsnr and state are unspecified until the reset.  Feed zeros behind a
+ * clip's samples.  A later call must pass 0 for a row that has ended (else DFX_ERR_INVALID_ARG, like a count outside [0, n_frames]; nothing is
+ * enqueued).  A call in which no row ends and none has ended enqueues exactly what dfx_stream_process / _pcm16 enqueue and gives the same bits.
+ * The counts travel to the device as kernel arguments (512 rows per launch): no upload, no wait.  Exact-fp32 and mask-only models are served;
+ * DFX_ERR_UNSUPPORTED, the handle not advanced, on gated or pausable handles, with channels > 1 and at a caller's sample rate.  In the
+ * handle-wide undelayed pass-through valid_hops is ignored.  Ends work inside the one-hop passes of a reset row's warm-up too. */
+int dfx_stream_process_ends(dfx_stream_state *s, const void *x, int x_format, int64_t n_frames, void *y, float *lsnr,
+                            const int64_t *valid_hops, void *stream);
+/* Device bytes of a handle of that size without a sample rate: what dfx_stream_create allocates plus the two staging rows
+ * [streams, max_frames * hop] the first 16-bit PCM or G.711 call adds.  No device access; refuses what dfx_stream_create refuses. */
+int dfx_stream_memory_bytes(const dfx_model *m, const dfx_state *st, int64_t streams, int max_frames, int64_t *bytes);
 /* Moving live streams between handles.  In the reference a caller's DfTract is a value the host owns; here a stream's state is its rows of
  * the handle's device arrays, in forms that change with the handle and the moment.  A snapshot of a stream is
  *   payload: one packed record of dfx_stream_snapshot_bytes() bytes in DEVICE memory — every state row of the stream's `channels` rows in a
