@@ -527,26 +527,41 @@ static __device__ __forceinline__ void dfx_copy_patch(float2 (&d)[4], const floa
 }
 static __device__ __forceinline__ void dfx_copy_patch(DfxPatchPs &d, const DfxPatchPs &s) { d = s; }
 
-// (the products and the epilogue of a c0 tile, behind the B operand's halves)
+// (the products and the epilogue of a c0 tile, behind the B operand's halves; two functions, so that a kernel can put other work between them)
 template <int C>
-static __device__ __forceinline__ void dfx_c0_tile_h3p(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
-                                                       const float4 (&bias0)[C / 16], float unscale0, const dfx_h8 ph, const dfx_h8 pl,
-                                                       bool keep, float (&dst)[C / 4]) {
-    constexpr int NT = C / 16;
-    f32x4 acc[NT];  // the NT chains are independent: term-major order keeps dependent MFMAs NT issues apart
+static __device__ __forceinline__ void dfx_c0_tile_h3_products(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16], const dfx_h8 ph,
+                                                               const dfx_h8 pl, f32x4 (&acc)[C / 16]) {
+    constexpr int NT = C / 16;   // the NT chains are independent: term-major order keeps dependent MFMAs NT issues apart
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0l[nt], ph, f32x4{0.f, 0.f, 0.f, 0.f});
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0h[nt], pl, acc[nt]);
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) acc[nt] = dfx_mfma_16x16x32_f16(w0h[nt], ph, acc[nt]);
+}
+template <int C>
+static __device__ __forceinline__ void dfx_c0_tile_h3_epilogue(const f32x4 (&acc)[C / 16], const float4 (&bias0)[C / 16], float unscale0, bool keep,
+                                                               float (&dst)[C / 4]) {
+    constexpr int NT = C / 16;
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) {
-        dst[4 * nt + 0] = keep ? fmaxf(acc[nt][0] * unscale0 + bias0[nt].x, 0.f) : 0.f;
-        dst[4 * nt + 1] = keep ? fmaxf(acc[nt][1] * unscale0 + bias0[nt].y, 0.f) : 0.f;
-        dst[4 * nt + 2] = keep ? fmaxf(acc[nt][2] * unscale0 + bias0[nt].z, 0.f) : 0.f;
-        dst[4 * nt + 3] = keep ? fmaxf(acc[nt][3] * unscale0 + bias0[nt].w, 0.f) : 0.f;
+        // (the value first, then the select: written as keep ? fmaxf(...) : 0.f each value can become a branch of its own — an exec save / restore
+        // per value, and a frame body cut into basic blocks that nothing is scheduled across)
+        const float v0 = fmaxf(acc[nt][0] * unscale0 + bias0[nt].x, 0.f), v1 = fmaxf(acc[nt][1] * unscale0 + bias0[nt].y, 0.f);
+        const float v2 = fmaxf(acc[nt][2] * unscale0 + bias0[nt].z, 0.f), v3 = fmaxf(acc[nt][3] * unscale0 + bias0[nt].w, 0.f);
+        dst[4 * nt + 0] = keep ? v0 : 0.f;
+        dst[4 * nt + 1] = keep ? v1 : 0.f;
+        dst[4 * nt + 2] = keep ? v2 : 0.f;
+        dst[4 * nt + 3] = keep ? v3 : 0.f;
     }
+}
+template <int C>
+static __device__ __forceinline__ void dfx_c0_tile_h3p(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
+                                                       const float4 (&bias0)[C / 16], float unscale0, const dfx_h8 ph, const dfx_h8 pl,
+                                                       bool keep, float (&dst)[C / 4]) {
+    f32x4 acc[C / 16];
+    dfx_c0_tile_h3_products<C>(w0h, w0l, ph, pl, acc);
+    dfx_c0_tile_h3_epilogue<C>(acc, bias0, unscale0, keep, dst);
 }
 template <int C>
 static __device__ __forceinline__ void dfx_c0_tile_h3(const dfx_h8 (&w0h)[C / 16], const dfx_h8 (&w0l)[C / 16],
@@ -1074,6 +1089,41 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
 // df_dec.df_convp with df_conv0 recomputed, fp16-split form of dfx_k_df_convp2<C, KT, true> (same run decomposition: a wave walks a
 // segment of frames for 16 bins of one clip).  The window holds the hi/lo halves of the last KT c0 frames (the B operands), the
 // A fragments [KT][C/32][hi,lo] are persistent: 3*KT*C/32 + 3*C/16 MFMAs per 16 bins and frame.
+#ifndef DFX_CPH_ABLATE
+#define DFX_CPH_ABLATE 0   /* dev (tools/dev/convp_bench.hip): 1 no output stores, 2 no patch loads (zero patches) */
+#endif
+#ifndef DFX_CPH_TRACE
+#define DFX_CPH_TRACE 0    /* dev: lane 0 of every workgroup sums the s_memtime ticks of a frame's parts into DfxCphArgs::trace[block][5] */
+#endif
+#ifndef DFX_CPH_PARENT_LOOP
+#define DFX_CPH_PARENT_LOOP 0   /* dev: 1 = the PS instance runs the unsplit instance's frame loop (the schedule before the rework), for A/B runs */
+#endif
+#ifndef DFX_CPH_VALU_C0
+#define DFX_CPH_VALU_C0 4     /* vector instructions asked for in the shadow of each of c0's matrix ops (the next patch's addresses) */
+#endif
+#ifndef DFX_CPH_VALU_TAPS
+#define DFX_CPH_VALU_TAPS 5   /* ... and of each matrix op of the older frames' taps (c0's epilogue and split) */
+#endif
+// the region up to here (from the last DFX_SCHED_BARRIER): N matrix ops, V vector instructions in the shadow of each (dfx_gru_pair.h, pass B)
+template <int N, int V>
+static __device__ __forceinline__ void dfx_sched_mfma_valu() {
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        DFX_SCHED_GROUP(0x008, 1);
+        DFX_SCHED_GROUP(0x002, V);
+    }
+}
+#if DFX_CPH_TRACE
+#define DFX_CPH_TICK(i)                                                               \
+    do {                                                                                \
+        unsigned long long now_;                                                        \
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(now_)::"memory");    \
+        tk[i] += now_ - tlast;                                                          \
+        tlast = now_;                                                                   \
+    } while (0)
+#else
+#define DFX_CPH_TICK(i) do { } while (0)
+#endif
 struct DfxCphArgs {
     const float *feat;   // [B, T, Fd, 2]
     const dfx_h8 *w0f;   // [C/16][hi,lo][64]       folded df_conv0
@@ -1089,7 +1139,30 @@ struct DfxCphArgs {
     int64_t feat_T = 0;       // as in DfxC01hArgs
     const int *t_zero_rows = nullptr;   // non-null: t_zero per clip (streams of a handle that started over at different hops); null: the scalar
     const uint2 *feat_ps = nullptr;     // PS instances of dfx_k_df_convp_h3: the pre-split copy of feat (as in DfxDfEncArgs)
+#if DFX_CPH_TRACE
+    unsigned long long *trace = nullptr;   // dev: [block][5] ticks of the patch wait / c0 / taps / stores and the frames they were summed over
+#endif
 };
+// (a lane's patch registers are complete from here on: the wait for their loads stands HERE)
+static __device__ __forceinline__ void dfx_patch_ready(float2 (&p)[4]) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        DFX_OPAQUE(p[i].x);
+        DFX_OPAQUE(p[i].y);
+    }
+}
+static __device__ __forceinline__ void dfx_patch_ready(DfxPatchPs &p) {
+    DFX_OPAQUE(p.h);
+    DFX_OPAQUE(p.l);
+}
+template <typename E>
+static __device__ __forceinline__ void dfx_loads_ready(E (&ld)[4]) {   // (the same for four elements as they were loaded)
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        DFX_OPAQUE(ld[i].x);
+        DFX_OPAQUE(ld[i].y);
+    }
+}
 
 // (Two 16-bin blocks per wave side by side — two independent tiles in one instruction stream, df_conv0's fragments in LDS to make room for the
 // second window — was built and measured the same: 2.07 ms alone, 14.13 / 14.07 vs 14.10 / 14.17 ms per step.)
@@ -1139,6 +1212,9 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
     for (int r = 0; r < 4; ++r) biasr[r] = A.bias[4 * q + r];
     const int64_t nruns = A.B * A.nfb * A.nseg;
     float amax = 0.f;   // range guard of the f16 splits
+#if DFX_CPH_TRACE
+    unsigned long long tk[4] = {0, 0, 0, 0}, tlast, nframes = 0;
+#endif
     // Round 4: the run decomposition is WAVE-UNIFORM (clip, bin block, segment and every frame index live in scalar registers; the wave index
     // goes through readfirstlane) and a lane adds its bin and its taps as 32-bit element offsets from the scalar base of its clip's frame — the
     // per-lane 64-bit (clip, frame, bin) arithmetic and the division of the tap index by 3 at every patch load were ~40 % of the kernel's
@@ -1176,7 +1252,38 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
                 // branch-free: a tap outside reads the clip's first element (always there) and is zeroed by a select — an exec-masked load is a
                 // save / branch / restore sequence per tap
                 const bool in = ok && tin - Lk >= 0 && tin < T32 && fin >= 0 && fin < Fd;
-                dfx_put_tap(rw, i, in, feat2[in ? pbase + (unsigned)toff[i] : cbase]);
+                if constexpr (DFX_CPH_ABLATE & 2) dfx_put_tap(rw, i, false, Elem{});
+                else dfx_put_tap(rw, i, in, feat2[in ? pbase + (unsigned)toff[i] : cbase]);
+            }
+        };
+        // the same patch in two steps: its four loads as they come from memory, requested a frame ahead, and — behind the wait for them, a frame
+        // later — the zero selects.  (patch() as one step puts the selects, and with them the wait, into the frame that REQUESTS the loads.)
+        auto patch_in = [&](int t, bool ok, int i) {   // (patch()'s test with & for &&: no branches, the frame body stays one basic block)
+            return ok & (t + tdt[i] - Lk >= 0) & (t + tdt[i] < T32) & (f + tdf[i] >= 0) & (f + tdf[i] < Fd);
+        };
+        auto patch_load = [&](int t, bool ok, Elem (&ld)[4]) {
+            const unsigned pbase = cbase + (unsigned)(t * Fd + f);
+#pragma unroll
+            for (int i = 0; i < 4; ++i) {
+                if constexpr (DFX_CPH_ABLATE & 2) ld[i] = Elem{};
+                else {
+                    const bool in = patch_in(t, ok, i);
+                    ld[i] = feat2[in ? pbase + (unsigned)toff[i] : cbase];   // (a tap outside: the clip's first element, as in patch())
+                }
+            }
+        };
+        auto patch_select = [&](int t, bool ok, const Elem (&ld)[4], Patch &rw) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) dfx_put_tap(rw, i, patch_in(t, ok, i), ld[i]);
+        };
+        const bool st_on = !(DFX_CPH_ABLATE & 1) || A.NO < 0;   // (the ablated stores stay in the code behind a test that is never true)
+        // the two float2 of a lane's outputs of frame t
+        auto store_out = [&](int64_t t, const float2 (&v)[2]) {
+            if (fvalid && st_on) {
+                float *op = A.out + ((b * (A.NO / 2) * A.T + t) * A.Fd + f) * 2;
+#pragma unroll
+                for (int h = 0; h < 2; ++h)
+                    if (4 * q + 2 * h < A.NO) *reinterpret_cast<float2 *>(op + (int64_t)(2 * q + h) * A.T * A.Fd * 2) = v[h];
             }
         };
         dfx_h8 xh[KT][KC], xl[KT][KC];  // frame tau lives in slot (tau - t0) mod KT
@@ -1184,7 +1291,15 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         auto make_frame = [&](dfx_h8 (&dh)[KC], dfx_h8 (&dl)[KC], int64_t tau, const Patch &rw) {
             float c0v[CPL];
             // frames before the clip are the zero padding of c0 itself (wave-uniform test)
-            dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, rw, fvalid && tau >= tz, c0v, amax);
+            if constexpr (PS && !DFX_CPH_PARENT_LOOP) {   // (the warm-up frames of the batch passes' loop: the same tile in its two halves, a guard between)
+                dfx_h8 p_h, p_l;
+                dfx_c0_patch_ps(rw, p_h, p_l);
+                f32x4 acc0[NT];
+                dfx_c0_tile_h3_products<C>(w0h, w0l, p_h, p_l, acc0);
+                DFX_MFMA_GUARD();   // (the epilogue's first reads were found 8-10 wait states behind the last product, past a change of exec)
+                dfx_c0_tile_h3_epilogue<C>(acc0, bias0, A.unscale0, fvalid && tau >= tz, c0v);
+            } else
+                dfx_c0_tile_h3<C>(w0h, w0l, bias0, A.unscale0, rw, fvalid && tau >= tz, c0v, amax);
 #pragma unroll
             for (int kc = 0; kc < KC; ++kc) dfx_split8_g(c0v + 8 * kc, dh[kc], dl[kc], amax);
         };
@@ -1194,45 +1309,145 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
             patch((int)tau, fvalid && tau >= 0, raw);
             make_frame(xh[sl], xl[sl], tau, raw);
         });
-        patch((int)t0, fvalid, raw);
-        for (int64_t tb = t0; tb < t1; tb += KT) {
-            dfx_static_for<0, KT>([&](auto pc) {
-                constexpr int ph = decltype(pc)::value;
-                const int64_t t = tb + ph;
-                if (t < t1) {  // wave-uniform
-                    Patch cur;
-                    dfx_copy_patch(cur, raw);
-                    patch((int)t + 1, fvalid && t + 1 < t1, raw);
-                    make_frame(xh[ph], xl[ph], t, cur);
-                    // three independent accumulation chains (one per product term), summed small-to-large at the end
-                    f32x4 aa = f32x4{0.f, 0.f, 0.f, 0.f}, ab = aa, ac = aa;
-                    dfx_static_for<0, KT>([&](auto kcn) {
-                        constexpr int k = decltype(kcn)::value;
-                        constexpr int sl = (ph + 1 + k) % KT;  // tap k reads frame t - (KT-1) + k
+#if DFX_CPH_TRACE
+        asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");   // (the warm-up frames are not counted)
+        nframes += (unsigned long long)(t1 - t0);
+#endif
+        if constexpr (PS && !DFX_CPH_PARENT_LOOP) {
+            // The batch passes' schedule.  Same products in the same order per accumulator as the loop below (three chains, taps ascending,
+            // k-chunks inner, (aa + ab) + ac; the c0 tile and the split are the same functions), so the same bits; what differs is WHERE things stand:
+            // - A frame's outputs are held in four registers and stored in the NEXT frame's body, behind that frame's patch wait and in front of
+            //   the loads it requests.  Loads and stores share the in-order vmcnt, and the stores sit in a branch of their own, which the compiler
+            //   cannot count: stored at the end of their own frame, the next patch wait, vmcnt(0), also waited for their acknowledgement — a full
+            //   store round trip per frame.  Now no patch wait covers a store younger than a frame.
+            // - A patch is requested TWO frames ahead (patch_load) and zero-selected in the frame that uses it (patch_select): as one step the selects,
+            //   and with them the wait, stood in the frame that requested the loads.
+            // - The frame body is ONE basic block (the stores' branch stands in front of it), in the order c0's products, the taps of the KT - 1
+            //   older frames (their window slots exist before this frame's c0 does), c0's epilogue and split, the new frame's tap — last in each
+            //   chain, as before — and the scheduler is asked to lay the vector work under the matrix ops: the address arithmetic of the
+            //   next patch under c0's products, c0's epilogue and split under the older frames' taps.
+            float2 held[2] = {make_float2(0.f, 0.f), make_float2(0.f, 0.f)};
+            // two sets of load registers, frames t0 + even and t0 + odd: the frame loop is unrolled over both a whole window and a whole pair
+            constexpr int U = (KT % 2) ? 2 * KT : KT;
+            Elem ld2[2][4];
+            patch_load((int)t0, fvalid, ld2[0]);
+            patch_load((int)t0 + 1, fvalid && t0 + 1 < t1, ld2[1]);
+            // (The U frames of a round are NESTED — frame i + 1 stands inside frame i's `t < t1` — and a round that ends early leaves the loop: a
+            // frame body's only predecessor is the body before it, so the compiler counts the four younger loads between a patch wait and the
+            // loads it waits for, vmcnt(4).  As U tests side by side, each with a path around its body, every patch wait was vmcnt(0).)
+            for (int64_t tb = t0; tb < t1; tb += U) {
+                bool whole = false;
+                auto frame = [&](auto &self, auto pc) {
+                    constexpr int ph = decltype(pc)::value % KT;
+                    Elem(&ld)[4] = ld2[decltype(pc)::value & 1];
+                    const int64_t t = tb + decltype(pc)::value;
+                    if (t < t1) {  // wave-uniform
+                        dfx_loads_ready(ld);
+                        DFX_CPH_TICK(0);
+                        DFX_SCHED_BARRIER();
+                        if (t > t0) store_out(t - 1, held);   // (wave-uniform test)
+                        DFX_CPH_TICK(3);
+                        DFX_SCHED_BARRIER();
+                        Patch cur;
+                        patch_select((int)t, fvalid, ld, cur);
+                        patch_load((int)t + 2, fvalid && t + 2 < t1, ld);
+                        dfx_h8 p_h, p_l;
+                        dfx_c0_patch_ps(cur, p_h, p_l);
+                        f32x4 acc0[NT];
+                        dfx_c0_tile_h3_products<C>(w0h, w0l, p_h, p_l, acc0);
+                        dfx_sched_mfma_valu<3 * NT, DFX_CPH_VALU_C0>();
+                        DFX_SCHED_BARRIER();
+                        f32x4 aa = f32x4{0.f, 0.f, 0.f, 0.f}, ab = aa, ac = aa;
+                        auto tap = [&](auto kcn) {
+                            constexpr int k = decltype(kcn)::value;
+                            constexpr int sl = (ph + 1 + k) % KT;  // tap k reads frame t - (KT-1) + k
 #pragma unroll
-                        for (int kc = 0; kc < KC; ++kc) {
-                            const dfx_h8 whk = wh[k][kc], wlk = wl[k][kc];
-                            aa = dfx_mfma_16x16x32_f16(wlk, xh[sl][kc], aa);
-                            ab = dfx_mfma_16x16x32_f16(whk, xl[sl][kc], ab);
-                            ac = dfx_mfma_16x16x32_f16(whk, xh[sl][kc], ac);
-                        }
-                    });
-                    f32x4 acc;
+                            for (int kc = 0; kc < KC; ++kc) {
+                                const dfx_h8 whk = wh[k][kc], wlk = wl[k][kc];
+                                aa = dfx_mfma_16x16x32_f16(wlk, xh[sl][kc], aa);
+                                ab = dfx_mfma_16x16x32_f16(whk, xl[sl][kc], ab);
+                                ac = dfx_mfma_16x16x32_f16(whk, xh[sl][kc], ac);
+                            }
+                        };
+                        dfx_static_for<0, KT - 1>(tap);
+                        float c0v[CPL];
+                        dfx_c0_tile_h3_epilogue<C>(acc0, bias0, A.unscale0, fvalid && t >= tz, c0v);
 #pragma unroll
-                    for (int r = 0; r < 4; ++r) acc[r] = (aa[r] + ab[r]) + ac[r];
-                    if (fvalid) {
-                        float *op = A.out + ((b * (A.NO / 2) * A.T + t) * A.Fd + f) * 2;
+                        for (int kc = 0; kc < KC; ++kc) dfx_split8_g(c0v + 8 * kc, xh[ph][kc], xl[ph][kc], amax);
+                        dfx_sched_mfma_valu<3 * KC * (KT - 1), DFX_CPH_VALU_TAPS>();
+                        DFX_SCHED_BARRIER();
+                        tap(std::integral_constant<int, KT - 1>{});
+                        f32x4 acc;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[r] = (aa[r] + ab[r]) + ac[r];
 #pragma unroll
                         for (int h = 0; h < 2; ++h)
-                            if (4 * q + 2 * h < A.NO)
-                                *reinterpret_cast<float2 *>(op + (int64_t)(2 * q + h) * A.T * A.Fd * 2) =
-                                    make_float2(fmaxf(acc[2 * h] * A.unscale + biasr[2 * h], 0.f),
-                                                fmaxf(acc[2 * h + 1] * A.unscale + biasr[2 * h + 1], 0.f));
+                            held[h] = make_float2(fmaxf(acc[2 * h] * A.unscale + biasr[2 * h], 0.f),
+                                                  fmaxf(acc[2 * h + 1] * A.unscale + biasr[2 * h + 1], 0.f));
+                        DFX_CPH_TICK(1);
+                        DFX_SCHED_BARRIER();
+                        if constexpr (decltype(pc)::value + 1 < U) self(self, std::integral_constant<int, decltype(pc)::value + 1>{});
+                        else whole = true;
                     }
-                }
-            });
+                };
+                frame(frame, std::integral_constant<int, 0>{});
+                if (!whole) break;
+            }
+            if (t1 > t0) store_out(t1 - 1, held);   // the last frame of the segment
+        } else {   // the unsplit instance: the loop as it was, the in-tree reference for the bits (test hook DFX_C0_PRESPLIT=0)
+            patch((int)t0, fvalid, raw);
+            for (int64_t tb = t0; tb < t1; tb += KT) {
+                dfx_static_for<0, KT>([&](auto pc) {
+                    constexpr int ph = decltype(pc)::value;
+                    const int64_t t = tb + ph;
+                    if (t < t1) {  // wave-uniform
+                        Patch cur;
+                        dfx_copy_patch(cur, raw);
+#if DFX_CPH_TRACE
+                        dfx_patch_ready(cur);
+                        DFX_CPH_TICK(0);
+#endif
+                        patch((int)t + 1, fvalid && t + 1 < t1, raw);
+                        make_frame(xh[ph], xl[ph], t, cur);
+                        DFX_CPH_TICK(1);
+                        // three independent accumulation chains (one per product term), summed small-to-large at the end
+                        f32x4 aa = f32x4{0.f, 0.f, 0.f, 0.f}, ab = aa, ac = aa;
+                        dfx_static_for<0, KT>([&](auto kcn) {
+                            constexpr int k = decltype(kcn)::value;
+                            constexpr int sl = (ph + 1 + k) % KT;  // tap k reads frame t - (KT-1) + k
+#pragma unroll
+                            for (int kc = 0; kc < KC; ++kc) {
+                                const dfx_h8 whk = wh[k][kc], wlk = wl[k][kc];
+                                aa = dfx_mfma_16x16x32_f16(wlk, xh[sl][kc], aa);
+                                ab = dfx_mfma_16x16x32_f16(whk, xl[sl][kc], ab);
+                                ac = dfx_mfma_16x16x32_f16(whk, xh[sl][kc], ac);
+                            }
+                        });
+                        f32x4 acc;
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) acc[r] = (aa[r] + ab[r]) + ac[r];
+                        DFX_CPH_TICK(2);
+                        if (fvalid && st_on) {
+                            float *op = A.out + ((b * (A.NO / 2) * A.T + t) * A.Fd + f) * 2;
+#pragma unroll
+                            for (int h = 0; h < 2; ++h)
+                                if (4 * q + 2 * h < A.NO)
+                                    *reinterpret_cast<float2 *>(op + (int64_t)(2 * q + h) * A.T * A.Fd * 2) =
+                                        make_float2(fmaxf(acc[2 * h] * A.unscale + biasr[2 * h], 0.f),
+                                                    fmaxf(acc[2 * h + 1] * A.unscale + biasr[2 * h + 1], 0.f));
+                        }
+                        DFX_CPH_TICK(3);
+                    }
+                });
+            }
         }
     }
+#if DFX_CPH_TRACE
+    if (tid == 0 && A.trace) {
+        for (int i = 0; i < 4; ++i) A.trace[(size_t)blockIdx.x * 5 + i] = tk[i];
+        A.trace[(size_t)blockIdx.x * 5 + 4] = nframes;
+    }
+#endif
     if (amax >= DFX_H3_LIMIT && A.err) dfx_raise(A.err + 1);
 }
 
