@@ -36,6 +36,12 @@ class ModelCfg(C.Structure):
         ("pf_beta", C.c_float), ("norm_alpha", C.c_float)] + [(n, C.c_int32) for n in ("emb_gru_skip_enc", "emb_gru_skip", "enc_concat")]
 
 
+class FlacInfo(C.Structure):
+    """dfx_flac_info (include/dfx.h)"""
+    _fields_ = [(n, C.c_int32) for n in ("sample_rate", "channels", "bits_per_sample", "min_block", "max_block", "first_frame")] + [
+        ("total_samples", C.c_int64), ("md5", C.c_uint8 * 16)]
+
+
 _vp, _i, _i64, _f = C.c_void_p, C.c_int, C.c_int64, C.c_float
 _fp = C.c_void_p  # data pointers are passed as raw addresses (device or, in the interpreter build, host)
 _u64p = C.POINTER(C.c_uint64)
@@ -102,6 +108,9 @@ SIGNATURES = {
     "dfx_f32_to_pcm16": (_i, [_fp, _i64, _vp, _vp]),
     "dfx_g711_decode": (_i, [_vp, _i, _i64, _vp, _i, _vp]),
     "dfx_g711_encode": (_i, [_vp, _i, _i, _i64, _vp, _vp]),
+    "dfx_flac_probe": (_i, [_vp, _i64, _vp]),
+    "dfx_flac_workspace_bytes": (_i, [_i64, C.POINTER(_i64), _vp, C.POINTER(_i64)]),
+    "dfx_flac_decode": (_i, [_vp, _i64, _i64, C.POINTER(_i64), C.POINTER(_i64), _vp, C.POINTER(_i64), _vp, _i64, _vp, _vp, _i64, _vp]),
     "dfx_resampler_create": (_i,[_i, _i, _i, C.c_double, _i, C.c_double, C.POINTER(_vp)]),
     "dfx_resampler_free": (None, [_vp]),
     "dfx_resampler_out_len": (_i64, [_vp, _i64]),

@@ -130,6 +130,7 @@ extern "C" int dfx_f32_to_pcm16(const float *x, int64_t n, int16_t *out, void *s
 }
 
 #include "dfx_g711.h"
+#include "dfx_flac.h"
 
 static double bessel_i0(double x) {  // torch.i0: power series (converges quickly for the beta range used here, <= ~15)
     double sum = 1.0, term = 1.0;

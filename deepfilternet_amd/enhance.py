@@ -581,6 +581,34 @@ def _unpack_long(yh, ev, items) -> None:
         dst.copy_(yh[j, lo:hi])
 
 
+# FLAC files decoded per io.decode_flac call (and bytes: their compressed size), consecutive FLAC inputs only
+_FLAC_GROUP_FILES = 512
+_FLAC_GROUP_BYTES = 1 << 30
+
+
+def _load_inputs(files, sr: int, method: str):
+    """(file, audio, meta) of every input in order, loaded as enhance_files wants them (int16 when no resampling is needed); consecutive FLAC
+    files are decoded together."""
+    from .io import is_flac, load_audio, load_flac_files
+
+    i = 0
+    while i < len(files):
+        if not is_flac(files[i]):
+            audio, meta = load_audio(files[i], sr=sr, verbose=False, method=method, pcm16=True)
+            yield files[i], audio, meta
+            i += 1
+            continue
+        group, size = [], 0
+        while i < len(files) and len(group) < _FLAC_GROUP_FILES and is_flac(files[i]):
+            size += os.path.getsize(files[i])
+            if group and size > _FLAC_GROUP_BYTES:
+                break
+            group.append(files[i])
+            i += 1
+        for file, (audio, meta) in zip(group, load_flac_files(group, sr=sr, verbose=False, method=method, pcm16=True)):
+            yield file, audio, meta
+
+
 def enhance_files(model: DfNet, df_state: DF, input_files, output_dir: Optional[str] = None, suffix: Optional[str] = None,
                   compensate_delay: bool = True, atten_lim_db: Optional[float] = None, method: str = "sinc_fast"):
     """The body of the reference's file loop, ``df.enhance.main`` (enhance.py:73-89), without its argument parser: every file is
@@ -592,7 +620,7 @@ def enhance_files(model: DfNet, df_state: DF, input_files, output_dir: Optional[
     The files are read in order and gathered into windows of at most _FILE_WINDOW_ROWS channels whose workspace, as one pass, fits the cap of
     ``enhance()``; a window is enhanced with ``enhance_batch`` — every file gets the samples ``enhance()`` gives it alone, so the files written
     are byte for byte those of one ``enhance()`` per file — and written before the next window is read."""
-    from .io import load_audio, resample, save_audio
+    from .io import resample, save_audio
 
     sr = df_state.sr()
     out, win, lens = [], [], []
@@ -602,12 +630,13 @@ def enhance_files(model: DfNet, df_state: DF, input_files, output_dir: Optional[
         for (file, _, meta), e in zip(win, enhanced):
             if e.dtype != torch.int16:
                 e = resample(e, sr, meta.sample_rate, method=method)
+            if meta.encoding == "FLAC":   # the outputs are WAVE files, as in the reference: a FLAC input's name gets the extension of what is written
+                file = os.path.splitext(file)[0] + ".wav"
             out.append(save_audio(file, e, sr=meta.sample_rate, output_dir=output_dir, suffix=suffix))
         win.clear()
         lens.clear()
 
-    for file in input_files:
-        audio, meta = load_audio(file, sr=sr, verbose=False, method=method, pcm16=True)   # int16 when no resampling is needed
+    for file, audio, meta in _load_inputs(list(input_files), sr, method):
         more = lens + [audio.shape[-1]] * audio.shape[0]
         if win and len(more) > _FILE_WINDOW_ROWS:
             flush()

@@ -1,7 +1,8 @@
 """Host-side mirror of ``df/io.py`` (load_audio :25-57, save_audio :60-84, get_resample_params :92-111, resample :114-116) with
 the sample work on the MI355X: the file is parsed on the host (a RIFF/WAVE reader / writer of its own, below — the reference goes
 through torchaudio, which is not a dependency here; 8 / 16 / 24 / 32-bit integer PCM, 32 / 64-bit IEEE float and 8-bit G.711 A-law /
-mu-law, plain or WAVE_FORMAT_EXTENSIBLE), the int16 -> float scaling, the G.711 codec, the sample-rate conversion and the float -> int16 encoding run as HIP kernels
+mu-law, plain or WAVE_FORMAT_EXTENSIBLE; FLAC files are not parsed on the host at all: their bytes go up as they are and ``decode_flac`` decodes them on
+the device, csrc/dfx_flac.h), the int16 -> float scaling, the G.711 codec, the sample-rate conversion and the float -> int16 encoding run as HIP kernels
 (csrc/dfx_io.hip), so a file -> file loop like ``enhance.main`` (enhance.py:73-89) keeps its audio on the device between decode and
 encode (the rarer sample formats are scaled with torch ops on the device):
 
@@ -348,6 +349,155 @@ def _write_riff(file: str, data: np.ndarray, sr: int, is_float: bool, law: Optio
         f.write(b"RIFF" + struct.pack("<I", len(body)) + body)
 
 
+def is_flac(file: str) -> bool:
+    """Does the file start with the ``fLaC`` marker, or with an ID3v2 tag (which no RIFF file starts with: what follows it is left to the probe)?"""
+    with open(file, "rb") as f:
+        head = f.read(4)
+    return head == b"fLaC" or head[:3] == b"ID3"
+
+
+def _as_bytes(blob) -> np.ndarray:
+    if isinstance(blob, torch.Tensor):
+        if blob.dtype != torch.uint8:
+            raise TypeError("a FLAC stream is given as bytes or as a uint8 array")
+        return blob.detach().cpu().contiguous().reshape(-1).numpy()
+    if isinstance(blob, np.ndarray):
+        if blob.dtype != np.uint8:
+            raise TypeError("a FLAC stream is given as bytes or as a uint8 array")
+        return np.ascontiguousarray(blob).reshape(-1)
+    return np.frombuffer(blob, dtype=np.uint8)
+
+
+def flac_probe(blob, name: str = "stream") -> "_lib.FlacInfo":
+    """STREAMINFO of a FLAC stream (``dfx_flac_probe``: host arithmetic): sample_rate, channels, bits_per_sample, min_block, max_block,
+    first_frame (byte offset), total_samples, md5.  RuntimeError for what is not decoded: Ogg-FLAC, no STREAMINFO, more than 8 channels,
+    bit depths outside 8 .. 24."""
+    b = _as_bytes(blob)
+    info = _lib.FlacInfo()
+    rc = _lib.lib().dfx_flac_probe(C.c_void_p(b.ctypes.data), int(b.size), C.byref(info))
+    if rc != _lib.DFX_OK:
+        raise RuntimeError(f"{name}: {_lib.lib().dfx_last_error().decode()}")
+    return info
+
+
+def _align16(n: int) -> int:
+    return (n + 15) // 16 * 16
+
+
+def decode_flac(blobs, pcm16: bool = False, names=None, infos_out: Optional[list] = None) -> list:
+    """The bytes of many FLAC files through ONE ``dfx_flac_decode`` call: the compressed bytes go up as they are (one buffer, one copy), the
+    decoder runs on the device, frames and channels of every stream side by side.  ``blobs``: ``bytes`` / uint8 arrays, one per stream.
+    Returns one ``[C, T]`` tensor per stream, on the device: float32 = sample / 2^(bits - 1) — what ``load_audio`` returns for a WAVE file of
+    the same samples —, or with ``pcm16=True`` int16 for the streams of at most 16 bits (a stream below 16 bits fills the int16 from the top).
+    A stream with a frame that was lost (CRC-16, cut short, damaged header) raises RuntimeError naming it (``names``) and the count.
+    ``infos_out``: a list that receives every stream's ``flac_probe`` result."""
+    arrs = [_as_bytes(b) for b in blobs]
+    n = len(arrs)
+    names = list(names) if names is not None else [f"stream {i}" for i in range(n)]
+    infos = [flac_probe(a, nm) for a, nm in zip(arrs, names)]
+    if infos_out is not None:
+        infos_out.extend(infos)
+    if n == 0:
+        return []
+    for I, a, nm in zip(infos, arrs, names):
+        if I.total_samples == 0 and a.size > I.first_frame:
+            raise RuntimeError(f"{nm}: a FLAC stream whose STREAMINFO does not state its length (total samples 0) is not decoded")
+    dev = _lib.device()
+    cuda = dev.type == "cuda"
+    offs, at = [], 0
+    for a in arrs:
+        offs.append(at)
+        at = _align16(at + int(a.size))
+    host = torch.zeros(max(at, 16), dtype=torch.uint8, pin_memory=cuda)
+    hv = host.numpy()
+    for a, o in zip(arrs, offs):
+        hv[o:o + a.size] = a
+    blob = host.to(dev, non_blocking=cuda)
+    if blob.data_ptr() == host.data_ptr():
+        blob = host
+    out_offs, oat = [], 0
+    for I in infos:
+        out_offs.append(oat)
+        oat = _align16(oat + (2 if I.bits_per_sample <= 16 else 4) * I.channels * I.total_samples)
+    out = torch.empty(max(oat, 16), dtype=torch.uint8, device=dev)
+    status = torch.zeros((n, 4), dtype=torch.int64, device=dev)
+    i64 = C.c_int64 * n
+    lens = i64(*[int(a.size) for a in arrs])
+    info_arr = (_lib.FlacInfo * n)(*infos)
+    need = C.c_int64()
+    L = _lib.lib()
+    _lib.check(L.dfx_flac_workspace_bytes(n, lens, C.cast(info_arr, C.c_void_p), C.byref(need)))
+    ws = torch.empty(int(need.value), dtype=torch.uint8, device=dev)
+    _lib.check(L.dfx_flac_decode(_lib.ptr(blob), int(blob.numel()), n, i64(*offs), lens, C.cast(info_arr, C.c_void_p), i64(*out_offs), _lib.ptr(out),
+                                 int(out.numel()), _lib.ptr(status), _lib.ptr(ws), int(ws.numel()), _lib.stream()))
+    st = status.cpu().numpy()
+    res = []
+    for i, I in enumerate(infos):
+        good, lost, written, flags = (int(v) for v in st[i])
+        if lost or flags or written != I.total_samples:
+            raise RuntimeError(f"{names[i]}: {lost} FLAC frame(s) lost (CRC-16 failed, stream cut short or header damaged); {good} decoded, "
+                               f"{written} of {I.total_samples} samples" + ("; more sync-code look-alikes than the decoder lists" if flags else ""))
+        i16 = I.bits_per_sample <= 16
+        nb = (2 if i16 else 4) * I.channels * I.total_samples
+        x = out[out_offs[i]:out_offs[i] + nb].view(torch.int16 if i16 else torch.float32).reshape(I.channels, I.total_samples)
+        res.append(x if (not i16 or pcm16) else pcm16_to_float(x))
+    return res
+
+
+def flac_md5(audio: torch.Tensor, bits: int) -> bytes:
+    """The MD5 STREAMINFO carries: over the interleaved samples, little endian, ceil(bits / 8) bytes each.  ``audio``: what ``decode_flac``
+    returned for the stream (a device -> host copy)."""
+    import hashlib
+
+    a = audio.detach().cpu()
+    if a.dtype == torch.int16:
+        v = a.numpy().astype(np.int64) >> max(0, 16 - bits)
+    else:
+        v = np.round(a.numpy().astype(np.float64) * float(1 << (bits - 1))).astype(np.int64)
+    nb = (bits + 7) // 8
+    raw = np.ascontiguousarray(v.T).astype("<i8").view(np.uint8).reshape(-1, 8)[:, :nb]
+    return hashlib.md5(np.ascontiguousarray(raw).tobytes()).digest()
+
+
+def load_flac_files(files, sr: Optional[int] = None, verbose: bool = True, method: str = "sinc_fast", pcm16: bool = False,
+                    frame_offset: int = 0, num_frames: int = -1, verify_md5: bool = False) -> list:
+    """``load_audio`` of several FLAC files, decoded together (one ``decode_flac`` call): [(audio, meta)] in input order."""
+    blobs = []
+    for f in files:
+        with open(f, "rb") as fh:
+            blobs.append(fh.read())
+    infos: list = []
+    native = decode_flac(blobs, pcm16=True, names=files, infos_out=infos)
+    res = []
+    for file, x, I in zip(files, native, infos):
+        if verify_md5 and any(I.md5) and flac_md5(x, I.bits_per_sample) != bytes(I.md5):
+            raise RuntimeError(f"{file}: the decoded samples do not have the MD5 that STREAMINFO states")
+        total, rate = int(I.total_samples), int(I.sample_rate)
+        frames = num_frames
+        if frames is not None and frames > 0 and sr is not None:
+            if rate < sr:
+                raise RuntimeError(f"{file}: num_frames with a file rate ({rate}) below the requested rate ({sr}) selects no frames (df/io.py:46-47)")
+            frames *= rate // sr
+        off = min(max(int(frame_offset or 0), 0), total)
+        n = total - off if frames is None or frames <= 0 else min(int(frames), total - off)
+        x = x[:, off:off + n]
+        meta = AudioMetaData(sample_rate=rate, num_frames=total, num_channels=int(I.channels), bits_per_sample=int(I.bits_per_sample),
+                             encoding="FLAC")
+        if x.dtype == torch.int16:
+            if pcm16 and (sr is None or rate == sr):
+                res.append((x.contiguous(), meta))
+                continue
+            x = pcm16_to_float(x)
+        if sr is not None and rate != sr:
+            if verbose:
+                import warnings
+
+                warnings.warn(f"Audio sampling rate does not match model sampling rate ({rate}, {sr}). Resampling...")
+            x = resample(x, rate, sr, method=method)
+        res.append((x.contiguous(), meta))
+    return res
+
+
 def load_audio(file: str, sr: Optional[int] = None, verbose: bool = True, **kwargs) -> Tuple[torch.Tensor, AudioMetaData]:
     """io.py:25-57: audio [C, T] float32 (on the device), resampled to ``sr`` when given; ``method=`` selects the resampler set.
     Sample formats as torchaudio.load(normalize=True) scales them: int16 / 32768 (a HIP kernel), 24-bit / 2^23, int32 / 2^31,
@@ -357,14 +507,24 @@ def load_audio(file: str, sr: Optional[int] = None, verbose: bool = True, **kwar
     A-law / mu-law files (``meta.encoding`` "ALAW" / "ULAW", 8 bits): the codes' 16-bit linear values / 32768 (``g711_to_float``);
     read from the extended 'fmt ' chunk (18 bytes or more, or extensible) that non-PCM formats carry — a G.711 tag in a 16-byte PCM header is
     refused as before.
+    FLAC files (recognised by their ``fLaC`` marker, or an ID3v2 tag in front of it, not by their name; native FLAC of 8 to 24 bits and up to 8
+    channels; ``meta.encoding`` "FLAC", ``bits_per_sample`` / ``num_frames`` / ``sample_rate`` from STREAMINFO): the file's bytes go up as they
+    are and are decoded on the device (``decode_flac``); the result is that of a WAVE file of the same samples, ``pcm16=True`` hands back
+    int16 for streams of at most 16 bits.  A frame that fails its CRC raises RuntimeError with the file's name and the count;
+    ``verify_md5=True`` also checks a non-zero STREAMINFO MD5 (a device -> host copy).  Ogg-FLAC and 32-bit FLAC are refused; FLAC is not written.
     ``g711=True`` (extension): the call returns ``(audio, meta, law)``; a G.711 file that needs no resampling comes back as its uint8
     codes (on the device) with ``law`` "ulaw" / "alaw" — what ``DfStream.process(..., law=law)`` takes —, anything else as usual with
     ``law`` None."""
     method = kwargs.pop("method", "sinc_fast")
     want_pcm = bool(kwargs.pop("pcm16", False))
     want_g711 = bool(kwargs.pop("g711", False))
+    verify_md5 = bool(kwargs.pop("verify_md5", False))
     frames = kwargs.get("num_frames", -1)
     off = kwargs.get("frame_offset", 0)
+    if is_flac(file):
+        ((audio, info),) = load_flac_files([file], sr=sr, verbose=verbose, method=method, pcm16=want_pcm, frame_offset=off, num_frames=frames,
+                                           verify_md5=verify_md5)
+        return (audio, info, None) if want_g711 else (audio, info)
     if frames is not None and frames > 0 and sr is not None:
         rate0 = _read_riff(file, 0, 1)[1]        # io.py:46-47 scales num_frames by the file's own rate: read it first
         if rate0 < sr:   # (the reference's `num_frames *= rate0 // sr` is 0 there, which torchaudio reads as "nothing": say so instead of loading the whole file)

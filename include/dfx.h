@@ -567,6 +567,35 @@ int dfx_pcm16_to_f32(const int16_t *pcm, int64_t n, float *out, void *stream);
 int dfx_f32_to_pcm16(const float *x, int64_t n, int16_t *out, void *stream);
 int dfx_g711_decode(const uint8_t *codes, int law, int64_t n, void *out, int out_is_pcm16, void *stream);
 int dfx_g711_encode(const void *x, int x_is_pcm16, int law, int64_t n, uint8_t *out, void *stream);
+/* Native FLAC -> planar PCM, the bytes of .flac files decoded on the device (the reference loads them through torchaudio.load, df/io.py:25-57).
+ * Read: native FLAC streams of 1 to 8 channels and 8 to 24 bits per sample, fixed or variable blocking, every subframe kind, behind an optional
+ * ID3v2 tag.  Refused: Ogg-FLAC, 32-bit streams; nothing here writes FLAC.
+ *   probe    HOST arithmetic, no device: the first bytes of a stream (through its last metadata block) -> STREAMINFO and the byte offset of the
+ *            first frame.  DFX_ERR_INVALID_ARG: no 'fLaC' marker (Ogg-FLAC's 'OggS' is named), no STREAMINFO, more than 8 channels, bit depths
+ *            outside 8 .. 24, metadata that does not end inside the n bytes given.
+ *   decode   blob: DEVICE buffer (16-byte aligned) holding the bytes of n_streams streams; stream i lies at offsets[i] (a multiple of 16) with
+ *            lengths[i] bytes (2^28 at most), and the buffer extends to the end of the 16-byte chunk of every stream's last byte.  offsets,
+ *            lengths, infos (dfx_flac_probe's results) and out_offsets are HOST arrays, not read after the return.  Stream i's samples go to
+ *            out + out_offsets[i] (BYTES, a multiple of 4) as a planar [channels, total_samples] block: int16 where the stream has at most
+ *            16 bits (sample << (16 - bits): exactly what a 16-bit WAVE of the same audio holds), float32 = sample / 2^(bits - 1) otherwise (the
+ *            scaling of a 24-bit WAVE).  The whole of out (out_bytes) is cleared first.  status: DEVICE int64 [n_streams][4]: frames decoded,
+ *            frames lost, samples written per channel, flags (bit 0: more sync-code look-alikes than the candidate list holds).
+ *            A frame counts only if it starts where the previous frame ended and its CRC-16 holds: the sync code appearing inside a frame's
+ *            payload, even followed by a header with a valid CRC-8, does not split it.  A frame whose CRC-16 fails, that runs out of bytes or
+ *            uses a reserved code leaves zeros for its block and counts as lost; decoding goes on at the next frame whose CRC-16 holds, at
+ *            the sample position its header states.  Corrupt input never faults: every read is bounded by the stream's length.
+ *            Asynchronous on `stream`; workspace (device, 16-byte aligned): dfx_flac_workspace_bytes. */
+typedef struct dfx_flac_info {
+    int32_t sample_rate, channels, bits_per_sample, min_block, max_block;
+    int32_t first_frame;   /* byte offset of the first frame */
+    int64_t total_samples; /* per channel; 0 = not stated */
+    uint8_t md5[16];       /* of the interleaved little-endian samples; all zero = not computed */
+} dfx_flac_info;
+int dfx_flac_probe(const uint8_t *head, int64_t n, dfx_flac_info *out);
+int dfx_flac_workspace_bytes(int64_t n_streams, const int64_t *lengths, const dfx_flac_info *infos, int64_t *bytes);
+int dfx_flac_decode(const uint8_t *blob, int64_t blob_bytes, int64_t n_streams, const int64_t *offsets, const int64_t *lengths,
+                    const dfx_flac_info *infos, const int64_t *out_offsets, void *out, int64_t out_bytes, int64_t *status, void *workspace,
+                    int64_t workspace_bytes, void *stream);
 typedef struct dfx_resampler dfx_resampler;
 int dfx_resampler_create(int orig_sr, int new_sr, int lowpass_filter_width, double rolloff, int method, double beta,
                          dfx_resampler **out);
