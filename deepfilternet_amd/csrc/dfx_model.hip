@@ -21,6 +21,9 @@ static int check_cfg(const dfx_model_cfg *c) {
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "conv_ch=%d: the HIP kernels are instantiated for 16, 32, 64", c->conv_ch);
     if (c->emb_hidden_dim != 256 || c->df_hidden_dim != 256) DFX_FAIL(DFX_ERR_UNSUPPORTED, "GRU hidden size must be 256");
     if (c->nb_erb <= 0 || c->nb_erb % 8 || c->nb_erb > 64) DFX_FAIL(DFX_ERR_UNSUPPORTED, "nb_erb must be a multiple of 8, <= 64");
+    // the ERB decoder's last two layers run frame-resident (dfx_k_erb_dec10) at every shape these bounds accept: nb_erb is even and two workgroups
+    // fit the LDS at the largest one.  Widening either bound means bringing the layer-by-layer end (convt1, then conv0_out) back.
+    static_assert(2 * DFX_DEC10_SMEM(64, 64) <= 160 * 1024, "conv_ch <= 64, nb_erb <= 64: dfx_k_erb_dec10 must fit every accepted shape");
     if (c->nb_df <= 0 || c->nb_df % 2 || c->nb_df > c->fft_size / 2 + 1) DFX_FAIL(DFX_ERR_UNSUPPORTED, "nb_df must be even and <= F");
     if (c->df_order <= 0 || c->df_order > 16 || c->df_lookahead < 0 || c->df_lookahead >= c->df_order)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "need 0 <= df_lookahead < df_order <= 16");
@@ -442,8 +445,8 @@ struct DfxCan {
     bool enc_fan = false;      // dfx_k_enc_fan: df_fc_emb + the encoder GRU's linear_in in one pass over c1 (pack_encfan's nesting, no enc_concat)
     bool dfenc = false;        // dfx_k_df_enc_h3: the DF branch of the encoder as one kernel, c1 never stored (else dfx_k_df_conv01_h3 + dfx_k_enc_fan)
     // frame-resident ERB encoder head (dfx_k_erb_enc: a frame's zero-bordered feature rows within the kernel's 192 staging lanes, two workgroups' rows
-    // within the LDS; streaming has no other form of the head) / decoder end (dfx_k_erb_dec10: convt1 + conv0_out)
-    bool fuse_enc = false, fuse_dec = false;
+    // within the LDS; streaming has no other form of the head).  (The decoder end, dfx_k_erb_dec10: convt1 + conv0_out, fits every accepted shape: check_cfg.)
+    bool fuse_enc = false;
     // The ERB decoder's convolutions as ONE launch (dfx_k_erb_tail: d3 / d2 / d1 stay in LDS, -12 KB per frame beside the GRU chain); otherwise
     // three launches (convt3, convt2, convt1 + conv0_out).  Measured at config 2 (profiles/r03_fusion_ab.log): the first version (8 waves per
     // CU) 2.19 ms alone against 1.5 ms for the three launches and +0.37 ms per step; the second (12 waves per CU, 8.5 KB of strips per wave,
@@ -1274,8 +1277,7 @@ static void model_capabilities(dfx_model *m, const Prep::Packed &k) {
     can.enc_fan = k.encfan && !c.enc_concat && emb == 16 * m->efan_groups;
     can.dfenc = can.c0_h3 && can.enc_fan && k.dfenc;
     can.fuse_enc = E % 2 == 0 && 3 * (E + 2) <= 192 && 2 * DFX_ENC_SMEM(C, E) <= (size_t)160 * 1024;
-    can.fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= (size_t)160 * 1024;
-    can.erb_tail = can.fuse_dec && can.pw_h3 && k.tail && dfx_tail_ok(C, E);
+    can.erb_tail = can.pw_h3 && k.tail && dfx_tail_ok(C, E);
     // (dfx_k_erb_enc4's strips assume what DeepFilterNet3's encoder is: erb_conv1..3 of kernel 1 x 3 over frequency, strides 2 / 2 / 1 — the only
     // form prep_sep packs for these layers)
     can.erb_enc4 = can.fuse_enc && can.pw_h3 && dfx_enc4_ok(C, E);
@@ -1465,7 +1467,7 @@ static inline float *dfx_ws_base(void *workspace) { return reinterpret_cast<floa
 namespace {
 struct Ws {
     // offsets in floats, each 64-float (256 B) aligned
-    size_t e0, e1, e2, e3, c0, c1, emb_in, emb, xa, xb, gi, xa2, xb2, gi2, demb, d3, d2, d1, mask, c0p, xdf, coefs, lsnr, skp_e, skp_d, fps, total;
+    size_t e0, e1, e2, e3, c0, c1, emb_in, emb, xa, xb, gi, xa2, xb2, gi2, demb, d3, d2, mask, c0p, xdf, coefs, lsnr, skp_e, skp_d, fps, total;
     size_t pgi[DFX_MAX_GRU_LAYERS], py[DFX_MAX_GRU_LAYERS], ph[DFX_MAX_GRU_LAYERS];  // layer-pipelined GRU phase: gi, y, h state per layer
 };
 Ws plan_ws(const dfx_model *m, int64_t R, int64_t B) {
@@ -1496,7 +1498,6 @@ Ws plan_ws(const dfx_model *m, int64_t R, int64_t B) {
     w.demb = take(R * emb);
     w.d3 = take(R * (E / 4) * C);
     w.d2 = take(R * (E / 2) * C);
-    w.d1 = take(R * E * C);
     w.mask = take(R * E);
     w.c0p = take(R * Fd * NO);
     w.xdf = take(R * 256);

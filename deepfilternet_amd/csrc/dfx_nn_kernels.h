@@ -26,6 +26,48 @@ static __device__ __forceinline__ float dfx_act(float v, int act) {
     return v;
 }
 
+// A 256-value row as the B operands of the fp16-split matrix ops (dfx_k_proj256_h3 and the kernels that share its fragments): lane
+// (jl, q) holds the row's values 32 kc + 8 q .. + 7 as raw[2 kc], raw[2 kc + 1].  The row is scaled by a power of two (exact) so that its
+// largest magnitude sits just below 2^14 before the f16 split: any finite row then keeps ~22 bits relative to ITS OWN scale — rows of tiny
+// values would otherwise lose their lo halves to the f16 subnormals (|x| < 6e-5) and values above 65504 would turn into inf.  The scale
+// is taken over the four lanes (q) that share the row; a row of zeros, infinities or NaNs is split unscaled.  Returns 2^-e, the factor
+// that takes the products back to the row's own scale.
+static __device__ __forceinline__ float dfx_row256_scale_split(const float4 (&raw)[16], dfx_h8 (&xh)[8], dfx_h8 (&xl)[8]) {
+    float mx = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) mx = fmaxf(mx, fmaxf(fmaxf(fabsf(raw[i].x), fabsf(raw[i].y)), fmaxf(fabsf(raw[i].z), fabsf(raw[i].w))));
+    mx = fmaxf(mx, __shfl_xor(mx, 16));
+    mx = fmaxf(mx, __shfl_xor(mx, 32));
+    int e = 0;
+    if (mx > 0.f && mx < 3.0e38f) {
+        int ex;
+        (void)frexpf(mx, &ex);   // mx = f * 2^ex, f in [0.5, 1)
+        e = 14 - ex;
+        e = e > 100 ? 100 : (e < -100 ? -100 : e);
+    }
+    const float sc = ldexpf(1.f, e);
+#pragma unroll
+    for (int kc = 0; kc < 8; ++kc) {
+        const float4 xu = raw[2 * kc], xv = raw[2 * kc + 1];
+        float x[8];
+        x[0] = xu.x * sc, x[1] = xu.y * sc, x[2] = xu.z * sc, x[3] = xu.w * sc;
+        x[4] = xv.x * sc, x[5] = xv.y * sc, x[6] = xv.z * sc, x[7] = xv.w * sc;
+        dfx_split8(x, xh[kc], xl[kc]);
+    }
+    return ldexpf(1.f, -e);
+}
+// the same on the lane's part of a row in memory (p = row + 8 q; !ok: a row of zeros, nothing read)
+static __device__ __forceinline__ float dfx_row256_split(const float *p, bool ok, dfx_h8 (&xh)[8], dfx_h8 (&xl)[8]) {
+    const float4 *p4 = reinterpret_cast<const float4 *>(p);
+    float4 raw[16];
+#pragma unroll
+    for (int kc = 0; kc < 8; ++kc) {
+        raw[2 * kc] = ok ? p4[8 * kc] : make_float4(0.f, 0.f, 0.f, 0.f);
+        raw[2 * kc + 1] = ok ? p4[8 * kc + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    return dfx_row256_scale_split(raw, xh, xl);
+}
+
 // compile-time loop (the fully unrolled bodies index register arrays with constants only)
 template <int I, int N, typename F>
 static __device__ __forceinline__ void dfx_static_for(F &&f) {
@@ -1095,9 +1137,6 @@ __global__ void __launch_bounds__(DFX_PW_THREADS, 3) dfx_k_df_enc_h3(DfxDfEncArg
 #ifndef DFX_CPH_TRACE
 #define DFX_CPH_TRACE 0    /* dev: lane 0 of every workgroup sums the s_memtime ticks of a frame's parts into DfxCphArgs::trace[block][5] */
 #endif
-#ifndef DFX_CPH_PARENT_LOOP
-#define DFX_CPH_PARENT_LOOP 0   /* dev: 1 = the PS instance runs the unsplit instance's frame loop (the schedule before the rework), for A/B runs */
-#endif
 #ifndef DFX_CPH_VALU_C0
 #define DFX_CPH_VALU_C0 4     /* vector instructions asked for in the shadow of each of c0's matrix ops (the next patch's addresses) */
 #endif
@@ -1291,7 +1330,7 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         auto make_frame = [&](dfx_h8 (&dh)[KC], dfx_h8 (&dl)[KC], int64_t tau, const Patch &rw) {
             float c0v[CPL];
             // frames before the clip are the zero padding of c0 itself (wave-uniform test)
-            if constexpr (PS && !DFX_CPH_PARENT_LOOP) {   // (the warm-up frames of the batch passes' loop: the same tile in its two halves, a guard between)
+            if constexpr (PS) {   // (the warm-up frames of the batch passes' loop: the same tile in its two halves, a guard between)
                 dfx_h8 p_h, p_l;
                 dfx_c0_patch_ps(rw, p_h, p_l);
                 f32x4 acc0[NT];
@@ -1313,7 +1352,7 @@ __global__ void __launch_bounds__(256, 1) dfx_k_df_convp_h3(DfxCphArgs A) {
         asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(tlast)::"memory");   // (the warm-up frames are not counted)
         nframes += (unsigned long long)(t1 - t0);
 #endif
-        if constexpr (PS && !DFX_CPH_PARENT_LOOP) {
+        if constexpr (PS) {
             // The batch passes' schedule.  Same products in the same order per accumulator as the loop below (three chains, taps ascending,
             // k-chunks inner, (aa + ab) + ac; the c0 tile and the split are the same functions), so the same bits; what differs is WHERE things stand:
             // - A frame's outputs are held in four registers and stored in the NEXT frame's body, behind that frame's patch wait and in front of
@@ -1939,62 +1978,11 @@ __global__ void __launch_bounds__(256, 2) dfx_k_erb_enc(DfxEncArgs A) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// erb_dec.conv0_out: Conv2d(C -> 1, 1x3) + BN(1) + Sigmoid on  xin = relu(a*e0 + b) + d1   (deepfilternet3.py:241-243,253)
-//   m[r, f] = sigmoid(bias + sum_j sum_c w[j][c] * xin[r, f+j-1, c])
-// A tile is a whole number of frames (E positions each); xin is staged in LDS, threads (pos, j) form the three per-
-// position dot products, then one thread per position combines the neighbours.
-// ---------------------------------------------------------------------------------------------------------------------
-#define DFX_CO_THREADS 256
-template <int C>
-__global__ void __launch_bounds__(DFX_CO_THREADS) dfx_k_conv_out(const float *x, const float *skip, const float *sk_a,
-                                                                 const float *sk_b, const float *w /*[3][C]*/, float bias,
-                                                                 float *out, int64_t R, int E, int frames_per_tile, DfxRowMap rm) {
-    constexpr int LDA = C + 1;
-    DFX_DYN_SMEM(float, sm);
-    const int MT = frames_per_tile * E;
-    float *As = sm;                 // [MT][LDA]
-    float *V = sm + MT * LDA;       // [MT][3]
-    float *W = V + MT * 3;          // [3][C]
-    const int tid = threadIdx.x;
-    for (int i = tid; i < 3 * C; i += DFX_CO_THREADS) W[i] = w[i];
-    const int64_t ntiles = (R + frames_per_tile - 1) / frames_per_tile;
-    for (int64_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const int64_t r0 = tile * frames_per_tile;
-        const int64_t npos = ((R - r0) < frames_per_tile ? (R - r0) : frames_per_tile) * E;
-        for (int i = tid; i < MT * C; i += DFX_CO_THREADS) {
-            const int p = i / C, c = i - p * C;
-            float v = 0.f;
-            if (p < npos) {
-                const int64_t g = (dfx_row(rm, r0 + p / E) * E + p % E) * C + c;
-                v = x[g] + fmaxf(sk_a[c] * skip[g] + sk_b[c], 0.f);
-            }
-            As[p * LDA + c] = v;
-        }
-        __syncthreads();
-        for (int i = tid; i < MT * 3; i += DFX_CO_THREADS) {
-            const int p = i / 3, j = i - p * 3;
-            float acc = 0.f;
-            for (int c = 0; c < C; ++c) acc += W[j * C + c] * As[p * LDA + c];
-            V[i] = acc;
-        }
-        __syncthreads();
-        for (int p = tid; p < npos; p += DFX_CO_THREADS) {
-            const int f = p % E;
-            float acc = bias + V[p * 3 + 1];
-            if (f > 0) acc += V[(p - 1) * 3 + 0];
-            if (f < E - 1) acc += V[(p + 1) * 3 + 2];
-            out[dfx_row(rm, r0 + p / E) * E + f] = dfx_sigmoid(acc);
-        }
-        __syncthreads();
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------------------
 // ERB decoder tail, fused: erb_dec.convt1 (transposed 1x3, stride 2, with the conv1p pathway) -> erb_dec.conv0_out (with the conv0p
 // pathway) + sigmoid   (deepfilternet3.py:252-253).  d1 [B*T, E, C], the widest decoder activation, never reaches HBM: a wave owns
 // one frame, the convt1 tiles (dfx_k_pwconv's DWT3 + SKIP body, operands from HBM) put  xin = d1 + relu(a0*e0 + b0)  into an LDS
-// strip [E][C + 4], and the 3-tap C -> 1 conv reads it back exactly like dfx_k_conv_out (same per-(position, tap) dot products, same
-// combination order -> the same bits).  HBM per frame: reads d2, e1 (E/2 positions) and e0, writes E mask values.
+// strip [E][C + 4], and the 3-tap C -> 1 conv reads it back: per (position, tap) a dot product over the C channels, then per position
+// bias + middle tap + left neighbour's tap 0 + right neighbour's tap 2  (m[r, f] = sigmoid(bias + sum_j sum_c w[j][c] * xin[r, f+j-1, c])).  HBM per frame: reads d2, e1 (E/2 positions) and e0, writes E mask values.
 // ---------------------------------------------------------------------------------------------------------------------
 struct DfxDec10Args {
     const float *x;      // d2 [R, E/2, C]
@@ -3545,42 +3533,9 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_proj256_h3(DfxPhArgs 
     // stage the first chunk
 #pragma unroll
     for (int i = 0; i < PER_T; ++i) ws[(size_t)(cfirst & 1) * DFX_PH_CHUNK_H8 + i * DFX_PH_THREADS + tid] = A.wf[(size_t)cfirst * DFX_PH_CHUNK_H8 + i * DFX_PH_THREADS + tid];
-    // this lane's B operands: row m, k = 32*kc + 8*q .. +7.  The row is scaled by a power of two (exact) so that its largest magnitude
-    // sits just below 2^14 before the f16 split: any finite row then keeps ~22 bits relative to ITS OWN scale — rows of tiny values
-    // would otherwise lose their lo halves to the f16 subnormals (|x| < 6e-5) and values above 65504 would turn into inf.
+    // this lane's B operands: row m, k = 32*kc + 8*q .. +7, scaled by the row's own power of two (dfx_row256_split)
     dfx_h8 xh[8], xl[8];
-    float row_unscale = 1.f;
-    {
-        const float4 *p = reinterpret_cast<const float4 *>(A.a + m * 256 + 8 * q);
-        float4 xu[8], xv[8];
-        float mx = 0.f;
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            xu[kc] = ok ? p[8 * kc] : make_float4(0.f, 0.f, 0.f, 0.f);
-            xv[kc] = ok ? p[8 * kc + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xu[kc].x), fabsf(xu[kc].y)), fmaxf(fabsf(xu[kc].z), fabsf(xu[kc].w))));
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xv[kc].x), fabsf(xv[kc].y)), fmaxf(fabsf(xv[kc].z), fabsf(xv[kc].w))));
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));   // the four lanes (q) that share row jl
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex;
-            (void)frexpf(mx, &ex);            // mx = f * 2^ex, f in [0.5, 1)
-            e = 14 - ex;
-            e = e > 100 ? 100 : (e < -100 ? -100 : e);
-        }
-        const float sc = ldexpf(1.f, e);
-        row_unscale = ldexpf(1.f, -e);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            float x[8];
-            x[0] = xu[kc].x * sc, x[1] = xu[kc].y * sc, x[2] = xu[kc].z * sc, x[3] = xu[kc].w * sc;
-            x[4] = xv[kc].x * sc, x[5] = xv[kc].y * sc, x[6] = xv[kc].z * sc, x[7] = xv[kc].w * sc;
-            dfx_split8(x, xh[kc], xl[kc]);
-        }
-    }
-    const float unscale = A.unscale * row_unscale;   // D leaves lane (jl, q) with row jl: the row's own scale
+    const float unscale = A.unscale * dfx_row256_split(A.a + m * 256 + 8 * q, ok, xh, xl);   // D leaves lane (jl, q) with row jl: the row's own scale
     __syncthreads();
     for (int c = cfirst; c < nchunks; ++c) {
         const dfx_h8 *wc = ws + (size_t)(c & 1) * DFX_PH_CHUNK_H8;
@@ -3658,22 +3613,61 @@ struct DfxGstArgs {
 #ifndef DFX_GST_ABLATE
 #define DFX_GST_ABLATE 0   /* dev ablations (tools/dev/gru_step_bench.hip): 1 no matrix ops, 2 no chunk loads after the first, 4 no operand rows, 8 no gate math */
 #endif
+// Placement of a workgroup of the one-step kernels: u = its block of 16 * CT hidden units, b = the lane's row (wave w holds rows 16 w + jl
+// of the block); false: the workgroup's row block lies past the last row.  The 16 / CT workgroups that share a block of 128 rows are dealt
+// to ONE XCD (workgroups go round-robin over the 8 XCDs: block i runs on XCD i % 8 up to a rotation that is constant within a launch): the
+// operand rows then come from HBM into one L2 instead of all eight — with row-major block order the step spent half its time fetching
+// 8 x 8 MB of rows (grid: row blocks padded to a multiple of 8, times 16 / CT)
+template <int CT>
+static __device__ __forceinline__ bool dfx_gru_step_place(int64_t B, int wave, int jl, int &u, int64_t &b) {
+    constexpr int NU = 16 / CT;   // unit blocks per layer
+    const int xcd = (int)(blockIdx.x & 7), kk = (int)(blockIdx.x >> 3);
+    u = kk % NU;
+    const int64_t rb = xcd + 8 * (int64_t)(kk / NU);
+    b = rb * DFX_PH_BM + 16 * wave + jl;
+    return rb * DFX_PH_BM < B;
+}
+// The gate epilogue of the one-step kernels on g = gi (r, z, n) then gh (r, z, n): D leaves lane (row jl, q) of unit tile ct with the units
+// 16 CT u + 16 ct + 4 q .. + 3.  h' goes to h_out and, when A.y is set, to the layer's output row.
+template <int CT>
+static __device__ __forceinline__ void dfx_gru_step_gates(const DfxGstArgs &A, const f32x4 (&g)[6][CT], int64_t b, int u, int q) {
+    const int64_t yr = A.y ? dfx_row(A.yrm, b) : 0;
+#pragma unroll
+    for (int ct = 0; ct < CT; ++ct) {
+        const int n0 = 16 * CT * u + 16 * ct + 4 * q;
+        const float4 br = *reinterpret_cast<const float4 *>(A.bias_i + n0), bz = *reinterpret_cast<const float4 *>(A.bias_i + 256 + n0),
+                     bn = *reinterpret_cast<const float4 *>(A.bias_i + 512 + n0), bh = *reinterpret_cast<const float4 *>(A.bhn + n0),
+                     hp = *reinterpret_cast<const float4 *>(A.h_in + b * 256 + n0);
+        const float brr[4] = {br.x, br.y, br.z, br.w}, bzz[4] = {bz.x, bz.y, bz.z, bz.w}, bnn[4] = {bn.x, bn.y, bn.z, bn.w},
+                    bhh[4] = {bh.x, bh.y, bh.z, bh.w}, hpp[4] = {hp.x, hp.y, hp.z, hp.w};
+        float o[4];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            if (DFX_GST_ABLATE & 8) {
+                o[r] = g[0][ct][r] + g[1][ct][r] + g[2][ct][r] + g[3][ct][r] + g[4][ct][r] + g[5][ct][r] + brr[r] + bzz[r] + bnn[r] + bhh[r] + hpp[r];
+                continue;
+            }
+            const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[0][ct][r] + brr[r]) + g[3][ct][r])));
+            const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[1][ct][r] + bzz[r]) + g[4][ct][r])));
+            const float pre = (g[2][ct][r] + bnn[r]) + rg * (g[5][ct][r] + bhh[r]);
+            const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
+            o[r] = (1.f - zg) * ng + zg * hpp[r];
+        }
+        const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
+        *reinterpret_cast<float4 *>(A.h_out + b * 256 + n0) = ov;
+        if (A.y) *reinterpret_cast<float4 *>(A.y + yr * 256 + n0) = ov;
+    }
+}
 template <int CT>
 __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_h3(DfxGstArgs A) {
     static_assert(CT == 2 || CT == 4, "32 or 64 hidden units per workgroup");
     constexpr int CHUNK = 8 * CT * 2 * 64;   // dfx_h8 per chunk of this workgroup: [kc][ct][hi,lo][lane]
     constexpr int PER_T = CHUNK / DFX_PH_THREADS;
-    constexpr int NU = 16 / CT;              // unit blocks per layer
     DFX_DYN_SMEM(dfx_h8, ws);  // [2][CHUNK]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
-    // The NU workgroups that share a block of 128 rows are dealt to ONE XCD (workgroups go round-robin over the 8 XCDs: block i runs on XCD
-    // i % 8 up to a rotation that is constant within a launch): the operand rows then come from HBM into one L2 instead of all eight —
-    // with row-major block order the step spent half its time fetching 8 x 8 MB of rows (grid: row blocks padded to a multiple of 8)
-    const int xcd = (int)(blockIdx.x & 7), kk = (int)(blockIdx.x >> 3);
-    const int u = kk % NU;   // block of 16 * CT hidden units
-    const int64_t rb = xcd + 8 * (int64_t)(kk / NU);
-    if (rb * DFX_PH_BM >= A.B) return;
-    const int64_t b = rb * DFX_PH_BM + 16 * wave + jl;
+    int u;
+    int64_t b;
+    if (!dfx_gru_step_place<CT>(A.B, wave, jl, u, b)) return;
     const bool ok = b < A.B;
     // chunk i of this workgroup: i < 3: W_ih, gate i; else W_hh, gate i - 3: columns 256 g + 16 CT u .. of the [12][8][4][2][64] fragments,
     // i.e. the tiles ct0 .. ct0 + CT - 1 of the 64-column chunk 4 g + (CT u) / 4
@@ -3704,33 +3698,9 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_h3(DfxGstArg
 #pragma unroll
         for (int i = 0; i < PER_T; ++i) ws[i * DFX_PH_THREADS + tid] = src[src_index(i * DFX_PH_THREADS + tid)];
     }
-    // a row's 256 values as B operands, scaled by the row's own power of two before the f16 split (see dfx_k_proj256_h3)
-    auto split_row = [&](const float4 (&raw)[16], dfx_h8 (&vh)[8], dfx_h8 (&vl)[8]) -> float {
-        float mx = 0.f;
-#pragma unroll
-        for (int i = 0; i < 16; ++i) mx = fmaxf(mx, fmaxf(fmaxf(fabsf(raw[i].x), fabsf(raw[i].y)), fmaxf(fabsf(raw[i].z), fabsf(raw[i].w))));
-        mx = fmaxf(mx, __shfl_xor(mx, 16));
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) {
-            int ex;
-            (void)frexpf(mx, &ex);
-            e = 14 - ex;
-            e = e > 100 ? 100 : (e < -100 ? -100 : e);
-        }
-        const float sc = ldexpf(1.f, e);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            const float4 xu = raw[2 * kc], xv = raw[2 * kc + 1];
-            float x[8];
-            x[0] = xu.x * sc, x[1] = xu.y * sc, x[2] = xu.z * sc, x[3] = xu.w * sc;
-            x[4] = xv.x * sc, x[5] = xv.y * sc, x[6] = xv.z * sc, x[7] = xv.w * sc;
-            dfx_split8(x, vh[kc], vl[kc]);
-        }
-        return ldexpf(1.f, -e);
-    };
+    // a row's 256 values as B operands, scaled by the row's own power of two before the f16 split (dfx_row256_scale_split)
     dfx_h8 xh[8], xl[8], hh[8], hl[8];
-    const float us_x = A.unscale_i * split_row(xraw, xh, xl);
+    const float us_x = A.unscale_i * dfx_row256_scale_split(xraw, xh, xl);
     float us_h = 0.f;   // (the recurrent operand is split under the matrix ops of chunk 1: it is first used by chunk 3)
     f32x4 g[6][CT];   // gi (r, z, n) then gh (r, z, n)
     __syncthreads();
@@ -3747,7 +3717,7 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_h3(DfxGstArg
         f32x4 acc[CT];
 #pragma unroll
         for (int ct = 0; ct < CT; ++ct) acc[ct] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if constexpr (c == 1) us_h = A.unscale_h * split_row(hraw, hh, hl);
+        if constexpr (c == 1) us_h = A.unscale_h * dfx_row256_scale_split(hraw, hh, hl);
 #pragma unroll
         for (int kc = 0; kc < 8; ++kc) {
             dfx_h8 whi[CT], wlo[CT];
@@ -3774,34 +3744,7 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_h3(DfxGstArg
             __syncthreads();
         }
     });
-    if (ok) {
-        const int64_t yr = A.y ? dfx_row(A.yrm, b) : 0;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int n0 = 16 * CT * u + 16 * ct + 4 * q;   // D leaves lane (row jl, q) with the units n0 .. n0 + 3
-            const float4 br = *reinterpret_cast<const float4 *>(A.bias_i + n0), bz = *reinterpret_cast<const float4 *>(A.bias_i + 256 + n0),
-                         bn = *reinterpret_cast<const float4 *>(A.bias_i + 512 + n0), bh = *reinterpret_cast<const float4 *>(A.bhn + n0),
-                         hp = *reinterpret_cast<const float4 *>(A.h_in + b * 256 + n0);
-            const float brr[4] = {br.x, br.y, br.z, br.w}, bzz[4] = {bz.x, bz.y, bz.z, bz.w}, bnn[4] = {bn.x, bn.y, bn.z, bn.w},
-                        bhh[4] = {bh.x, bh.y, bh.z, bh.w}, hpp[4] = {hp.x, hp.y, hp.z, hp.w};
-            float o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (DFX_GST_ABLATE & 8) {
-                    o[r] = g[0][ct][r] + g[1][ct][r] + g[2][ct][r] + g[3][ct][r] + g[4][ct][r] + g[5][ct][r] + brr[r] + bzz[r] + bnn[r] + bhh[r] + hpp[r];
-                    continue;
-                }
-                const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[0][ct][r] + brr[r]) + g[3][ct][r])));
-                const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[1][ct][r] + bzz[r]) + g[4][ct][r])));
-                const float pre = (g[2][ct][r] + bnn[r]) + rg * (g[5][ct][r] + bhh[r]);
-                const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
-                o[r] = (1.f - zg) * ng + zg * hpp[r];
-            }
-            const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-            *reinterpret_cast<float4 *>(A.h_out + b * 256 + n0) = ov;
-            if (A.y) *reinterpret_cast<float4 *>(A.y + yr * 256 + n0) = ov;
-        }
-    }
+    if (ok) dfx_gru_step_gates<CT>(A, g, b, u, q);
 }
 
 // The exact form of the step (DFX_EXACT_FP32=1): the same workgroup shape, chunk pipeline, XCD dealing and state contract on
@@ -3818,16 +3761,12 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_x32(DfxGstAr
     static_assert(CT == 2 || CT == 4, "32 or 64 hidden units per workgroup");
     constexpr int CHUNK = 8 * CT * 2 * 64;   // 16-byte pieces per chunk of this workgroup: [kc][ct][half][lane]
     constexpr int PER_T = CHUNK / DFX_PH_THREADS;
-    constexpr int NU = 16 / CT;              // unit blocks per layer
     static_assert((size_t)2 * CHUNK * 16 <= DFX_PH_SMEM, "two chunks fit the projection kernel's LDS");
     DFX_DYN_SMEM(dfx_h8, ws);  // [2][CHUNK]
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, jl = lane & 15;
-    // (row blocks dealt to the XCDs as in dfx_k_gru_step_h3: grid = row blocks padded to a multiple of 8, times NU)
-    const int xcd = (int)(blockIdx.x & 7), kk = (int)(blockIdx.x >> 3);
-    const int u = kk % NU;   // block of 16 * CT hidden units = the unit tiles CT u .. CT u + CT - 1
-    const int64_t rb = xcd + 8 * (int64_t)(kk / NU);
-    if (rb * DFX_PH_BM >= A.B) return;
-    const int64_t b = rb * DFX_PH_BM + 16 * wave + jl;
+    int u;       // block of 16 * CT hidden units = the unit tiles CT u .. CT u + CT - 1
+    int64_t b;
+    if (!dfx_gru_step_place<CT>(A.B, wave, jl, u, b)) return;
     const bool ok = b < A.B;
     // piece e = ((kc * CT + ct) * 2 + half) * 64 + lane of chunk i (i < 3: W_ih, gate i; else W_hh, gate i - 3) inside the fragment array
     auto src_of = [&](int i, int e) -> const dfx_h8 * {
@@ -3890,34 +3829,7 @@ __global__ void __launch_bounds__(DFX_PH_THREADS, 2) dfx_k_gru_step_x32(DfxGstAr
             __syncthreads();
         }
     });
-    if (ok) {
-        const int64_t yr = A.y ? dfx_row(A.yrm, b) : 0;
-#pragma unroll
-        for (int ct = 0; ct < CT; ++ct) {
-            const int n0 = 16 * CT * u + 16 * ct + 4 * q;   // D leaves lane (row jl, q) with the units n0 .. n0 + 3
-            const float4 br = *reinterpret_cast<const float4 *>(A.bias_i + n0), bz = *reinterpret_cast<const float4 *>(A.bias_i + 256 + n0),
-                         bn = *reinterpret_cast<const float4 *>(A.bias_i + 512 + n0), bh = *reinterpret_cast<const float4 *>(A.bhn + n0),
-                         hp = *reinterpret_cast<const float4 *>(A.h_in + b * 256 + n0);
-            const float brr[4] = {br.x, br.y, br.z, br.w}, bzz[4] = {bz.x, bz.y, bz.z, bz.w}, bnn[4] = {bn.x, bn.y, bn.z, bn.w},
-                        bhh[4] = {bh.x, bh.y, bh.z, bh.w}, hpp[4] = {hp.x, hp.y, hp.z, hp.w};
-            float o[4];
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                if (DFX_GST_ABLATE & 8) {
-                    o[r] = g[0][ct][r] + g[1][ct][r] + g[2][ct][r] + g[3][ct][r] + g[4][ct][r] + g[5][ct][r] + brr[r] + bzz[r] + bnn[r] + bhh[r] + hpp[r];
-                    continue;
-                }
-                const float rg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[0][ct][r] + brr[r]) + g[3][ct][r])));
-                const float zg = dfx_fast_rcp(1.f + dfx_fast_exp(-((g[1][ct][r] + bzz[r]) + g[4][ct][r])));
-                const float pre = (g[2][ct][r] + bnn[r]) + rg * (g[5][ct][r] + bhh[r]);
-                const float ng = 2.f * dfx_fast_rcp(1.f + dfx_fast_exp(-2.f * pre)) - 1.f;
-                o[r] = (1.f - zg) * ng + zg * hpp[r];
-            }
-            const float4 ov = make_float4(o[0], o[1], o[2], o[3]);
-            *reinterpret_cast<float4 *>(A.h_out + b * 256 + n0) = ov;
-            if (A.y) *reinterpret_cast<float4 *>(A.y + yr * 256 + n0) = ov;
-        }
-    }
+    if (ok) dfx_gru_step_gates<CT>(A, g, b, u, q);
 }
 
 // The same projection with TWO row tiles per wave: every W fragment read from LDS feeds 6 matrix ops instead of 3.  dfx_k_proj256_h3 is
@@ -3959,34 +3871,7 @@ __global__ void __launch_bounds__(64 * NW, CT == 2 ? 2 : 1) dfx_k_proj256_h3x2(D
         const int64_t ml = (int64_t)blockIdx.x * BM2 + 32 * wave + 16 * t + jl;
         okr[t] = ml < A.M;
         mrow[t] = okr[t] ? dfx_row(A.rm, ml) : 0;
-        const float4 *p = reinterpret_cast<const float4 *>(A.a + mrow[t] * 256 + 8 * q);
-        float4 xu[8], xv[8];
-        float mx = 0.f;
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            xu[kc] = okr[t] ? p[8 * kc] : make_float4(0.f, 0.f, 0.f, 0.f);
-            xv[kc] = okr[t] ? p[8 * kc + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xu[kc].x), fabsf(xu[kc].y)), fmaxf(fabsf(xu[kc].z), fabsf(xu[kc].w))));
-            mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xv[kc].x), fabsf(xv[kc].y)), fmaxf(fabsf(xv[kc].z), fabsf(xv[kc].w))));
-        }
-        mx = fmaxf(mx, __shfl_xor(mx, 16));   // the four lanes (q) that share row jl
-        mx = fmaxf(mx, __shfl_xor(mx, 32));
-        int e = 0;
-        if (mx > 0.f && mx < 3.0e38f) {       // per-row power-of-two scale, exactly as in dfx_k_proj256_h3
-            int ex;
-            (void)frexpf(mx, &ex);
-            e = 14 - ex;
-            e = e > 100 ? 100 : (e < -100 ? -100 : e);
-        }
-        const float sc = ldexpf(1.f, e);
-        unscale[t] = A.unscale * ldexpf(1.f, -e);
-#pragma unroll
-        for (int kc = 0; kc < 8; ++kc) {
-            float x[8];
-            x[0] = xu[kc].x * sc, x[1] = xu[kc].y * sc, x[2] = xu[kc].z * sc, x[3] = xu[kc].w * sc;
-            x[4] = xv[kc].x * sc, x[5] = xv[kc].y * sc, x[6] = xv[kc].z * sc, x[7] = xv[kc].w * sc;
-            dfx_split8(x, xh[t][kc], xl[t][kc]);
-        }
+        unscale[t] = A.unscale * dfx_row256_split(A.a + mrow[t] * 256 + 8 * q, okr[t], xh[t], xl[t]);
     }
     __syncthreads();
     for (int c = 0; c < nchunks; ++c) {
@@ -5095,34 +4980,7 @@ __global__ void __launch_bounds__(512, 1) dfx_k_proj_follow(DfxPfArgs A) {
             trow[t] = t0 + 2 * wave + t;
             okr[t] = okc && trow[t] < t1;
             if (!okr[t]) trow[t] = t0;
-            const float4 *p = reinterpret_cast<const float4 *>(xrow + trow[t] * 256);
-            float4 xu[8], xv[8];
-            float mx = 0.f;
-#pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                xu[kc] = okr[t] ? p[8 * kc] : make_float4(0.f, 0.f, 0.f, 0.f);
-                xv[kc] = okr[t] ? p[8 * kc + 1] : make_float4(0.f, 0.f, 0.f, 0.f);
-                mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xu[kc].x), fabsf(xu[kc].y)), fmaxf(fabsf(xu[kc].z), fabsf(xu[kc].w))));
-                mx = fmaxf(mx, fmaxf(fmaxf(fabsf(xv[kc].x), fabsf(xv[kc].y)), fmaxf(fabsf(xv[kc].z), fabsf(xv[kc].w))));
-            }
-            mx = fmaxf(mx, __shfl_xor(mx, 16));   // the four lanes (q) that share a row
-            mx = fmaxf(mx, __shfl_xor(mx, 32));
-            int e = 0;
-            if (mx > 0.f && mx < 3.0e38f) {       // per-row power-of-two scale, exactly as in dfx_k_proj256_h3
-                int ex;
-                (void)frexpf(mx, &ex);
-                e = 14 - ex;
-                e = e > 100 ? 100 : (e < -100 ? -100 : e);
-            }
-            const float sc = ldexpf(1.f, e);
-            unscale[t] = A.unscale[f] * ldexpf(1.f, -e);
-#pragma unroll
-            for (int kc = 0; kc < 8; ++kc) {
-                float x[8];
-                x[0] = xu[kc].x * sc, x[1] = xu[kc].y * sc, x[2] = xu[kc].z * sc, x[3] = xu[kc].w * sc;
-                x[4] = xv[kc].x * sc, x[5] = xv[kc].y * sc, x[6] = xv[kc].z * sc, x[7] = xv[kc].w * sc;
-                dfx_split8(x, xh[t][kc], xl[t][kc]);
-            }
+            unscale[t] = A.unscale[f] * dfx_row256_split(xrow + trow[t] * 256, okr[t], xh[t], xl[t]);
         }
         for (int c = 0; c < nchunks; ++c) {
             const dfx_h8 *wc = ws + (size_t)(c & 1) * CH8;

@@ -149,7 +149,7 @@ static __device__ __forceinline__ float dfx_lane_gather4(float v, unsigned byte_
 // block (an `if (valid)` epilogue: s_and_saveexec, then the read).  Round 5: dfx_fft480_mfma returned one wrong bin in ~10 % of its runs on the
 // GPU (never on the interpreter) where the compiler had left 8 wait states between a chain of back-to-back DEPENDENT matrix ops and such a
 // read; four more — or just keeping the scheduler from sinking the ops to the end of their block — and 450 of 450 runs were right
-// (tools/dev/dbg_mf.py, tools/dev/scan_mfma_reads.py).  Chains are also kept three ops apart (term-major order), as everywhere else here.
+// (tools/dev/patches/r05_fft480_mfma.patch, tools/dev/scan_mfma_reads.py).  Chains are also kept three ops apart (term-major order), as everywhere else here.
 #define DFX_MFMA_GUARD()                         \
     do {                                         \
         __builtin_amdgcn_sched_barrier(0);       \

@@ -260,7 +260,7 @@ int dfx_model_check(const dfx_model *m);
 #define DFX_PLAN_DF_OUT_STREAMING 2   /* dfx_k_df_out_h3 */
 #define DFX_PLAN_DF_OUT_GGEMM 3       /* the grouped GEMM */
 #define DFX_PLAN_ROWS_FINISH (1 << 14) /* deep filter + gains inside the inverse transform (dfx_k_synthesis_rows) */
-#define DFX_PLAN_FUSE_DEC (1 << 15)   /* frame-resident last two ERB decoder layers (dfx_k_erb_dec10 / inside dfx_k_erb_tail) */
+#define DFX_PLAN_FUSE_DEC (1 << 15)   /* frame-resident last two ERB decoder layers (dfx_k_erb_dec10 / inside dfx_k_erb_tail): set on every pass, every accepted shape */
 int dfx_model_query(const dfx_model *m, int what, int64_t *value);
 
 /* Scratch memory the caller must provide (device bytes) for a [B, T-frames] batch.  What a workspace — this one, dfx_enhance's, dfx_enhance_varlen's —

@@ -107,10 +107,10 @@ def test_enhance_shapes_match_oracle(backend, shape):
 
 # Decisions that check_cfg leaves only one side of, each with the arithmetic that excludes the other side.  Only such bits may stand here.
 UNREACHABLE = {
-    # plan(): fuse_dec = E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= 160 KiB.  check_cfg takes nb_erb in multiples of 8 up to 64 (even) and conv_ch
-    # 16 / 32 / 64; DFX_DEC10_SMEM(C, E) = (3C/4 + 4C/4 + 3C/4) * 16 + 16 * (E * (C + 4) + 4 E) bytes grows with both, and at the largest,
-    # C = 64, E = 64, it is 2560 + 16 * 4608 = 76288 bytes: 2 * 76288 = 152576 <= 163840.  So fuse_dec is never false (dfx_k_conv_out and the
-    # separate convt1 launch behind it are never enqueued).
+    # fuse_dec: dfx_k_erb_dec10 needs E % 2 == 0 && 2 * DFX_DEC10_SMEM(C, E) <= 160 KiB.  check_cfg takes nb_erb in multiples of 8 up to 64 (even)
+    # and conv_ch 16 / 32 / 64; DFX_DEC10_SMEM(C, E) = (3C/4 + 4C/4 + 3C/4) * 16 + 16 * (E * (C + 4) + 4 E) bytes grows with both, and at the
+    # largest, C = 64, E = 64, it is 2560 + 16 * 4608 = 76288 bytes: 2 * 76288 = 152576 <= 163840.  So fuse_dec is never false: the layer-by-layer
+    # end (a separate convt1, then dfx_k_conv_out) is gone from the library, and a static_assert beside check_cfg holds the bound.
     ("fuse_dec", False),
 }
 

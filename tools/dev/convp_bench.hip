@@ -1,7 +1,6 @@
 // Dev: dfx_k_df_convp_h3<64, 5> alone at the benchmark's shape (256 clips x 1002 frames x 96 bins, segments of 40 frames): the PS instance
 // (pre-split patches, the batch passes' frame loop) against the unsplit instance (the loop as it was), outputs compared bit for bit, ms per
 // launch of each, and — built with -DDFX_CPH_TRACE=1 — the s_memtime ticks per frame of the loop's parts.
-//   -DDFX_CPH_PARENT_LOOP=1   the PS instance runs the unsplit instance's loop (the schedule before the rework)
 //   -DDFX_CPH_ABLATE=1 / 2    no output stores / no patch loads (the comparison then only says that both forms were ablated alike)
 //   -DDFX_CPH_VALU_C0=n -DDFX_CPH_VALU_TAPS=n   the vector instructions asked for in the shadow of each matrix op
 // build: hipcc --offload-arch=gfx950 -O3 -std=c++17 -mllvm -amdgpu-mfma-vgpr-form=1 -Xclang -target-feature -Xclang -packed-fp32-ops
@@ -96,8 +95,7 @@ int main(int argc, char **argv) {
     };
     for (int form = 0; form < 2; ++form) {
         const std::vector<float> ms = run(form);
-        printf("%s instance%s: median %.3f min %.3f max %.3f ms of %d launches\n", form ? "PS" : "unsplit",
-               form && DFX_CPH_PARENT_LOOP ? " (the unsplit instance's loop)" : "", ms[reps / 2], ms[0], ms[reps - 1], reps);
+        printf("%s instance: median %.3f min %.3f max %.3f ms of %d launches\n", form ? "PS" : "unsplit", ms[reps / 2], ms[0], ms[reps - 1], reps);
 #if DFX_CPH_TRACE
         std::vector<unsigned long long> h((size_t)grid * 5);
         CK(hipMemcpy(h.data(), trace, h.size() * 8, hipMemcpyDeviceToHost));
@@ -105,7 +103,7 @@ int main(int argc, char **argv) {
         for (int g = 0; g < grid; ++g)
             for (int i = 0; i < 5; ++i) s[i] += (double)h[(size_t)g * 5 + i];
         printf("  s_memtime ticks per frame, wave 0 of every workgroup (%.0f frames): patch wait %.1f, c0%s %.1f, taps %.1f, stores %.1f, all %.1f\n", s[4],
-               s[0] / s[4], form && !DFX_CPH_PARENT_LOOP ? " + taps (one block)" : "", s[1] / s[4], s[2] / s[4], s[3] / s[4], (s[0] + s[1] + s[2] + s[3]) / s[4]);
+               s[0] / s[4], form ? " + taps (one block)" : "", s[1] / s[4], s[2] / s[4], s[3] / s[4], (s[0] + s[1] + s[2] + s[3]) / s[4]);
 #endif
     }
     std::vector<float> h0(nout), h1(nout);

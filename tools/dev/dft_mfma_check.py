@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Dev: numeric model of dfx_fft480_mfma (csrc/dfx_dsp_kernels.h) — the 480-point transform as two chained fp16-split matrix products, 480 = 16 x 30,
+"""Dev: numeric model of dfx_fft480_mfma (the rejected round-5 kernel; its code is tools/dev/patches/r05_fft480_mfma.patch) — the 480-point transform as two chained fp16-split matrix products, 480 = 16 x 30,
 with the kernel's scales (frame peak -> just below 2^14, matrices x 2^13, twiddle factors x 2^-17) — against numpy's double-precision FFT.
     python tools/dev/dft_mfma_check.py"""
 import numpy as np

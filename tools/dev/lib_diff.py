@@ -181,7 +181,8 @@ if len(sys.argv) > 1 and sys.argv[1] == "--child":
 
 import numpy as np
 
-la, lb = sys.argv[1], sys.argv[2]
+(la_name, la), (lb_name, lb) = [l.split("=", 1) if "=" in l else (l, l) for l in sys.argv[1:3]]
+print(f"enhance(): A = {la_name}, B = {lb_name}")
 clips = int(sys.argv[3]) if len(sys.argv) > 3 else 37
 samples = int(sys.argv[4]) if len(sys.argv) > 4 else 100001
 ys = []
