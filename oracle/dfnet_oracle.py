@@ -86,7 +86,7 @@ def gru_manual(x: Tensor, sd, prefix: str, layers: int, h0: Optional[Tensor] = N
     for l in range(layers):
         w_ih, w_hh = _t(sd, f"{prefix}.weight_ih_l{l}"), _t(sd, f"{prefix}.weight_hh_l{l}")
         b_ih, b_hh = _t(sd, f"{prefix}.bias_ih_l{l}"), _t(sd, f"{prefix}.bias_hh_l{l}")
-        h = torch.zeros(B, H) if h0 is None else h0[l]
+        h = x.new_zeros(B, H) if h0 is None else h0[l]
         ys = []
         for t in range(T):
             gi = x[:, t] @ w_ih.t() + b_ih
@@ -104,7 +104,7 @@ def gru_manual(x: Tensor, sd, prefix: str, layers: int, h0: Optional[Tensor] = N
 def gru_aten(x: Tensor, sd, prefix: str, layers: int) -> Tensor:
     """torch.nn.GRU(batch_first=True), h0 = 0 — the ATen kernel the reference calls (modules.py:721)."""
     H = x.shape[-1]
-    g = torch.nn.GRU(H, H, num_layers=layers, batch_first=True)
+    g = torch.nn.GRU(H, H, num_layers=layers, batch_first=True, dtype=x.dtype)
     with torch.no_grad():
         for l in range(layers):
             for n in ("weight_ih", "weight_hh", "bias_ih", "bias_hh"):
@@ -127,6 +127,15 @@ def squeezed_gru(x: Tensor, sd, prefix: str, layers: int, has_out: bool, manual:
     elif skip == "groupedlinear":
         y = y + grouped_linear(x, _t(sd, f"{prefix}.gru_skip.weight"))
     return y
+
+
+def to_dtype(sd, dtype) -> Dict[str, Tensor]:
+    """The state dict with every floating tensor converted to ``dtype`` (float32 -> float64 is exact); integer entries stay."""
+    out = {}
+    for k in sd:
+        v = _t(sd, k)
+        out[k] = v.to(dtype) if v.is_floating_point() else v
+    return out
 
 
 def pad_feat(x: Tensor, lookahead: int) -> Tensor:
@@ -229,7 +238,8 @@ def dfnet_forward(p: ModelParams, sd: Dict[str, Tensor], widths: np.ndarray, spe
                   feat_spec: Tensor, manual_gru: bool = False, run_df: bool = True) -> Dict[str, Tensor]:
     """deepfilternet3.py:389-456 DfNet.forward (lsnr_dropout=False path); run_df=False: :433-446 (mask only, no coefficients).
 
-    spec [B,1,T,F,2], feat_erb [B,1,T,E], feat_spec [B,1,T,F',2]  (all float32).
+    spec [B,1,T,F,2], feat_erb [B,1,T,E], feat_spec [B,1,T,F',2]: float32, or all of them AND every floating tensor of ``sd`` float64 (``to_dtype``):
+    the arithmetic follows the dtype of what it is given, so that the same restatement is its own float64 reference (tests/test_gru_precision.py).
     Returns dict with spec_e [B,1,T,F,2], m [B,1,T,E], lsnr [B,T,1], df_coefs [B,O,T,F',2] plus intermediates.
     """
     O = p.df_order

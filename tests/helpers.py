@@ -84,6 +84,32 @@ def torch_sd(p: ModelParams, seed: int):
     return {k: torch.as_tensor(v) for k, v in sd.items()}
 
 
+LIVELY_GAIN = 4.0      # on the GRU matrices and on the three linear_in weights in front of them
+LIVELY_Z_BIAS = 2.0    # U(0, LIVELY_Z_BIAS) added to the update-gate third of every bias_hh
+
+
+def lively_state_dict(p: ModelParams, seed: int):
+    """random_state_dict with GRUs that work: under the fan-in initialiser the stacks see inputs of std 0.09, hold |h| <= 0.19 and no gate
+    saturates, so an error in the recurrence hardly reaches an output.  Here every GRU matrix and the three linear_in weights are multiplied
+    by LIVELY_GAIN and U(0, LIVELY_Z_BIAS) is added to the update-gate third of bias_hh (PyTorch's gate order r, z, n): gates saturate, z holds
+    states over many frames, r * gh matters, and h moves by tenths per step (tests/test_gru_precision.py asserts these properties on the
+    oracle).  Any accepted shape; numpy float32, the reference's key names."""
+    sd = random_state_dict(p, seed, widths=widths_for(p))
+    rng = np.random.default_rng([seed, 0x6C6976656C79])
+    for name in sd:
+        leaf = name.rsplit(".", 1)[-1]
+        if ".gru." in name and leaf.startswith("weight_"):
+            sd[name] = (LIVELY_GAIN * sd[name]).astype(np.float32)
+        elif ".gru." in name and leaf.startswith("bias_hh"):
+            h = sd[name].shape[0] // 3
+            b = sd[name].copy()
+            b[h:2 * h] += rng.uniform(0.0, LIVELY_Z_BIAS, h).astype(np.float32)
+            sd[name] = b
+        elif name.endswith(".linear_in.0.weight"):
+            sd[name] = (LIVELY_GAIN * sd[name]).astype(np.float32)
+    return sd
+
+
 def rms(a):
     a = np.asarray(a)
     return float(np.sqrt(np.mean(np.abs(a) ** 2)))

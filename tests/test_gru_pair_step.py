@@ -6,25 +6,28 @@ Shapes: the smallest at which the reordered step can go wrong.  Clips 17 (tile 1
 (three 16-clip groups: the last pair's second half is empty); frames per clip 5 (fewer steps than a block of the emb follower), 17 (a full block of
 the projection followers plus one step) and 40.  Sequences this short only take the layer-pipelined forms when the shortest chunk worth a launch is
 lowered (DfNet.set_pipeline): every case asserts through DfNet.last_plan() / Q_GRU_PERSISTENT that the persistent phase really ran and through
-Q_PASSES_PAIR that its recurrences ran on pairs of CUs (and, under DFX_GRU_PAIR=0 / DFX_GRU_SEQ=0, that they did not)."""
+Q_PASSES_PAIR that its recurrences ran on pairs of CUs (and, under DFX_GRU_PAIR=0 / DFX_GRU_SEQ=0, that they did not).
+
+Weights: the seeded random ones, and tests/helpers.py lively_state_dict, under which the forms are compared where h actually moves and gates saturate
+(tests/test_gru_precision.py ties each form to a float64 oracle under the same kind of weights)."""
 import numpy as np
 import pytest
 import torch
 
-from helpers import named_params
+from tests.helpers import lively_state_dict, named_params
 
 HOP = 480
 SWITCHES = ("DFX_GRU_SEQ", "DFX_EXACT_FP32", "DFX_GRU_PAIR", "DFX_GRU_PAIR_FAR")
 
 
-def _run(monkeypatch, p, x, env, persistent, pair=False):
+def _run(monkeypatch, p, x, env, persistent, pair=False, state_dict=None):
     from deepfilternet_amd.enhance import enhance, init_df
 
     for k in SWITCHES:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    model, df_state, _, _ = init_df(params=p, epoch="none", seed=4)   # (the switches are read when the handle is created)
+    model, df_state, _, _ = init_df(params=p, state_dict=state_dict, epoch="none", seed=4)   # (the switches are read when the handle is created; no state_dict: seeded random weights)
     model.set_pipeline(time_chunks=12, min_chunk_frames=2)
     before, before_pair = model.query(model.Q_PASSES_PERSISTENT), model.query(model.Q_PASSES_PAIR)
     ys = [enhance(model, df_state, x, pad=False).cpu() for _ in range(3)]
@@ -39,16 +42,19 @@ def _run(monkeypatch, p, x, env, persistent, pair=False):
     return ys[0]
 
 
+# weights: "random" = init_df's seeded random_state_dict, under which the GRUs are almost idle (|h| <= 0.19); "lively" = tests/helpers.py
+# lively_state_dict: h moves by tenths per step and gates saturate, so what a hand-over delivers a step late or to the wrong rows shows in the samples
 @pytest.mark.gpu
-@pytest.mark.parametrize("frames", [5, 17, 40])
-@pytest.mark.parametrize("clips", [17, 20, 48])
-def test_pair_step_gives_the_bits_of_the_other_forms(hip_backend, clips, frames, monkeypatch):
+@pytest.mark.parametrize("clips,frames,weights", [pytest.param(c, f, w, id=f"{c}-{f}" + ("" if w == "random" else "-lively"))
+                                                  for w in ("random", "lively") for f in (5, 17, 40) for c in (17, 20, 48)])
+def test_pair_step_gives_the_bits_of_the_other_forms(hip_backend, clips, frames, weights, monkeypatch):
     p = named_params("df3")
+    sd = lively_state_dict(p, 4) if weights == "lively" else None
     x = torch.from_numpy((0.1 * np.random.default_rng(100 * clips + frames).standard_normal((clips, frames * HOP))).astype(np.float32)).cuda()
-    y_pair = _run(monkeypatch, p, x, {}, True, pair=True)
+    y_pair = _run(monkeypatch, p, x, {}, True, pair=True, state_dict=sd)
     assert torch.isfinite(y_pair).all() and float(y_pair.abs().max()) > 0
-    assert torch.equal(y_pair, _run(monkeypatch, p, x, {"DFX_GRU_PAIR": "0"}, True))
-    assert torch.equal(y_pair, _run(monkeypatch, p, x, {"DFX_GRU_SEQ": "0"}, False))
+    assert torch.equal(y_pair, _run(monkeypatch, p, x, {"DFX_GRU_PAIR": "0"}, True, state_dict=sd))
+    assert torch.equal(y_pair, _run(monkeypatch, p, x, {"DFX_GRU_SEQ": "0"}, False, state_dict=sd))
 
 
 @pytest.mark.gpu

@@ -57,6 +57,32 @@ def test_stream_equals_batch_delayed(backend, name):
     model.check()
 
 
+def test_stream_equals_batch_delayed_with_lively_weights(backend):
+    """The same with GRUs that work (tests/helpers.py lively_state_dict: gates saturate, h moves by tenths per hop), so the state the runtime
+    carries from call to call matters to the samples; tests/test_gru_precision.py ties the batch side's network to a float64 oracle."""
+    from deepfilternet_amd.enhance import enhance, init_df
+    from deepfilternet_amd.streaming import DfStream
+    from tests.helpers import lively_state_dict
+
+    p = named_params("df3")
+    sd = lively_state_dict(p, 9)
+    model, df_state, _, _ = init_df(params=p, state_dict=sd, epoch="none")
+    hop, T = 480, (9 if backend == "emu" else 23)
+    x = torch.from_numpy((0.1 * np.random.default_rng(2).standard_normal((3, hop * T))).astype(np.float32))
+    ref = enhance(model, df_state, x, pad=False).cpu()
+    assert rms(ref.numpy() - O.enhance(p, {k: torch.as_tensor(v) for k, v in sd.items()}, x.numpy(), pad=False)) < 2e-6
+    rt = DfStream(model, df_state, streams=3, max_frames=7)
+    d = rt.delay_frames
+    for cuts in (([1, 1, 1, 3, 1, 2],) if backend == "emu" else ([1] * T, [7, 7, 7, 2], [3, 1, 5, 2, 7, 1, 4])):
+        rt.reset()
+        y = _run_stream(rt, x, cuts).cpu()
+        assert y.shape == x.shape and float(y[:, : d * hop].abs().max()) == 0.0   # warm-up hops are silence
+        err = rms((y[:, d * hop:] - ref[:, : (T - d) * hop]).numpy())
+        print(f"  df3 lively [{backend}] cuts {cuts if len(cuts) < 9 else '1 x %d' % len(cuts)}: rms {err:.3e}")
+        assert err < 1e-6, (cuts, err)
+    model.check()
+
+
 def test_stream_controls(backend):
     from deepfilternet_amd.enhance import enhance, init_df
     from deepfilternet_amd.streaming import DfStream
