@@ -13,7 +13,7 @@ _os.environ.setdefault("GPU_MAX_HW_QUEUES", "24")
 from .config import ModelParams  # noqa: F401,E402
 
 __version__ = "0.1.0"
-__all__ = ["ModelParams", "init_df", "enhance", "enhance_batch", "enhance_long", "enhance_files", "df_features", "DfNet", "libdf", "export_dfx"]
+__all__ = ["ModelParams", "init_df", "enhance", "enhance_batch", "enhance_long", "enhance_files", "df_features", "DfNet", "libdf", "export_dfx", "metrics"]
 
 
 def __getattr__(name):
@@ -31,8 +31,8 @@ def __getattr__(name):
         from .model import export_dfx
 
         return export_dfx
-    if name == "libdf":
+    if name in ("libdf", "metrics"):
         import importlib
 
-        return importlib.import_module(".libdf", __name__)
+        return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

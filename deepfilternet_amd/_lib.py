@@ -116,6 +116,10 @@ SIGNATURES = {
     "dfx_resampler_out_len": (_i64, [_vp, _i64]),
     "dfx_resampler_kernel": (_i, [_i, _i, _i, C.c_double, _i, C.c_double, C.POINTER(_i), C.POINTER(_i), C.POINTER(_i), _f32p, _i64]),
     "dfx_resample": (_i, [_vp, _fp, _i64, _i64, _i64, _fp, _i64, _vp]),
+    "dfx_si_sdr_workspace_bytes": (_i, [_i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dfx_si_sdr": (_i, [_fp, _fp, _i64, _i64, C.POINTER(_i64), _fp, _vp, _i64, _vp]),
+    "dfx_stoi_workspace_bytes": (_i, [_i, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dfx_stoi": (_i, [_vp, _fp, _fp, _i64, _i64, C.POINTER(_i64), _fp, _vp, _vp, _i64, _vp]),
     "dfx_stream_create": (_i, [_vp, _vp, _i64, _i, C.POINTER(_vp)]),
     "dfx_stream_free": (None, [_vp]),
     "dfx_stream_reset": (_i, [_vp, _vp]),

@@ -25,7 +25,8 @@ struct dfx_resampler {
 struct DfxRsArgs {
     int64_t B, T, x_stride, y_stride, out_len, frames;  // frames = ceil(out_len / nw) per clip
     int orig, nw, nw_pad, width, K4, tn, fw, jw;        // K4 = taps padded to a multiple of 4 (zero taps); tn = 64*fw frames per workgroup
-};
+    const int64_t *rows;                                // null, or device [2][B]: row b has rows[b] input and rows[B + b] output samples (T, out_len,
+};                                                      //   frames are then the largest row's: workgroups past a row's own frames exit)
 
 // One thread per output frame n (nw consecutive output samples).  A workgroup is 4 waves = fw groups of 64 frames x jw groups of
 // phase tiles (fw * jw == 4): the input segment of its 64*fw frames sits in LDS once (lane n reads xs[n*orig + k]: stride orig
@@ -40,6 +41,11 @@ __global__ void __launch_bounds__(256) dfx_k_resample(const float *__restrict__ 
     const int64_t b = blockIdx.x / tiles;
     const int64_t n0 = (int64_t)(blockIdx.x - b * tiles) * A.tn;
     if (b >= A.B) return;
+    if (A.rows) {
+        A.T = A.rows[b], A.out_len = A.rows[A.B + b];
+        A.frames = (A.out_len + A.nw - 1) / A.nw;
+        if (n0 >= A.frames) return;
+    }
     const float *xb = x + b * A.x_stride;
     const int seg = (A.tn - 1) * A.orig + A.K4;
     const int64_t s0 = n0 * A.orig - A.width;  // stream index of xs[0]
@@ -239,8 +245,9 @@ extern "C" int dfx_resampler_kernel(int orig_sr, int new_sr, int lowpass_filter_
     return DFX_OK;
 }
 
-extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, int64_t T, int64_t x_stride, float *y, int64_t y_stride,
-                            void *stream) {
+// rows: null, or device [2][B] (DfxRsArgs::rows): every row its own length, T the largest
+static int dfx_resample_rows(const dfx_resampler *r, const float *x, int64_t B, int64_t T, int64_t x_stride, float *y, int64_t y_stride,
+                             const int64_t *rows, void *stream) {
     if (!r || B < 0 || T < 0 || x_stride < T) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_resample: bad arguments");
     if (int rc = dfx_require_device()) return rc;
     const int64_t out_len = dfx_resampler_out_len(r, T);
@@ -248,7 +255,7 @@ extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, i
     if (B == 0 || out_len == 0) return DFX_OK;
     if (!x || !y) DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_resample: null buffer");
     DfxRsArgs A;
-    A.B = B, A.T = T, A.x_stride = x_stride, A.y_stride = y_stride, A.out_len = out_len;
+    A.B = B, A.T = T, A.x_stride = x_stride, A.y_stride = y_stride, A.out_len = out_len, A.rows = rows;
     A.frames = dfx_ceil_div(out_len, r->nw);
     A.orig = r->orig, A.nw = r->nw, A.nw_pad = r->nw_pad, A.width = r->width, A.K4 = r->K4;
     // 4 waves per workgroup: jw of them split the phase tiles (as many as there are tiles, 1 / 2 / 4), fw = 4 / jw own 64 frames each
@@ -267,4 +274,10 @@ extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, i
     return DFX_OK;
 }
 
+extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, int64_t T, int64_t x_stride, float *y, int64_t y_stride,
+                            void *stream) {
+    return dfx_resample_rows(r, x, B, T, x_stride, y, y_stride, nullptr, stream);
+}
+
+#include "dfx_metrics.h"
 #include "dfx_io_stream.h"

@@ -623,6 +623,31 @@ int dfx_stream_resampler_process(dfx_stream_resampler *h, const void *x, int x_f
                                  int y_format, int64_t y_stride, const unsigned char *active_host /* NULL = all */, void *stream);
 
 /* ------------------------------------------------------------------------------------------------------------------
+ * Scoring on the device: what the reference computes per clip on a CPU process pool (df/evaluation_utils.py SiSDRMetric / StoiMetric,
+ * evaluation_loop_dir_only) and pins its released models with (df/scripts/test_df.py:18-21,44-78).
+ *   dfx_si_sdr   si_sdr_speechmetrics (evaluation_utils.py:599-619) of every row, in two passes like the reference: rss = ref . ref and ref . est,
+ *                a = (eps + ref . est) / (rss + eps), then sum (a ref)^2 and sum (est - a ref)^2; out[b] = 10 log10((eps + sss) / (eps + snn)) dB,
+ *                eps = float32's.  Float32 products and differences as numpy forms them on float32 input, float64 sums.
+ *   dfx_stoi     df.stoi.stoi (stoi.py:163-231) of every row: both signals to 10 kHz (r: a dfx_resampler fs_source -> 10000, the reference's
+ *                df.io.resample default set is sinc_fast; NULL: the rows are at 10 kHz already), remove_silent_frames (stoi.py:35-110), the
+ *                512-point STFT (:146-160), thirdoct(10000, 512, 15, 150) (:113-143), the 30-frame normalised, clipped correlations (:206-230).
+ * ref / est / clean / degraded: DEVICE float32 [B, stride]; lengths_host: HOST int64 [B], row b has lengths_host[b] <= stride samples (not read
+ * after the return: the counts travel as kernel arguments); out: DEVICE float32 [B].  A row's result is that of the row alone —
+ * stoi(clean[b : b + 1, : lengths[b]], ...) —: the same bits whatever the batch around it, the padding behind it and the workspace's contents
+ * (the reference pads a batch to one length, which moves its pad_front; that is not copied).  Rows the reference skips (fewer than 512 samples
+ * left after silent-frame removal, stoi.py:195-197, where it leaves out[i] uninitialised) give NaN.  info: NULL, or DEVICE int32 [B][4]: windows
+ * examined, windows kept, STFT frames L, segments J (L = J = 0 for a skipped row).  The workspace (DEVICE, 16-byte aligned, the *_workspace_bytes
+ * of the same arguments; host arithmetic) is the caller's; the calls only enqueue on `stream`: no copy to the host, no wait, no float atomics.
+ * DFX_ERR_INVALID_ARG: a length outside [0, stride], a workspace that is too small, a resampler to another rate than 10 kHz.
+ * ---------------------------------------------------------------------------------------------------------------- */
+int dfx_si_sdr_workspace_bytes(int64_t B, const int64_t *lengths_host, int64_t *bytes);
+int dfx_si_sdr(const float *ref, const float *est, int64_t B, int64_t stride, const int64_t *lengths_host, float *out, void *workspace,
+               int64_t workspace_bytes, void *stream);
+int dfx_stoi_workspace_bytes(int fs_source, int64_t B, const int64_t *lengths_host, int64_t *bytes);
+int dfx_stoi(const dfx_resampler *r, const float *clean, const float *degraded, int64_t B, int64_t stride, const int64_t *lengths_host,
+             float *out, int32_t *info, void *workspace, int64_t workspace_bytes, void *stream);
+
+/* ------------------------------------------------------------------------------------------------------------------
  * Per-kernel timing (measurement aid, no reference counterpart; the reference only logs wall-clock RTF,
  * DeepFilterNet/df/enhance.py:77-87).  When a kernel's bit is set in `kernel_mask`, every launch of it is bracketed by
  * two hipEvents recorded on the stream the kernel is launched on.  dfx_prof_read() synchronises the pending events and
