@@ -31,6 +31,9 @@ int dfx_require_device();
 // the history rows of a step-form resampler (dfx_io_stream.h), for dfx_stream_export_streams / dfx_stream_import_streams
 void dfx_stream_resampler_rows(const dfx_stream_resampler *h, float **cur, float **other, int *hist);
 
+// LDS a workgroup can have on gfx950 (static + dynamic); the same number on the interpreter build, so that both refuse the same sizes
+#define DFX_LDS_PER_WG (160 * 1024)
+
 // ---- FFT plan (passed by value into kernels) ----------------------------------------------------------------------
 #define DFX_MAX_STAGES 12
 struct DfxFftPlan {

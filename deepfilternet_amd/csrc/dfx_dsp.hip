@@ -251,12 +251,14 @@ static int make_plan(int N, DfxFftPlan *pl) {
     return rem == 1 ? 0 : -1;
 }
 
+static size_t dsp_smem_bytes(const dfx_state *st);   // (launch helpers below; dfx_state_create holds every accepted size to them)
+static size_t ana_smem_bytes(const dfx_state *st);
+
 extern "C" int dfx_state_create(int sr, int fft_size, int hop_size, int nb_bands, int min_nb_erb_freqs, dfx_state **out) {
     if (!out || sr <= 0 || fft_size <= 0 || hop_size <= 0 || nb_bands <= 0)
         DFX_FAIL(DFX_ERR_INVALID_ARG, "dfx_state_create: bad arguments");
     if (hop_size * 2 > fft_size) DFX_FAIL(DFX_ERR_INVALID_ARG, "assertion failed: hop_size * 2 <= fft_size");  // lib.rs:111
     if (fft_size & 1) DFX_FAIL(DFX_ERR_UNSUPPORTED, "fft_size must be even");
-    if (fft_size > 4096) DFX_FAIL(DFX_ERR_UNSUPPORTED, "fft_size > 4096 is not supported by the LDS-resident FFT");
     if ((fft_size + hop_size - 1) / hop_size > DFX_DSP_TEAMS)
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "fft_size/hop_size > %d overlapping frames is not supported", DFX_DSP_TEAMS);
     if (int rc = dfx_require_device()) return rc;
@@ -269,6 +271,14 @@ extern "C" int dfx_state_create(int sr, int fft_size, int hop_size, int nb_bands
     if (make_plan(fft_size, &st->plan) != 0) {
         delete st;
         DFX_FAIL(DFX_ERR_UNSUPPORTED, "fft_size/2 = %d has a prime factor other than 2, 3, 5", fft_size / 2);
+    }
+    // the transforms are LDS-resident: what the analysis or the synthesis launch of this state asks for must fit a workgroup (on every build:
+    // the interpreter has no such limit of its own)
+    const size_t smem = std::max(ana_smem_bytes(st), dsp_smem_bytes(st));
+    if (smem > DFX_LDS_PER_WG) {
+        delete st;
+        DFX_FAIL(DFX_ERR_UNSUPPORTED, "fft_size %d with %d ERB bands needs %zu bytes of LDS per workgroup for the LDS-resident FFT, the limit is %d",
+                 fft_size, nb_bands, smem, DFX_LDS_PER_WG);
     }
     // vorbis window in f64, stored as f32 (lib.rs:126-133)
     st->window_host.resize(fft_size);

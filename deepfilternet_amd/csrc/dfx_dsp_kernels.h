@@ -979,7 +979,7 @@ __global__ void __launch_bounds__(DFX_DSP_THREADS, IP ? 6 : 4) dfx_k_synthesis(D
 #pragma unroll
         for (int u = 0; u < 8; ++u) {
             const int k = lr + u * DFX_DSP_TEAM;
-            pre[u] = Y[k <= M ? k : lr];
+            pre[u] = Y[k <= M ? k : 0];   // (bin 0, not the lane's own: with fewer than 64 bins a lane's own index lies behind the frame)
         }
     };
     for (int64_t item = blockIdx.x; item < A.B * A.chunks; item += gridDim.x) {

@@ -67,8 +67,11 @@ int dfx_bands_nfreqs(const dfx_bands *b);
  * explicit caller-owned buffers (mem_in / mem_out below), so one handle serves any number of concurrent batches.
  * ---------------------------------------------------------------------------------------------------------------- */
 typedef struct dfx_state dfx_state;
-/* Fails with DFX_ERR_INVALID_ARG if hop*2 > fft (lib.rs:111 assert) and DFX_ERR_UNSUPPORTED if fft/2 has a prime
- * factor other than 2, 3, 5 or fft > 4096. */
+/* Fails with DFX_ERR_INVALID_ARG if hop*2 > fft (lib.rs:111 assert) and DFX_ERR_UNSUPPORTED if fft is odd, if fft/2 has a
+ * prime factor other than 2, 3, 5, if more than 8 frames overlap (fft / hop rounded up), or if the LDS-resident transforms
+ * of this size do not fit a workgroup: the analysis launch needs 76 * fft + 256 bytes of LDS and about 12 bytes per ERB band
+ * of tables (2.9 KB at 8 bands, 3.6 KB at 64), against 163 840 bytes.  fft = 2048 fits, fft = 2160 does not; the message
+ * names the bytes asked for and the limit.  The same limit holds on the CPU interpreter build. */
 int dfx_state_create(int sr, int fft_size, int hop_size, int nb_bands, int min_nb_erb_freqs, dfx_state **out);
 void dfx_state_free(dfx_state *st);
 int dfx_state_sr(const dfx_state *st);

@@ -115,6 +115,42 @@ def rms(a):
     return float(np.sqrt(np.mean(np.abs(a) ** 2)))
 
 
+DSP_MARGIN = 4.0   # as tests/test_gru_precision.py: two factors of two (see hold_to_f64)
+
+
+def dsp_base(c32, r64, rows: bool = False):
+    """(base, E32) of the DSP bound, from the oracles alone: E32 = |C oracle - dsp64|, float32's own error on the case, and
+    base = max(E32, 2^-23 max|dsp64|) — float32's spacing at the output's scale, which matters where the C oracle happens to round exactly
+    (10 log10f(1e-10f) is such a value).  ``rows``: one value per row (axis 0) instead of one over the whole array."""
+    c32, r64 = np.asarray(c32), np.asarray(r64)
+    assert c32.shape == r64.shape, (c32.shape, r64.shape)
+    ax = tuple(range(1, r64.ndim)) if rows else None
+    e32 = np.abs(c32 - r64).max(axis=ax)
+    return np.maximum(e32, 2.0 ** -23 * np.abs(r64).max(axis=ax)), e32
+
+
+def hold_to_f64(got, c32, r64, label: str, rows: bool = False, need_e32: bool = True):
+    """|kernel - dsp64| <= DSP_MARGIN * max(E32, 2^-23 max|dsp64|)  (oracle/dsp64.py is the float64 reference, the C oracle gives E32).
+    The kernel's factorisation and operation order are a second, independent draw of an error the size of E32, and a maximum over a few
+    thousand values scatters by about a factor of two: DSP_MARGIN = 4.  Nothing in the bound comes from what the kernel returns.  The achieved
+    ratio is printed (pytest -s; docs/measurements.md records the GPU's) and returned.  ``need_e32``: the case must be long enough for the C
+    oracle to round at all (E32 > 0)."""
+    got = np.asarray(got)
+    base, e32 = dsp_base(c32, r64, rows)
+    assert got.shape == np.asarray(r64).shape and np.isfinite(got).all(), label
+    if need_e32:
+        assert np.all(e32 > 0), (label, e32)
+    ax = tuple(range(1, got.ndim)) if rows else None
+    err = np.abs(got - np.asarray(r64)).max(axis=ax)
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ratio = np.where(base > 0, err / np.where(base > 0, base, 1.0), np.where(err > 0, np.inf, 0.0))
+    bits = "bit-equal to the C oracle" if np.array_equal(got, np.asarray(c32)) else ""
+    print(f"  {label}: |kernel - f64| / max(E32, ulp) = {np.array2string(np.atleast_1d(ratio), precision=2, separator=' ')}"
+          f"  E32 {np.array2string(np.atleast_1d(e32), precision=2, separator=' ')} {bits}")
+    assert np.all(ratio <= DSP_MARGIN), (label, ratio)
+    return ratio
+
+
 def emu_subset(backend: str) -> bool:
     """True when a test case should be skipped on the CPU interpreter to keep the CPU suite within a few minutes: the case still runs
     on the GPU (-m gpu), and on the interpreter too with DFX_EMU_ALL=1."""

@@ -2,13 +2,15 @@
 
 Every test runs twice: backend 'emu' executes the same kernel sources on the CPU SIMT interpreter (CPU CI, no GPU),
 backend 'hip' (-m gpu) executes libdfx.so on the MI355X.  Tolerances: index arithmetic (frame/band/bin placement) is
-exact; float values within a few ulp of the oracle (different FFT factorisation / fma contraction)."""
+exact; float values are held to the float64 restatement oracle/dsp64.py within 4 x max(|C oracle - dsp64|, float32's spacing at the output's scale)
+(tests/helpers.py hold_to_f64: the C oracle's own error on the case sets the bar) where that bound applies; elementwise relative bars stay."""
 import numpy as np
 import pytest
 import torch
 
+from oracle import dsp64 as R64
 from oracle import libdf_oracle as L
-from tests.helpers import rms
+from tests.helpers import hold_to_f64, rms
 
 
 def _libdf():
@@ -27,7 +29,7 @@ def test_analysis_matches_oracle(backend, N, H, nb):
     assert np.array_equal(d.fft_window(), o.fft_window())
     S, R = d.analysis(x), o.analysis(x)
     assert S.shape == R.shape and S.dtype == np.complex64
-    assert np.abs(S - R).max() < 3e-7 * max(1.0, np.abs(R).max() / 0.02)
+    hold_to_f64(S, R, R64.analysis(x, N, H)[0], f"analysis {N}/{H}")
 
 
 def test_analysis_many_frames_gridstride(backend):
@@ -35,7 +37,7 @@ def test_analysis_many_frames_gridstride(backend):
     rng = np.random.default_rng(1)
     x = rng.standard_normal((5, 96 * 41)).astype(np.float32)
     S, R = D.DF(48000, 192, 96, 8, 1).analysis(x), L.DF(48000, 192, 96, 8, 1).analysis(x)
-    assert np.abs(S - R).max() < 1e-6
+    hold_to_f64(S, R, R64.analysis(x, 192, 96)[0], "analysis 192/96, 5 x 41 frames")
 
 
 @pytest.mark.parametrize("N,H", [(960, 480), (192, 96), (96, 24), (960, 240)])
@@ -48,7 +50,7 @@ def test_synthesis_matches_oracle(backend, N, H):
     y, r = D.DF(48000, N, H, 8, 1).synthesis(Y), L.DF(48000, N, H, 8, 1).synthesis(Y)
     assert np.array_equal(Y, keep)
     assert y.shape == r.shape == (2, 19 * H)
-    assert np.abs(y - r).max() < 2e-5 * np.abs(r).max()
+    hold_to_f64(y, r, R64.synthesis(Y, N, H)[0], f"synthesis {N}/{H}")
 
 
 def test_roundtrip_and_streaming_state(backend):
@@ -64,12 +66,12 @@ def test_roundtrip_and_streaming_state(backend):
     d.reset()
     a = d.analysis(x[:, :480 * 5].copy(), reset=False)
     b = d.analysis(x[:, 480 * 5:].copy(), reset=False)
-    assert np.abs(np.concatenate([a, b], 1) - full).max() < 1e-6
+    hold_to_f64(np.concatenate([a, b], 1), full, R64.analysis(x, 960, 480)[0], "analysis 960/480 cut at frame 5")
     ys = o.synthesis(full.copy())
     d.reset()
     y1 = d.synthesis(full[:, :5].copy(), reset=False)
     y2 = d.synthesis(full[:, 5:].copy(), reset=False)
-    assert np.abs(np.concatenate([y1, y2], 1) - ys).max() < 2e-6
+    hold_to_f64(np.concatenate([y1, y2], 1), ys, R64.synthesis(full, 960, 480)[0], "synthesis 960/480 cut at frame 5")
 
 
 def test_roundtrip_quarter_hop_streaming(backend):
@@ -79,10 +81,11 @@ def test_roundtrip_quarter_hop_streaming(backend):
     x = rng.uniform(-1, 1, (2, 24 * 30)).astype(np.float32)
     S = o.analysis(x)
     ys = o.synthesis(S.copy())
-    assert np.abs(d.synthesis(S.copy()) - ys).max() < 2e-6
+    ys64 = R64.synthesis(S, 96, 24)[0]
+    hold_to_f64(d.synthesis(S.copy()), ys, ys64, "synthesis 96/24")
     d2 = D.DF(48000, 96, 24, 8, 1)
     parts = [d2.synthesis(S[:1, a:b].copy(), reset=False) for a, b in ((0, 3), (3, 4), (4, 17), (17, 30))]
-    assert np.abs(np.concatenate(parts, 1) - ys[:1]).max() < 2e-6
+    hold_to_f64(np.concatenate(parts, 1), ys[:1], ys64[:1], "synthesis 96/24 cut at frames 3, 4, 17")
 
 
 def test_erb_family_matches_oracle(backend):
@@ -93,7 +96,9 @@ def test_erb_family_matches_oracle(backend):
     for db in (True, False):
         a, b = D.erb(X, w, db), L.erb(X, w, db)
         assert a.shape == b.shape == (2, 3, 9, 32)
-        assert np.allclose(a, b, rtol=2e-6, atol=2e-5 if db else 1e-9)
+        assert np.allclose(a, b, rtol=2e-6, atol=2e-5 if db else 1e-9)   # (relative per element: band energies span orders of magnitude)
+        if db:
+            hold_to_f64(a, b, R64.erb_db(X, w), "erb dB")
     assert D.erb(X[0, 0], w).shape == (9, 32)
     g = rng.uniform(0, 1, (2, 7, 32)).astype(np.float32)
     assert np.array_equal(D.erb_inv(g, w), L.erb_inv(g, w))
@@ -118,9 +123,9 @@ def test_norms_match_oracle(backend):
     keep = X.copy()
     a, b = D.unit_norm(X, 0.99), L.unit_norm(X, 0.99)
     assert np.array_equal(X, keep)
-    assert np.abs(a - b).max() < 1e-5 * np.abs(b).max()
+    hold_to_f64(a, b, R64.unit_norm(X, 0.99)[0], "unit_norm")
     stu = rng.uniform(1e-4, 1e-3, (2, 96)).astype(np.float32)
-    assert np.abs(D.unit_norm(X, 0.99, stu) - L.unit_norm(X, 0.99, stu)).max() < 1e-5 * np.abs(b).max()
+    hold_to_f64(D.unit_norm(X, 0.99, stu), L.unit_norm(X, 0.99, stu), R64.unit_norm(X, 0.99, stu)[0], "unit_norm from a state")
 
 
 def test_features_fused_matches_oracle_pipeline(backend):
@@ -136,10 +141,11 @@ def test_features_fused_matches_oracle_pipeline(backend):
     FS = L.unit_norm(np.ascontiguousarray(S[..., :96]), 0.99)
     assert spec.shape == (3, 1, 13, 481, 2) and fe.shape == (3, 1, 13, 32) and fs.shape == (3, 1, 13, 96, 2)
     sc = torch.view_as_complex(spec.squeeze(1).cpu()).numpy()
-    assert np.abs(sc - S).max() < 1e-6
-    assert np.abs(fe.squeeze(1).cpu().numpy() - FE).max() < 2e-5
+    S64 = R64.analysis(x, 960, 480)[0]
+    hold_to_f64(sc, S, S64, "df_features spec")
+    hold_to_f64(fe.squeeze(1).cpu().numpy(), FE, R64.erb_norm(R64.erb_db(S64, o.erb_widths()), 0.99)[0], "df_features feat_erb")
     fsc = torch.view_as_complex(fs.squeeze(1).cpu()).numpy()
-    assert np.abs(fsc - FS).max() < 2e-5 * np.abs(FS).max()
+    hold_to_f64(fsc, FS, R64.unit_norm(S64[..., :96], 0.99)[0], "df_features feat_spec")
 
 
 @pytest.mark.parametrize("N,H,nb,minf", [(960, 480, 32, 2), (960, 480, 80, 1), (320, 160, 24, 1), (192, 96, 8, 1), (960, 240, 64, 1)])
@@ -172,7 +178,7 @@ def test_device_tensor_path_no_host_roundtrip(backend):
     assert isinstance(S, torch.Tensor) and S.dtype == torch.complex64 and S.device.type == _lib.device().type
     un = D.unit_norm(S[..., :40], 0.99)  # strided view read in place
     ref = L.unit_norm(np.ascontiguousarray(L.DF(48000, 192, 96, 8, 1).analysis(x)[..., :40]), 0.99)
-    assert np.abs(un.cpu().numpy() - ref).max() < 1e-5 * np.abs(ref).max()
+    hold_to_f64(un.cpu().numpy(), ref, R64.unit_norm(R64.analysis(x, 192, 96)[0][..., :40], 0.99)[0], "unit_norm of a strided device view")
 
 
 def test_error_conventions(backend):
