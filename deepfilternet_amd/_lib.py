@@ -120,6 +120,8 @@ SIGNATURES = {
     "dfx_si_sdr": (_i, [_fp, _fp, _i64, _i64, C.POINTER(_i64), _fp, _vp, _i64, _vp]),
     "dfx_stoi_workspace_bytes": (_i, [_i, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
     "dfx_stoi": (_i, [_vp, _fp, _fp, _i64, _i64, C.POINTER(_i64), _fp, _vp, _vp, _i64, _vp]),
+    "dfx_sepm_workspace_bytes": (_i, [_i, _i64, C.POINTER(_i64), C.POINTER(_i64)]),
+    "dfx_sepm": (_i, [_vp, _fp, _fp, _i64, _i64, C.POINTER(_i64), _fp, _vp, _vp, _i64, _vp]),
     "dfx_stream_create": (_i, [_vp, _vp, _i64, _i, C.POINTER(_vp)]),
     "dfx_stream_free": (None, [_vp]),
     "dfx_stream_reset": (_i, [_vp, _vp]),

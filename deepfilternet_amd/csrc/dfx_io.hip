@@ -280,4 +280,5 @@ extern "C" int dfx_resample(const dfx_resampler *r, const float *x, int64_t B, i
 }
 
 #include "dfx_metrics.h"
+#include "dfx_sepm.h"
 #include "dfx_io_stream.h"

@@ -3,8 +3,11 @@ and what ``df/evaluation_utils.py`` (``SiSDRMetric``, ``StoiMetric``, ``evaluati
 
     si_sdr(reference, estimate, lengths=None) -> Tensor[B]      evaluation_utils.py:599-619 (si_sdr_speechmetrics), dB
     stoi(clean, degraded, sr, lengths=None, return_info=False)  df/stoi.py:163-231
-    score_files([(clean, enhanced), ...], sr=None)              [{"sisdr", "stoi"}] per pair of files
-    python -m deepfilternet_amd.metrics CLEAN_DIR ENHANCED_DIR [--csv FILE]
+    sepm(clean, processed, sr, lengths=None)                    df/sepm.py: {"ssnr", "llr", "wss", "fwsnr"} from one pass;
+    seg_snr / llr / wss / fw_seg_snr(clean, processed, sr)      one of them (SNRseg :28-51, llr :241-277, wss :299-487, fwSNRseg :54-182)
+    composite(clean, processed, sr, pesq=None)                  sepm.py:490-510: {"pesq", "csig", "cbak", "covl", "ssnr", "llr", "wss"}
+    score_files([(clean, enhanced), ...], sr=None)              [{"sisdr", "stoi"}] per pair of files (composite=True: + ssnr, llr, wss, fwsnr)
+    python -m deepfilternet_amd.metrics CLEAN_DIR ENHANCED_DIR [--csv FILE] [--composite]
 
 Inputs: ``[T]``, ``[B, T]`` or a list of 1-D tensors of different lengths (what ``enhance_batch`` returns), on the CPU or the device, float32 or
 int16 PCM (scaled with ``pcm16_to_float``).  ``lengths`` gives each row's sample count inside a padded ``[B, T]``.  Row ``i`` of a batch is
@@ -16,6 +19,13 @@ STOI resamples from ``sr`` to 10 kHz with the library's resampler and the refere
 rate the resampler takes is accepted, rates below 10 kHz included (they are up-sampled, as the reference does); ``sr == 10000`` resamples nothing.
 Rows the reference skips (fewer than 512 samples left after silent-frame removal, stoi.py:195-197, where it leaves ``out[i]`` uninitialised)
 are NaN.  ``return_info=True`` adds an int32 ``[B, 4]`` tensor: windows examined, windows kept, STFT frames L, segments J (L = J = 0 when skipped).
+
+The composite measures' parts are computed at 16 kHz in float64, as ``sepm.py`` computes them; other rates are resampled first with the same
+resampler (``sinc_fast``, evaluation_utils.py:32,583-584), every row with its own length.  Clips of fewer than 600 samples at 16 kHz have no
+frame (the reference raises, or averages nothing): NaN.  LLR's two quadratic forms are taken in float64 from the float32-rounded LPC
+coefficients and lags; the reference takes them in float32 (2e-8 .. 3e-7 apart for noise-like clips, up to 4e-3 for strongly tonal ones, where
+the float32 value is the inexact one).  PESQ (ITU-T P.862) is not computed here: it is not in the reference's own code either (it calls the
+third-party ``pesq`` package); ``composite`` takes the caller's values.
 
 NOTE: test_df.py's STOI pins were produced by pystoi, not by ``df/stoi.py`` (whose docstring says "use pystoi for reporting test results");
 this module implements ``df/stoi.py``.
@@ -32,6 +42,7 @@ from . import _lib
 from .io import _resampler, load_audio, pcm16_to_float
 
 STOI_FS = 10_000
+SEPM_FS = 16_000
 Audio = Union[torch.Tensor, Sequence[torch.Tensor]]
 
 
@@ -124,6 +135,78 @@ def stoi(clean: Audio, degraded: Audio, sr: int, lengths=None, return_info: bool
     return (out, info) if return_info else out
 
 
+def sepm(clean: Audio, processed: Audio, sr: int, lengths=None, dtype: torch.dtype = torch.float32, return_info: bool = False,
+         workspace: Optional[torch.Tensor] = None):
+    """Segmental SNR, LLR, WSS and frequency-weighted segmental SNR of every row as ``df/sepm.py`` defines them, from one pass:
+    ``{"ssnr", "llr", "wss", "fwsnr"}``, each ``[B]`` on the device.  The values are computed in float64; ``dtype=torch.float64`` hands them out
+    unrounded.  With ``return_info`` also int32 ``[B, 2]``: frames F, and the K = round(0.95 F) smallest per-frame values LLR and WSS average."""
+    sr = int(sr)
+    if sr <= 0:
+        raise ValueError("sepm: sr must be positive")
+    if dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"sepm: results are float32 or float64, not {dtype}")
+    x, y, lens, B, T = _pair(clean, processed, lengths, "sepm")
+    L = _lib.lib()
+    r = _resampler(sr, SEPM_FS, "sinc_fast", _lib.library_path()) if sr != SEPM_FS else None
+    out = torch.empty((B, 4), dtype=torch.float64, device=x.device)
+    info = torch.zeros((B, 2), dtype=torch.int32, device=x.device) if return_info else None
+    if workspace is None:
+        need = C.c_int64()
+        _check(L.dfx_sepm_workspace_bytes(sr, B, lens, C.byref(need)))
+        workspace = _workspace(need.value)
+    _check(L.dfx_sepm(r.h if r is not None else None, _lib.ptr(x), _lib.ptr(y), B, T, lens, _lib.ptr(out), _lib.ptr(info), _lib.ptr(workspace),
+                      int(workspace.numel()), _lib.stream()))
+    res = {k: out[:, i].to(dtype) for i, k in enumerate(("ssnr", "llr", "wss", "fwsnr"))}
+    return (res, info) if return_info else res
+
+
+def seg_snr(clean: Audio, processed: Audio, sr: int, **kw) -> torch.Tensor:
+    """Segmental SNR in dB (sepm.py:28-51) of every row; ``sepm``'s ``"ssnr"``."""
+    return sepm(clean, processed, sr, **kw)["ssnr"]
+
+
+def llr(clean: Audio, processed: Audio, sr: int, **kw) -> torch.Tensor:
+    """Log-likelihood ratio (sepm.py:200-277) of every row; ``sepm``'s ``"llr"``."""
+    return sepm(clean, processed, sr, **kw)["llr"]
+
+
+def wss(clean: Audio, processed: Audio, sr: int, **kw) -> torch.Tensor:
+    """Weighted spectral slope (sepm.py:280-487) of every row; ``sepm``'s ``"wss"``."""
+    return sepm(clean, processed, sr, **kw)["wss"]
+
+
+def fw_seg_snr(clean: Audio, processed: Audio, sr: int, **kw) -> torch.Tensor:
+    """Frequency-weighted segmental SNR in dB (sepm.py:54-182) of every row; ``sepm``'s ``"fwsnr"``."""
+    return sepm(clean, processed, sr, **kw)["fwsnr"]
+
+
+def composite(clean: Audio, processed: Audio, sr: int, pesq=None, lengths=None, dtype: torch.dtype = torch.float32,
+              workspace: Optional[torch.Tensor] = None) -> Dict[str, torch.Tensor]:
+    """The composite measures (sepm.py:490-510) of every row: ``{"pesq", "csig", "cbak", "covl", "ssnr", "llr", "wss"}``, each ``[B]`` on the
+    device; CSIG / CBAK / COVL limited to [1, 5].  ``pesq``: a ``[B]`` tensor or sequence of wide-band PESQ MOS values computed elsewhere —
+    P.862 is not in the reference's own code (it calls the third-party ``pesq`` package), so it is not computed here.  With ``pesq=None``,
+    ``pesq``, ``csig``, ``cbak`` and ``covl`` are NaN and the rest is filled."""
+    m = sepm(clean, processed, sr, lengths=lengths, dtype=torch.float64, workspace=workspace)
+    B = int(m["ssnr"].shape[0])
+    dev = m["ssnr"].device
+    if pesq is None:
+        p = torch.full((B,), float("nan"), dtype=torch.float64, device=dev)
+    else:
+        p = torch.as_tensor(pesq, dtype=torch.float64).reshape(-1).to(dev)
+        if int(p.shape[0]) != B:
+            raise ValueError(f"composite: pesq has {int(p.shape[0])} entries for {B} rows")
+
+    def lim(v):   # np.min((5, np.max((1, v)))): a NaN stays
+        return torch.where(torch.isnan(v), v, v.clamp(1.0, 5.0))
+
+    res = {"pesq": p,
+           "csig": lim(3.093 - 1.029 * m["llr"] + 0.603 * p - 0.009 * m["wss"]),
+           "cbak": lim(1.634 + 0.478 * p - 0.007 * m["wss"] + 0.063 * m["ssnr"]),
+           "covl": lim(1.594 + 0.805 * p - 0.512 * m["llr"] - 0.007 * m["wss"]),
+           "ssnr": m["ssnr"], "llr": m["llr"], "wss": m["wss"]}
+    return {k: v.to(dtype) for k, v in res.items()}
+
+
 def _check(rc: int) -> None:
     """Argument errors of the C calls are ValueErrors here; everything else stays a DfxError."""
     if rc == _lib.DFX_ERR_INVALID_ARG:
@@ -131,10 +214,14 @@ def _check(rc: int) -> None:
     _lib.check(rc)
 
 
-def score_files(pairs: Sequence[Tuple[str, str]], sr: Optional[int] = None, batch_seconds: float = 600.0) -> List[Dict[str, float]]:
+SEPM_KEYS = ("ssnr", "llr", "wss", "fwsnr")
+
+
+def score_files(pairs: Sequence[Tuple[str, str]], sr: Optional[int] = None, batch_seconds: float = 600.0, composite: bool = False) -> List[Dict[str, float]]:
     """``[(clean file, enhanced file)]`` -> ``[{"sisdr": dB, "stoi": value}]`` in input order.  Both files of a pair are loaded with ``load_audio`` at
     ``sr`` (default: the clean file's own rate), their first channel cut to the shorter of the two; pairs of equal rate are sorted by length
-    and scored in batches of at most ``batch_seconds`` of padded audio, so that clips of similar length share a pass."""
+    and scored in batches of at most ``batch_seconds`` of padded audio, so that clips of similar length share a pass.  ``composite=True`` adds
+    ``ssnr``, ``llr``, ``wss`` and ``fwsnr`` (``sepm``; computed at 16 kHz, as ``evaluation_loop_dir_only`` does)."""
     items = []
     for i, (cf, ef) in enumerate(pairs):
         c, meta = load_audio(cf, sr, verbose=False)
@@ -154,6 +241,10 @@ def score_files(pairs: Sequence[Tuple[str, str]], sr: Optional[int] = None, batc
         sd, st = si_sdr(cs, es).cpu().tolist(), stoi(cs, es, rate).cpu().tolist()
         for b, u, v in zip(batch, sd, st):
             res[b[2]] = {"sisdr": float(u), "stoi": float(v)}
+        if composite:
+            m = {k: v.cpu().tolist() for k, v in sepm(cs, es, rate, dtype=torch.float64).items()}
+            for j, b in enumerate(batch):
+                res[b[2]].update({k: float(m[k][j]) for k in SEPM_KEYS})
         at = end
     return res  # type: ignore[return-value]
 
@@ -182,10 +273,12 @@ def main(argv=None) -> int:
     ap.add_argument("enhanced_dir")
     ap.add_argument("--sr", type=int, default=None, help="score at this rate (default: each clean file's own; evaluation_loop_dir_only uses 16000)")
     ap.add_argument("--csv", default=None, help="write one line per file here")
+    ap.add_argument("--composite", action="store_true", help="add segmental SNR, LLR, WSS and frequency-weighted segmental SNR (df/sepm.py)")
     args = ap.parse_args(argv)
     pairs = pair_directories(args.clean_dir, args.enhanced_dir)
-    scores = score_files(pairs, sr=args.sr)
-    lines = ["file,sisdr,stoi"] + [f"{os.path.basename(c)},{s['sisdr']:.6f},{s['stoi']:.6f}" for (c, _), s in zip(pairs, scores)]
+    scores = score_files(pairs, sr=args.sr, composite=args.composite)
+    cols = ("sisdr", "stoi") + (SEPM_KEYS if args.composite else ())
+    lines = ["file," + ",".join(cols)] + [os.path.basename(c) + "".join(f",{s[k]:.6f}" for k in cols) for (c, _), s in zip(pairs, scores)]
     if args.csv:
         with open(args.csv, "w") as f:
             f.write("\n".join(lines) + "\n")

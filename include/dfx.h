@@ -650,6 +650,27 @@ int dfx_stoi_workspace_bytes(int fs_source, int64_t B, const int64_t *lengths_ho
 int dfx_stoi(const dfx_resampler *r, const float *clean, const float *degraded, int64_t B, int64_t stride, const int64_t *lengths_host,
              float *out, int32_t *info, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* The composite measures' parts (df/sepm.py; evaluation_utils.py's third default metric, "composite", without PESQ, which the reference takes
+ * from the third-party pesq package):
+ *   dfx_sepm     of every row, at 16 kHz (r: a dfx_resampler fs_source -> 16000, the reference's sinc_fast, evaluation_utils.py:32,583-584, every
+ *                row with its own length; NULL: the rows are at 16 kHz already), in float64 as sepm.py computes them:
+ *                  out[b][0]  SNRseg    (sepm.py:28-51)    mean over the frames of 10 log10(sum c^2 / (sum (c - p)^2 + eps) + eps) in [-10, 35]
+ *                  out[b][1]  llr       (sepm.py:200-277)  lags 0..16, Levinson with max(E, eps), a and R rounded to float32, the two quadratic
+ *                                                          forms IN FLOAT64 (the reference: float32, in its BLAS's order; 2e-8 .. 3e-7 apart
+ *                                                          for noise-like clips, up to 4e-3 for strongly tonal ones, where the float32 value is
+ *                                                          the inexact one), frac <= 0 -> 1000, log; mean of the K smallest
+ *                  out[b][2]  wss       (sepm.py:280-487)  25 critical bands of the 1024-point spectrum, -100 dB clip, findLocPeaks; mean of the
+ *                                                          K smallest
+ *                  out[b][3]  fwSNRseg  (sepm.py:54-182)   mean over the frames, each in [-10, 35]
+ *                480-sample frames at hop 120: a row of n samples at 16 kHz has F = (n - 480) / 120 of them, K = round_half_even(0.95 F) (host,
+ *                double).  F < 1 (n < 600), where the reference raises or averages nothing: all four NaN.  info: NULL, or DEVICE int32 [B][2]: F, K.
+ * clean / processed, lengths_host, the workspace, the stream and the row-alone guarantee: as dfx_stoi; out: DEVICE float64 [B][4].
+ * DFX_ERR_INVALID_ARG: null pointers, a length outside [0, stride], a workspace that is too small, a resampler to another rate than 16 kHz. */
+int dfx_sepm_workspace_bytes(int fs_source, int64_t B, const int64_t *lengths_host, int64_t *bytes);
+int dfx_sepm(const dfx_resampler *r, const float *clean, const float *processed, int64_t B, int64_t stride, const int64_t *lengths_host,
+             double *out /* [B, 4]: ssnr, llr, wss, fwsnr */, int32_t *info /* [B, 2] or NULL: F, K */, void *workspace, int64_t workspace_bytes,
+             void *stream);
+
 /* ------------------------------------------------------------------------------------------------------------------
  * Per-kernel timing (measurement aid, no reference counterpart; the reference only logs wall-clock RTF,
  * DeepFilterNet/df/enhance.py:77-87).  When a kernel's bit is set in `kernel_mask`, every launch of it is bracketed by
